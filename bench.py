@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: device-resident radix sort of 1 B uniform-random u32 keys per GPU
-(BASELINE.json configs[1]), Gkeys/s, with the dominant kernel's HBM roofline and a CPU baseline.
+(BASELINE.json configs[1]), Gkeys/s; with --full also the dominant kernel's HBM roofline and a CPU baseline.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype u32|u64|f32]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype u32|u64|f32] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 A bare `python bench.py --gpus N` (N > 1, no WORLD_SIZE in the environment) starts its own N ranks as fresh child
 processes (torch.distributed.run, 127.0.0.1) BEFORE anything touches the GPU, waits, and exits with their code; rank 0's
@@ -12,10 +12,18 @@ A step = one sort of the workload.  N == 1: `rdst_hip_sort_device` on 10^9 keys 
 N > 1 (weak scaling, BASELINE configs[4] "C5": u64 keys unless --dtype says otherwise): every rank holds 10^9 keys;
 one step = the sharded route (local top-digit histogram, all-gather of the 256 counts, top-digit scatter,
 all-to-all over RCCL/xGMI, local sort) — value = N * 10^9 * K keys / wall time.  Every step sorts a fresh unsorted copy that was
-placed in HBM before the timed region (no copies inside it).
+placed in HBM before the timed region (no copies inside it); when K + W copies do not fit in HBM, a pool of them that does is
+refilled between rounds of timed steps, outside the clock.
 
-The JSON line also carries (protocol of SURVEY.md §8(d) / BASELINE.md §3-4):
-  median_ms_per_step  median of the K steps (HIP events around each step, same stream) beside the mean
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the JSON line: metric, value (Gkeys/s),
+unit, higher_is_better, dtype, ms_per_step (wall time of the timed steps / K), median_ms_per_step (HIP events around each step,
+same stream), the route and the sort-level HBM figures derived from them.
+
+--dump-outputs DIR writes what the last timed step returned, the sorted keys, as .npy files (see dump_outputs).  The inputs
+are generated from fixed seeds, so two runs with the same arguments sort the same keys.
+
+--full adds everything else (protocol of SURVEY.md §8(d) / BASELINE.md §3-4); its timed steps record HIP events between
+their kernel launches, and the last output is checked (sorted, and a permutation of the input):
   roofline       the dominant kernel (K3, one scatter pass): algorithmic bytes per launch (2k per key: one
                  read + one write) / its average launch duration over the launches that moved keys, taken
                  with HIP events recorded between launches on the kernels' stream, inside the timed region
@@ -30,6 +38,8 @@ The JSON line also carries (protocol of SURVEY.md §8(d) / BASELINE.md §3-4):
   end_to_end     `rdst_hip_sort` on a host slice of the same workload (PCIe both ways) — never `value`
   cpu_baseline   the oracle (C restatement of rdst's StandardTuner route, OpenMP) timed on this box's host
                  cores on THE SAME ARRAY the GPU leg sorted; the two outputs are compared bit for bit
+  sharded_breakdown  N > 1: where a sharded step's time goes, stage by stage (max over ranks), and one shard sorted alone
+--no-extras, --no-big and --no-cpu-baseline leave parts of a --full run out.
 """
 import argparse
 import json
@@ -318,12 +328,24 @@ ROUTE_TEXT = {
 }
 
 
-def timed_sorts(torch, rdst_amd, src, name, K, W, step=None, fence=None, in_place=True):
+def pool_size(torch, src, want):
+    """How many unsorted copies of `src` to hold at once: all `want` when they fit in the HBM left after what the sort and
+    the checks need beside them (tmp, the library's workspace — 1.7 x the slice on the byte-saving routes —, a full-size
+    temporary of the checks, 8 GiB of slack), else as many as do."""
+    free, _total = torch.cuda.mem_get_info()
+    spare = free - 6 * src.nbytes - 8 * 2**30
+    return int(max(1, min(want, spare // max(1, src.nbytes))))
+
+
+def timed_sorts(torch, rdst_amd, src, name, K, W, step=None, fence=None, in_place=True, profile=True):
     """W warm-up + K timed sorts of fresh copies of `src` (already in HBM).  Returns (elapsed s, per-step ms,
-    profiled run indices, last output).  in_place=False: `step` leaves its input alone (the sharded sort returns a new
-    tensor), so every step reads `src` itself — 25 copies of a 10^9-key u64 shard would be 200 GB per GPU."""
+    profiled run indices, last output, buffers, tmp).  The copies are made before the clock starts; when K + W of them do not
+    fit in HBM (pool_size), the pool is refilled from `src` between rounds of timed steps, each round clocked on its own and
+    the clock stopped while refilling.  in_place=False: `step` leaves its input alone (the sharded sort returns a new tensor),
+    so every step reads `src` itself — 25 copies of a 10^9-key u64 shard would be 200 GB per GPU.  profile: HIP events
+    between the launches of every timed step (kernel_table reads them)."""
     view_dt = getattr(torch, DTYPES[name][0])
-    bufs = [src.clone().view(view_dt) for _ in range(K + W)] if in_place else [src.view(view_dt)] * (K + W)
+    bufs = [src.clone().view(view_dt) for _ in range(pool_size(torch, src, K + W))] if in_place else [src.view(view_dt)]
     tmp = torch.empty_like(bufs[0])
     if step is None:
         def step(buf):  # noqa: E306
@@ -331,23 +353,93 @@ def timed_sorts(torch, rdst_amd, src, name, K, W, step=None, fence=None, in_plac
             return buf
     if fence is None:
         fence = torch.cuda.synchronize
+    used = 0   # buffers of the pool sorted since it was last filled
+
+    def next_round(left):
+        """the buffers of the next round of at most `left` steps: unsorted copies, refilled (outside any clock) when all are used"""
+        nonlocal used
+        if not in_place:
+            return bufs * left
+        if used == len(bufs):
+            for b in bufs:
+                b.view(src.dtype).copy_(src)
+            fence()
+            used = 0
+        batch = bufs[used:used + left]
+        used += len(batch)
+        return batch
+
     out = None
-    for i in range(W):
-        out = step(bufs[i])
+    left = W
+    while left:
+        batch = next_round(left)
+        left -= len(batch)
+        for b in batch:
+            out = step(b)
     fence()
-    rdst_amd.set_profiling(True)   # HIP events between the launches of every timed step
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(K + 1)]
-    t0 = time.perf_counter()
-    ev[0].record()
-    for i in range(K):
-        out = step(bufs[W + i])
-        ev[i + 1].record()
-    fence()
-    elapsed = time.perf_counter() - t0
+    if profile:
+        rdst_amd.set_profiling(True)   # HIP events between the launches of every timed step
+    elapsed, per_step, left = 0.0, [], K
+    while left:
+        batch = next_round(left)
+        left -= len(batch)
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(len(batch) + 1)]
+        t0 = time.perf_counter()
+        ev[0].record()
+        for i, b in enumerate(batch):
+            out = step(b)
+            ev[i + 1].record()
+        fence()
+        elapsed += time.perf_counter() - t0
+        per_step += [ev[i].elapsed_time(ev[i + 1]) for i in range(len(batch))]
     rdst_amd.device_status()       # any kernel failure of any step (the error word is sticky) raises here
-    runs = list(range(rdst_amd.profile_runs()))
-    per_step = [ev[i].elapsed_time(ev[i + 1]) for i in range(K)]
+    runs = list(range(rdst_amd.profile_runs())) if profile else []
     return elapsed, per_step, runs, out, bufs, tmp
+
+
+DUMP_SAMPLE = 1 << 21   # positions of the sorted output --dump-outputs writes (per GPU: divided by the number of ranks)
+DUMP_CHUNK = 1 << 20    # keys per chunk sum: 2^20 32-bit words add up to less than 2^53, exact in float64
+
+
+def dump_outputs(torch, out, name, directory, rank=0, world=1):
+    """--dump-outputs: what the last timed step returned to its caller, the sorted keys, as .npy files (under 64 MB in all):
+      sorted_keys_sample.npy      the keys at a fixed, seeded sample of positions: u32 as float64, f32 as float32, u64 as
+                                  float64 of shape (m, 2) holding the high and low 32-bit halves (all exact)
+      sample_positions.npy        those positions, ascending (float64)
+      sorted_keys_chunk_sums.npy  sums of the keys' 32-bit words (4-byte keys: the bit pattern; u64: (c, 2), high and low
+                                  halves) over consecutive chunks of DUMP_CHUNK keys that cover the whole output (float64, exact)
+    With --gpus N > 1 every rank writes its own shard's files, named rank<r>_*.npy."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    prefix = f"rank{rank}_" if world > 1 else ""
+    kb = DTYPES[name][2]
+    x = out.view(torch.int32 if kb == 4 else torch.int64)
+    n = x.numel()
+    m = min(n, DUMP_SAMPLE // world)
+    pos = np.sort(np.random.default_rng(0x5D5700D0 + rank).integers(0, n, size=m)) if n else np.zeros(0, np.int64)
+    vals = x[torch.from_numpy(pos).to(x.device)].cpu().numpy()
+    if name == "f32":
+        sample = vals.view(np.float32)
+    elif kb == 4:
+        sample = vals.view(np.uint32).astype(np.float64)
+    else:
+        u = vals.view(np.uint64)
+        sample = np.stack((u >> np.uint64(32), u & np.uint64(0xFFFFFFFF)), 1).astype(np.float64)
+    sums = []
+    slab = 64 * DUMP_CHUNK   # bounded temporaries: int64 words of 64 chunks at a time
+    for s in range(0, n, slab):
+        c = x[s:s + slab].to(torch.int64)
+        w = (c & 0xFFFFFFFF).unsqueeze(1) if kb == 4 else torch.stack(((c >> 32) & 0xFFFFFFFF, c & 0xFFFFFFFF), 1)
+        full = w.shape[0] // DUMP_CHUNK * DUMP_CHUNK
+        sums.append(w[:full].view(-1, DUMP_CHUNK, w.shape[1]).sum(1))
+        if full < w.shape[0]:
+            sums.append(w[full:].sum(0, keepdim=True))
+    sums = torch.cat(sums).cpu().numpy() if sums else np.zeros((0, kb // 4), np.int64)
+    if kb == 4:
+        sums = sums[:, 0]
+    np.save(os.path.join(directory, prefix + "sorted_keys_sample.npy"), sample)
+    np.save(os.path.join(directory, prefix + "sample_positions.npy"), pos.astype(np.float64))
+    np.save(os.path.join(directory, prefix + "sorted_keys_chunk_sums.npy"), sums.astype(np.float64))
 
 
 def main():
@@ -358,11 +450,18 @@ def main():
     ap.add_argument("--keys", type=int, default=KEYS_PER_GPU, help="keys per GPU (default: the BASELINE workload)")
     ap.add_argument("--dtype", choices=sorted(DTYPES), default=None,
                     help="key type of the timed region (default: the headline u32 at N == 1; u64 — BASELINE configs[4], C5 — at N > 1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the other configs, the copy ceiling and the end-to-end leg")
-    ap.add_argument("--no-big", action="store_true", help="skip the 8 * 10^9-key u64 config (needs ~220 GB of HBM)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the sorted keys of the last timed step to DIR as .npy files (a fixed sample and chunk sums)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the per-kernel table and roofline, the output check, the copy ceiling, the other configs and sizes, "
+                         "end to end, the CPU baseline (N > 1: the stage breakdown)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the other configs, the copy ceiling and the end-to-end leg")
+    ap.add_argument("--no-big", action="store_true", help="with --full: skip the 8 * 10^9-key u64 config (needs ~220 GB of HBM)")
     ap.add_argument("--route", choices=("auto", "lsd"), default="auto", help="lsd: never take the hybrid route (A/B)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # no launcher around us: become one.  Nothing in this process has touched the GPU (torch is not even imported).
@@ -410,16 +509,22 @@ def main():
 
     src = gen_keys(torch, n, name, seed + rank)
     step = (lambda buf: sharded_sort(buf)) if distributed else None
-    elapsed, per_step, runs, out, bufs, tmp = timed_sorts(torch, rdst_amd, src, name, K, W, step=step, fence=fence, in_place=not distributed)
+    elapsed, per_step, runs, out, bufs, tmp = timed_sorts(torch, rdst_amd, src, name, K, W, step=step, fence=fence,
+                                                          in_place=not distributed, profile=args.full)
     route = rdst_amd.last_route()
-    kernels = kernel_table(rdst_amd, runs, n if not distributed else out.numel(), kb, levels)
-    rdst_amd.set_profiling(False)
+    if args.dump_outputs:
+        dump_outputs(torch, out, name, args.dump_outputs, rank, world)
+    kernels = None
+    if args.full:
+        kernels = kernel_table(rdst_amd, runs, n if not distributed else out.numel(), kb, levels)
+        rdst_amd.set_profiling(False)
 
     breakdown = None
     if distributed:
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda" if backend == "nccl" else "cpu")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if distributed and args.full:
         # outside the clock: where a sharded step's time goes (two more steps with events between the stages; max over ranks), and
         # what one rank's shard costs on its own GPU without the exchange (the same dtype: the N = 1 line of this bench is u32)
         stages = ("split", "counts_and_plan", "exchange", "local_sort")
@@ -445,18 +550,19 @@ def main():
                      "what": "events between the stages of one more sharded step (outside the clock); the last two figures: this "
                              "dtype's single-GPU sort of one rank's shard, no exchange"}
 
-    # sanity of the last result (outside the clock): sorted, and (single GPU) the same multiset as its input
     itype = torch.int32 if kb == 4 else torch.int64
-    assert is_sorted(torch, mapped_signed(torch, out.view(itype), name)), "output not sorted"
-    if not distributed:
-        assert int(out.view(itype).sum()) == int(src.sum()), "checksum differs: not a permutation of the input"
+    if args.full:
+        # sanity of the last result (outside the clock): sorted, and (single GPU) the same multiset as its input
+        assert is_sorted(torch, mapped_signed(torch, out.view(itype), name)), "output not sorted"
+        if not distributed:
+            assert int(out.view(itype).sum()) == int(src.sum()), "checksum differs: not a permutation of the input"
 
     total_keys = n * world * K
     value = total_keys / elapsed / 1e9
     ms_per_step = elapsed / K * 1e3
     roof = None
     # the dominant kernel: the scatter pass — K3 (onesweep_kernel) on the LSD and hybrid routes, msd_scatter_kernel on the atomic one
-    dom = [k for k in ("msd_pass_a", "pass") if k in kernels and "GBps" in kernels[k]][:1]
+    dom = [k for k in ("msd_pass_a", "pass") if k in kernels and "GBps" in kernels[k]][:1] if args.full else []
     if dom:
         launches = sum(kernels[k]["launches"] for k in dom)
         avg_ms = sum(kernels[k]["avg_ms"] * kernels[k]["launches"] for k in dom) / launches
@@ -494,13 +600,13 @@ def main():
                        "keys_per_gpu": n, "total_keys": n * world, "seed": seed, "route": route,
                        "parallelism": f"shard{world}" if distributed else "single"},
             **sort_level_fields(route, kb, levels, total_keys / elapsed / world),
-            "roofline": roof,
-            "kernels": kernels,
         }
+        if args.full:
+            line.update(roofline=roof, kernels=kernels)
         if breakdown:
             line["sharded_breakdown"] = breakdown
 
-    if rank == 0 and not distributed:
+    if rank == 0 and not distributed and args.full:
         # ---- outside the timed region: copy ceiling, the other BASELINE configs, end to end, CPU leg
         gpu_sorted_host = None
         host_keys = None
@@ -622,7 +728,7 @@ def main():
             line.setdefault("configs", {})["other_sizes"] = size_points(torch, rdst_amd)
             line.setdefault("configs", {})["u64_8e9"] = big_u64_config(torch, rdst_amd, 8 * KEYS_PER_GPU)
         line["cpu_baseline"] = None if args.no_cpu_baseline else cpu_baseline(host_keys, gpu_sorted_host)
-    elif rank == 0:
+    elif rank == 0 and args.full:
         line["cpu_baseline"] = None
     if rank == 0:
         print(json.dumps(line), flush=True)

@@ -5,6 +5,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -61,3 +63,12 @@ def test_main_spawns_before_touching_torch(monkeypatch):
     except SystemExit as e:
         assert e.code == 0
     assert called["n"] == 2 and called["argv"] == ["--gpus", "2", "--steps", "1", "--warmup", "0"]
+
+
+def test_steps_and_warmup_are_validated_before_torch(monkeypatch):
+    bench = _load_bench()
+    for argv in (["--steps", "0"], ["--warmup", "-1"]):
+        monkeypatch.setattr(sys, "argv", ["bench.py", *argv])
+        with pytest.raises(SystemExit) as e:
+            bench.main()
+        assert e.value.code == 2

@@ -8,7 +8,7 @@ sys.path.insert(0, %r)
 from rdst_amd import _lib
 _lib.LIB_PATH = %r
 import runpy
-sys.argv = ["bench.py", "--no-cpu-baseline", "--steps", "6", "--warmup", "2"]
+sys.argv = ["bench.py", "--full", "--no-cpu-baseline", "--steps", "6", "--warmup", "2"]
 runpy.run_path(%r, run_name="__main__")
 '''
 for rep in range(3):

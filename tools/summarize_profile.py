@@ -58,7 +58,7 @@ json.dump(out, open(f"profiles/{tag}_pmc_summary.json", "w"), indent=1, sort_key
 
 # HBM traffic per launch (MI355X_MICROARCH.md, HBM section: FETCH_SIZE / WRITE_SIZE are in KiB; on gfx950 FETCH_SIZE reports half
 # of the bytes of a coalesced streaming read — TCC_EA0_RDREQ counted at 64 B although requests are 128 B —: double it)
-traffic = {"source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of `python bench.py --steps 3 --warmup 1 --no-extras --no-cpu-baseline`, profile tag {tag}",
+traffic = {"source": f"rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE (separate passes) of `python bench.py --steps 3 --warmup 1 --full --no-extras --no-cpu-baseline`, profile tag {tag}",
            "correction": "FETCH_SIZE doubled (gfx950 counts 128-B read requests as 64 B); WRITE_SIZE as reported; both KiB -> bytes",
            "kernels": {}}
 for k, v in sorted(out.items()):
