@@ -44,7 +44,7 @@ struct RadixKey<T, std::enable_if_t<std::is_integral_v<T> && !std::is_same_v<T, 
 template <> struct RadixKey<float> { static constexpr std::size_t LEVELS = 4; static constexpr rdst_key_kind kind = RDST_KEY_FLOAT; };
 template <> struct RadixKey<double> { static constexpr std::size_t LEVELS = 8; static constexpr rdst_key_kind kind = RDST_KEY_FLOAT; };
 template <std::size_t N>
-struct RadixKey<std::array<std::uint8_t, N>, std::enable_if_t<(N >= 1 && N <= 16)>> {  // [u8; N], src/radix_key_impl.rs:78-85: lexicographic
+struct RadixKey<std::array<std::uint8_t, N>, std::enable_if_t<(N >= 1 && N <= RDST_BYTES_MAX_N)>> {  // [u8; N], src/radix_key_impl.rs:78-85: lexicographic
     static constexpr std::size_t LEVELS = N;
     static constexpr rdst_key_kind kind = RDST_KEY_BYTES_BE;
 };
@@ -159,11 +159,13 @@ template <typename T> void radix_sort_unstable(T* data, std::size_t len) { radix
 
 // A slice of structs whose key is one built-in field — what `impl RadixKey for LargeStruct` with
 // `get_level` = the field's expresses in the reference (benches/struct_sort.rs:11-27,
-// examples/impl_radix_key.rs:32-56).  Rows with equal keys keep their order.
+// examples/impl_radix_key.rs:32-56).  Rows with equal keys keep their order.  The field is a 4- or 8-byte built-in
+// key, or a std::array<std::uint8_t, N> (a [u8; N] key, N up to RDST_BYTES_MAX_N, at any offset).
 template <typename T, typename KeyT>
 void radix_sort_unstable_by_field(T* data, std::size_t len, KeyT T::*field) {
     static_assert(std::is_trivially_copyable<T>::value, "rows are moved as bytes");
-    static_assert(sizeof(KeyT) == 4 || sizeof(KeyT) == 8, "the device route takes 4- or 8-byte key fields");
+    static_assert(RadixKey<KeyT>::kind == RDST_KEY_BYTES_BE || sizeof(KeyT) == 4 || sizeof(KeyT) == 8,
+                  "the device route takes 4- or 8-byte key fields and [u8; N] fields");
     if (len <= 1) return;
     const std::size_t offset = static_cast<std::size_t>(reinterpret_cast<const char*>(&(data[0].*field)) - reinterpret_cast<const char*>(&data[0]));
     const int rc = rdst_hip_sort_records(data, len, sizeof(T), static_cast<std::uint32_t>(offset), sizeof(KeyT), RadixKey<KeyT>::kind, nullptr);

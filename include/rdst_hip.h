@@ -38,13 +38,14 @@ typedef enum {
     RDST_KEY_SIGNED   = 1, /* i8..i64: ((self ^ MIN) >> level*8) as u8  radix_key_impl.rs:87-160 */
     RDST_KEY_FLOAT    = 2, /* f32/f64: sign-magnitude flip, then ^ MIN  radix_key_impl.rs:162-185 */
     RDST_KEY_BYTES_BE = 3  /* [u8; N]: self[N - 1 - level], i.e. lexicographic  radix_key_impl.rs:78-85;
-                              N = elem_bytes = levels in 1..16, host entry point only */
+                              N = elem_bytes = levels in 1..RDST_BYTES_MAX_N: rdst_hip_sort, rdst_hip_sort_records (a key
+                              field) and the device entry rdst_hip_sort_bytes_device */
 } rdst_key_kind;
 
 typedef enum {
     RDST_OK              = 0,
     RDST_ERR_ARG         = -1, /* bad pointer / size / kind / levels (LEVELS == 0 panics in rdst: radix_sort_builder.rs:22) */
-    RDST_ERR_UNSUPPORTED = -2, /* element width / kind not built for the device path (built: 1-, 2-, 4-, 8-, 16-byte integers, f32, f64, [u8; 1..16] through rdst_hip_sort) */
+    RDST_ERR_UNSUPPORTED = -2, /* element width / kind not built for the device path (built: 1-, 2-, 4-, 8-, 16-byte integers, f32, f64, [u8; 1..RDST_BYTES_MAX_N] through rdst_hip_sort) */
     RDST_ERR_HIP         = -3, /* a HIP runtime call failed; see rdst_hip_last_error() */
     RDST_ERR_NO_DEVICE   = -4, /* no usable gfx950 device */
     RDST_ERR_DEVICE      = -5, /* a kernel reported failure through the workspace error word (bounded spin expired) */
@@ -149,7 +150,9 @@ int rdst_hip_sort_device(void* dev_keys, void* dev_tmp, uint64_t len, uint32_t e
  * `get_level` = the field's; examples/impl_radix_key.rs:32-56).  `record_bytes` = size_of::<T>(),
  * the key is `key_bytes` (4 or 8) at `key_offset`, naturally aligned; rows travel to the device,
  * (key, row index) pairs are sorted there, the rows gathered and copied back.  Rows with equal
- * keys keep their input order (rdst promises none).  Blocking; on failure the slice is untouched. */
+ * keys keep their input order (rdst promises none).  Blocking; on failure the slice is untouched.
+ * kind == RDST_KEY_BYTES_BE: the key is a [u8; N] field, key_bytes = N in 1..RDST_BYTES_MAX_N, at any
+ * offset in rows of any size (no alignment rule), len < 2^32; ordered as rdst_hip_sort_bytes_device orders rows. */
 int rdst_hip_sort_records(void* host_records, uint64_t len, uint32_t record_bytes, uint32_t key_offset,
                           uint32_t key_bytes, rdst_key_kind kind, const rdst_hip_opts* opts);
 
@@ -165,6 +168,20 @@ int rdst_hip_sort_records(void* host_records, uint64_t len, uint32_t record_byte
 int rdst_hip_sort_pairs_device(void* dev_keys, void* dev_vals, void* dev_tmp_keys, void* dev_tmp_vals,
                                uint64_t len, uint32_t key_bytes, rdst_key_kind kind, uint32_t levels,
                                uint32_t val_bytes, void* stream);
+
+/* [u8; N] rows (N = n_bytes in 1..RDST_BYTES_MAX_N), device-resident, sorted IN PLACE in lexicographic order
+ * (src/radix_key_impl.rs:78-85).  No alignment requirement on dev_rows.  dev_scratch: at least
+ * rdst_hip_sort_bytes_scratch_bytes(len, n_bytes) bytes, 256-byte aligned.  len <= 1: no-op.
+ * N <= 16: the rows are widened to 4-, 8- or 16-byte integers and take the integer route; asynchronous on `stream`.
+ * N > 16 (needs len < 2^32, else RDST_ERR_UNSUPPORTED): one stable (u64 prefix, u32 row) pair sort, then rounds over
+ * the rows still tied — short runs by a comparison kernel, long ones by another pair sort on (run, next bytes) — and a
+ * gather of the rows.  BLOCKING: the tie counts of every round come to the host (one copy and one wait per
+ * round; keys that differ in their first 8 bytes take exactly one).  Equal rows keep their input order.  Kernel failures
+ * are reported by rdst_hip_device_status. */
+#define RDST_BYTES_MAX_N 4096u
+int rdst_hip_sort_bytes_device(void* dev_rows, uint64_t len, uint32_t n_bytes,
+                               void* dev_scratch, uint64_t scratch_bytes, void* stream);
+uint64_t rdst_hip_sort_bytes_scratch_bytes(uint64_t len, uint32_t n_bytes);   /* 0 for n_bytes outside 1..RDST_BYTES_MAX_N */
 
 /* Blocks until everything queued on `stream` by this library has finished and returns
  * RDST_ERR_DEVICE if any kernel raised the device error word since the last check.  The word is kept

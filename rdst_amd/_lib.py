@@ -13,6 +13,7 @@ LIB_PATH = os.environ.get("RDST_HIP_LIB") or os.path.join(_HERE, "librdst_hip.so
 
 RDST_KEY_UNSIGNED, RDST_KEY_SIGNED, RDST_KEY_FLOAT, RDST_KEY_BYTES_BE = 0, 1, 2, 3
 RDST_OK = 0
+RDST_BYTES_MAX_N = 4096  # longest [u8; N] key the device route takes (include/rdst_hip.h)
 
 # every symbol include/rdst_hip.h declares; tests check that the library exports all of them
 SYMBOLS = (
@@ -24,6 +25,8 @@ SYMBOLS = (
     "rdst_hip_host_timing",
     "rdst_hip_sort_pairs_device",
     "rdst_hip_sort_records",
+    "rdst_hip_sort_bytes_device",
+    "rdst_hip_sort_bytes_scratch_bytes",
     "rdst_hip_device_status",
     "rdst_hip_level_counts",
     "rdst_hip_all_level_counts",
@@ -98,6 +101,9 @@ def load():
     lib.rdst_hip_sort_device.argtypes = [vp, vp, u64, u32, ci, u32, vp]
     lib.rdst_hip_sort_pairs_device.argtypes = [vp, vp, vp, vp, u64, u32, ci, u32, u32, vp]
     lib.rdst_hip_sort_records.argtypes = [vp, u64, u32, u32, u32, ci, ctypes.POINTER(HipOptsC)]
+    lib.rdst_hip_sort_bytes_device.argtypes = [vp, u64, u32, vp, u64, vp]
+    lib.rdst_hip_sort_bytes_scratch_bytes.argtypes = [u64, u32]
+    lib.rdst_hip_sort_bytes_scratch_bytes.restype = u64
     lib.rdst_hip_device_status.argtypes = [vp]
     lib.rdst_hip_level_counts.argtypes = [vp, u64, u32, ci, u32, u64p, u8p, u8p, u8p, vp]
     lib.rdst_hip_all_level_counts.argtypes = [vp, u64, u32, ci, u32, u64p, vp]
@@ -123,7 +129,7 @@ def load():
     lib.rdst_hip_stream_fill.argtypes = [vp, u64, vp]
     lib.rdst_hip_last_error.restype = ctypes.c_char_p
     for name in SYMBOLS:
-        if name not in ("rdst_hip_workspace_bytes", "rdst_hip_last_error"):
+        if name not in ("rdst_hip_workspace_bytes", "rdst_hip_sort_bytes_scratch_bytes", "rdst_hip_last_error"):
             getattr(lib, name).restype = ctypes.c_int
     _lib = lib
     return lib

@@ -1,0 +1,588 @@
+// rdst_bytes.hip — [u8; N] keys of any width up to RDST_BYTES_MAX_N on gfx950 (src/radix_key_impl.rs:78-85: level l
+// reads byte N-1-l, so rows sort lexicographically).
+//
+// One core orders the row indices of `n` rows of stride R by the byte string at (off, N) inside each row; the plain
+// [u8; N] entries use off = 0, R = N, the records entry its own stride and offset.  It drives the stable (u64, u32) pair
+// sort of rdst_kernels.hip through its C entry and adds the kernels below:
+//
+//   1. prefix    key[i] = big-endian u64 of key bytes [0, 8) (zero past N), val[i] = i; one stable pair sort.
+//   2. ties      a scan over the sorted keys marks the rows whose key equals a neighbour's, compacts them, numbers their
+//                runs; a second scan over the runs splits them into short and long ones.  Counts go to the host.
+//   3. short     runs of 2..BYTES_SMALL rows whose remaining bytes fit a wave's LDS budget: one wave stages them and
+//                ranks every row by (remaining bytes, row index) — the device twin of rdst's comparative_sort on small
+//                buckets (src/sorts/comparative_sort.rs, src/sorter.rs).
+//   4. long      every other run: key = run ordinal in the top b = ceil(log2(runs)) bits, then as many whole next key
+//                bytes as fit; val = the row's slot; one stable pair sort; the slots map 1:1 back onto the runs'
+//                positions.  Back to 2 on the rows still tied, until none are left or every byte is settled.
+//   5. gather    the rows in index order, in the widest unit stride and base alignment allow.
+//
+// Stability: the prefix sort is stable on row indices, every later sort is stable on positions that are in row order
+// within a run, and the comparison kernel breaks ties on the row index — equal keys keep their input order.
+
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include <stddef.h>
+
+#include "rdst_hip.h"
+#include "rdst_internal.h"
+
+namespace {
+
+using rdst_internal::set_error;
+
+constexpr uint32_t ERR_BYTES_RANGE = 8;  // a row index, slot or run read from memory fell out of range: never used to store
+
+constexpr int SCAN_THREADS = 256, SCAN_ITEMS = 16, SCAN_TILE = SCAN_THREADS * SCAN_ITEMS;
+constexpr int SUMS_THREADS = 1024, SUMS_ITEMS = 4;
+constexpr int CMP_WAVES = 4;                 // one run per wave, four waves per workgroup
+constexpr uint32_t BYTES_SMALL = 256;        // longest run the comparison kernel takes (four rows per lane)
+constexpr uint32_t CMP_WORDS = 3840;         // staging budget per wave in u32 words: 4 x (15 KiB keys + 1 KiB rows) = 64 KiB
+constexpr uint32_t GRID_CAP = 256 * 16;      // grid-stride kernels: at most 16 workgroups of 256 per CU
+
+// counters the host reads after the tie step of a round
+enum { CNT_TIED = 0, CNT_RUNS = 1, CNT_LONG_ROWS = 2, CNT_LONG_RUNS = 3, CNT_WORDS = 8 };
+
+__device__ __forceinline__ void raise(uint32_t* err, uint32_t bits) { atomicOr(err, bits); }
+
+__device__ __forceinline__ bool run_is_long(uint32_t len, uint32_t words) {
+    return len > BYTES_SMALL || (uint64_t)len * words > CMP_WORDS;
+}
+
+// key bytes [from, from + k) of the row at p (k <= 8), big-endian, zero past n_bytes
+__device__ __forceinline__ uint64_t load_be(const uint8_t* p, uint32_t from, uint32_t k, uint32_t n_bytes) {
+    const uint8_t* q = p + from;
+    if (k == 8 && from + 8 <= n_bytes) {
+        const uintptr_t a = reinterpret_cast<uintptr_t>(q);
+        if ((a & 7) == 0) return __builtin_bswap64(*reinterpret_cast<const uint64_t*>(q));
+        if ((a & 3) == 0)
+            return ((uint64_t)__builtin_bswap32(*reinterpret_cast<const uint32_t*>(q)) << 32) |
+                   __builtin_bswap32(*reinterpret_cast<const uint32_t*>(q + 4));
+    }
+    uint64_t v = 0;
+    for (uint32_t t = 0; t < k; ++t) {
+        uint32_t b = 0;
+        if (from + t < n_bytes) b = q[t];
+        v = (v << 8) | b;
+    }
+    return v;
+}
+
+// ---- 1 / 4: pair-sort keys --------------------------------------------------------------------------------------------
+// key[j] = (run[j] << (64 - b)) | bytes [depth, depth + k) of row idx[pos[j]] << (64 - b - 8k); val[j] = j.
+// pos == nullptr: row j itself (the prefix round, b = 0).
+__global__ __launch_bounds__(256) void bytes_keys_kernel(const uint8_t* __restrict__ rows, uint32_t stride, uint32_t off,
+                                                         uint32_t n_bytes, uint32_t depth, uint32_t k, uint32_t b,
+                                                         const uint32_t* __restrict__ idx, const uint32_t* __restrict__ pos,
+                                                         const uint32_t* __restrict__ run, uint64_t m, uint64_t n,
+                                                         uint64_t* __restrict__ keys, uint32_t* __restrict__ vals, uint32_t* err) {
+    const uint64_t step = (uint64_t)gridDim.x * 256;
+    const uint32_t low = 64 - b - 8 * k;
+    for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < m; j += step) {
+        uint64_t row = j;
+        if (pos) {
+            const uint32_t p = pos[j];
+            row = p < n ? idx[p] : n;
+            if (row >= n) { raise(err, ERR_BYTES_RANGE); keys[j] = 0; vals[j] = (uint32_t)j; continue; }
+        }
+        uint64_t key = load_be(rows + row * stride + off, depth, k, n_bytes) << low;
+        if (b) key |= (uint64_t)run[j] << (64 - b);
+        keys[j] = key;
+        vals[j] = (uint32_t)j;
+    }
+}
+
+// ---- 2: scans ---------------------------------------------------------------------------------------------------------
+// Reduce-then-scan in three launches over u64 values that pack two counts (low 32 bits, high 32 bits): per-tile sums,
+// one workgroup scans the tile sums, each tile rescans itself and emits.  The item count may live on the device (the
+// run scan): grids are sized for an upper bound, tiles past the end return.
+
+__device__ __forceinline__ uint64_t block_exclusive_scan(uint64_t v, uint64_t* s_w, uint64_t& total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    uint64_t x = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint64_t y = __shfl_up(x, d, 64);
+        if (lane >= d) x += y;
+    }
+    if (lane == 63) s_w[w] = x;
+    __syncthreads();
+    uint64_t before = 0, all = 0;
+    for (int i = 0; i < nw; ++i) {
+        const uint64_t t = s_w[i];
+        if (i < w) before += t;
+        all += t;
+    }
+    __syncthreads();
+    total = all;
+    return before + x - v;
+}
+
+// Tied rows among m sorted keys: tied = equal to a neighbour, head = first of its run.  Value: tied | (tied & head) << 32.
+struct TieOp {
+    const uint64_t* keys;
+    uint64_t m;
+    const uint32_t* cpos;  // slot -> position in the index array (nullptr: identity)
+    uint32_t* out_pos;     // tied row c -> its position
+    uint32_t* out_run;     // tied row c -> its run ordinal
+    uint32_t* run_start;   // run r -> its first tied row; run_start[runs] = tied rows
+    uint64_t* cnt;
+    __device__ uint64_t count() const { return m; }
+    __device__ uint64_t value(uint64_t j) const {
+        const uint64_t k = keys[j];
+        const bool head = j == 0 || keys[j - 1] != k;
+        const bool last = j + 1 == m || keys[j + 1] != k;
+        const bool tied = !(head && last);
+        return (uint64_t)tied | ((uint64_t)(tied && head) << 32);
+    }
+    __device__ void emit(uint64_t j, uint64_t before, uint64_t v) const {
+        if (!(v & 1)) return;
+        const uint32_t c = (uint32_t)before, h = (uint32_t)(before >> 32);
+        const bool head = (v >> 32) != 0;
+        out_pos[c] = cpos ? cpos[j] : (uint32_t)j;
+        out_run[c] = head ? h : h - 1;
+        if (head) run_start[h] = c;
+    }
+    __device__ void finish(uint64_t total) const {
+        const uint32_t tied = (uint32_t)total, runs = (uint32_t)(total >> 32);
+        cnt[CNT_TIED] = tied;
+        cnt[CNT_RUNS] = runs;
+        run_start[runs] = tied;
+    }
+};
+
+// Runs that go to the pair sort (long): value = 1 << 32 | length; the exclusive sums give each long run its ordinal and
+// the first of its compacted rows.
+struct RunOp {
+    const uint32_t* run_start;
+    uint32_t words;       // u32 words of remaining key bytes per row
+    uint64_t* run_scan;   // run r -> exclusive sum
+    uint64_t* cnt;
+    uint64_t max_runs;    // m / 2: what the tables and the grid are sized for
+    __device__ uint64_t count() const { const uint64_t r = cnt[CNT_RUNS]; return r < max_runs ? r : max_runs; }
+    __device__ uint64_t value(uint64_t r) const {
+        const uint32_t len = run_start[r + 1] - run_start[r];
+        return run_is_long(len, words) ? ((1ull << 32) | len) : 0;
+    }
+    __device__ void emit(uint64_t r, uint64_t before, uint64_t) const { run_scan[r] = before; }
+    __device__ void finish(uint64_t total) const {
+        cnt[CNT_LONG_ROWS] = (uint32_t)total;
+        cnt[CNT_LONG_RUNS] = (uint32_t)(total >> 32);
+    }
+};
+
+template <typename Op>
+__global__ __launch_bounds__(SCAN_THREADS) void scan_tiles_kernel(Op op, uint64_t* __restrict__ tile_sums) {
+    __shared__ uint64_t s_w[SCAN_THREADS / 64];
+    const uint64_t m = op.count(), base = (uint64_t)blockIdx.x * SCAN_TILE;
+    if (base >= m) return;
+    const uint64_t first = base + (uint64_t)threadIdx.x * SCAN_ITEMS;
+    uint64_t sum = 0;
+    for (int i = 0; i < SCAN_ITEMS; ++i)
+        if (first + i < m) sum += op.value(first + i);
+    uint64_t total;
+    (void)block_exclusive_scan(sum, s_w, total);
+    if (threadIdx.x == 0) tile_sums[blockIdx.x] = total;
+}
+
+template <typename Op>
+__global__ __launch_bounds__(SUMS_THREADS) void scan_sums_kernel(Op op, uint64_t* __restrict__ tile_sums) {
+    __shared__ uint64_t s_w[SUMS_THREADS / 64];
+    const uint64_t m = op.count(), tiles = (m + SCAN_TILE - 1) / SCAN_TILE;
+    uint64_t carry = 0;
+    for (uint64_t c = 0; c < tiles; c += (uint64_t)SUMS_THREADS * SUMS_ITEMS) {
+        const uint64_t first = c + (uint64_t)threadIdx.x * SUMS_ITEMS;
+        uint64_t v[SUMS_ITEMS], sum = 0;
+        for (int i = 0; i < SUMS_ITEMS; ++i) {
+            v[i] = first + i < tiles ? tile_sums[first + i] : 0;
+            sum += v[i];
+        }
+        uint64_t total;
+        uint64_t run = carry + block_exclusive_scan(sum, s_w, total);
+        for (int i = 0; i < SUMS_ITEMS; ++i) {
+            if (first + i < tiles) tile_sums[first + i] = run;
+            run += v[i];
+        }
+        carry += total;
+    }
+    if (threadIdx.x == 0) op.finish(carry);
+}
+
+template <typename Op>
+__global__ __launch_bounds__(SCAN_THREADS) void scan_emit_kernel(Op op, const uint64_t* __restrict__ tile_sums) {
+    __shared__ uint64_t s_w[SCAN_THREADS / 64];
+    const uint64_t m = op.count(), base = (uint64_t)blockIdx.x * SCAN_TILE;
+    if (base >= m) return;
+    const uint64_t first = base + (uint64_t)threadIdx.x * SCAN_ITEMS;
+    uint64_t v[SCAN_ITEMS], sum = 0;
+    for (int i = 0; i < SCAN_ITEMS; ++i) {
+        v[i] = first + i < m ? op.value(first + i) : 0;
+        sum += v[i];
+    }
+    uint64_t total;
+    uint64_t before = tile_sums[blockIdx.x] + block_exclusive_scan(sum, s_w, total);
+    for (int i = 0; i < SCAN_ITEMS; ++i) {
+        if (first + i < m) op.emit(first + i, before, v[i]);
+        before += v[i];
+    }
+}
+
+// The rows of long runs, compacted in order: long_pos[d] = position, long_run[d] = the run's ordinal among long runs.
+__global__ __launch_bounds__(256) void long_rows_kernel(const uint32_t* __restrict__ tied_pos, const uint32_t* __restrict__ tied_run,
+                                                        const uint32_t* __restrict__ run_start, const uint64_t* __restrict__ run_scan,
+                                                        const uint64_t* __restrict__ cnt, uint32_t words,
+                                                        uint32_t* __restrict__ long_pos, uint32_t* __restrict__ long_run, uint32_t* err) {
+    const uint64_t tied = cnt[CNT_TIED], runs = cnt[CNT_RUNS], long_rows = cnt[CNT_LONG_ROWS];
+    const uint64_t step = (uint64_t)gridDim.x * 256;
+    for (uint64_t c = (uint64_t)blockIdx.x * 256 + threadIdx.x; c < tied; c += step) {
+        const uint32_t r = tied_run[c];
+        if (r >= runs) { raise(err, ERR_BYTES_RANGE); continue; }
+        const uint32_t s0 = run_start[r], len = run_start[r + 1] - s0;
+        if (!run_is_long(len, words)) continue;
+        const uint64_t sc = run_scan[r];
+        const uint64_t d = (uint32_t)sc + (c - s0);
+        if (c < s0 || d >= long_rows) { raise(err, ERR_BYTES_RANGE); continue; }
+        long_pos[d] = tied_pos[c];
+        long_run[d] = (uint32_t)(sc >> 32);
+    }
+}
+
+// ---- 3: short runs ----------------------------------------------------------------------------------------------------
+// One wave per run: the run's remaining key bytes [depth, n_bytes) as big-endian u32 words (zero-padded) and its row
+// indices go to LDS; each lane ranks its rows (at most four) against all others by (bytes, row index) and writes them to
+// their places.  The run's positions are contiguous, so rank = offset from the run's first position.
+__global__ __launch_bounds__(64 * CMP_WAVES) void short_runs_kernel(const uint8_t* __restrict__ rows, uint32_t stride, uint32_t off,
+                                                                     uint32_t n_bytes, uint32_t depth, uint32_t words,
+                                                                     const uint32_t* __restrict__ tied_pos, const uint32_t* __restrict__ run_start,
+                                                                     const uint64_t* __restrict__ cnt, uint32_t* __restrict__ idx, uint64_t n,
+                                                                     uint32_t* err) {
+    __shared__ uint32_t s_key[CMP_WAVES][CMP_WORDS];
+    __shared__ uint32_t s_row[CMP_WAVES][BYTES_SMALL];
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const uint64_t runs = cnt[CNT_RUNS];
+    for (uint64_t base = (uint64_t)blockIdx.x * CMP_WAVES; base < runs; base += (uint64_t)gridDim.x * CMP_WAVES) {
+        const uint64_t r = base + w;
+        uint32_t len = 0, p0 = 0;
+        if (r < runs) {
+            const uint32_t s0 = run_start[r];
+            len = run_start[r + 1] - s0;
+            if (run_is_long(len, words) || len < 2) len = 0;
+            else {
+                p0 = tied_pos[s0];
+                if ((uint64_t)p0 + len > n) { if (lane == 0) raise(err, ERR_BYTES_RANGE); len = 0; }
+            }
+        }
+        bool bad = false;
+        for (uint32_t i = lane; i < len; i += 64) {
+            const uint32_t row = idx[p0 + i];
+            bad |= row >= n;
+            s_row[w][i] = row;
+        }
+        if (__any(bad)) {  // wave-uniform
+            if (lane == 0) raise(err, ERR_BYTES_RANGE);
+            len = 0;
+        }
+        __syncthreads();
+        for (uint32_t t = lane; t < len * words; t += 64) {
+            const uint32_t i = t / words, word = t - i * words;
+            const uint8_t* p = rows + (uint64_t)s_row[w][i] * stride + off;
+            const uint32_t from = depth + 4 * word;
+            uint32_t v = 0;
+            for (uint32_t q = 0; q < 4; ++q) {
+                uint32_t b = 0;
+                if (from + q < n_bytes) b = p[from + q];
+                v = (v << 8) | b;
+            }
+            s_key[w][t] = v;
+        }
+        __syncthreads();
+        uint32_t mine[BYTES_SMALL / 64], rank[BYTES_SMALL / 64];
+#pragma unroll
+        for (int u = 0; u < (int)(BYTES_SMALL / 64); ++u) {
+            const uint32_t i = lane + 64 * u;
+            rank[u] = 0;
+            mine[u] = 0;
+            if (i >= len) continue;
+            const uint32_t* ki = &s_key[w][i * words];
+            const uint32_t ri = s_row[w][i];
+            mine[u] = ri;
+            uint32_t less = 0;
+            for (uint32_t j = 0; j < len; ++j) {
+                if (j == i) continue;
+                const uint32_t* kj = &s_key[w][j * words];
+                int c = 0;
+                for (uint32_t q = 0; q < words && c == 0; ++q) c = kj[q] < ki[q] ? -1 : (kj[q] > ki[q] ? 1 : 0);
+                less += c < 0 || (c == 0 && s_row[w][j] < ri);
+            }
+            rank[u] = less;
+        }
+#pragma unroll
+        for (int u = 0; u < (int)(BYTES_SMALL / 64); ++u)
+            if (lane + 64 * u < len) idx[p0 + rank[u]] = mine[u];
+        __syncthreads();
+    }
+}
+
+// ---- 4: back from a pair sort of long-run slots -------------------------------------------------------------------------
+// tmp[j] = idx[pos[val[j]]]: the row that sorted to slot j; then idx[pos[j]] = tmp[j].
+__global__ __launch_bounds__(256) void slots_gather_kernel(const uint32_t* __restrict__ vals, const uint32_t* __restrict__ pos,
+                                                           const uint32_t* __restrict__ idx, uint64_t m, uint64_t n,
+                                                           uint32_t* __restrict__ tmp, uint32_t* err) {
+    const uint64_t step = (uint64_t)gridDim.x * 256;
+    for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < m; j += step) {
+        const uint32_t v = vals[j];
+        const uint32_t p = v < m ? pos[v] : (uint32_t)n;
+        if (p >= n) { raise(err, ERR_BYTES_RANGE); tmp[j] = (uint32_t)n; continue; }
+        tmp[j] = idx[p];
+    }
+}
+__global__ __launch_bounds__(256) void slots_scatter_kernel(const uint32_t* __restrict__ tmp, const uint32_t* __restrict__ pos,
+                                                            uint64_t m, uint64_t n, uint32_t* __restrict__ idx, uint32_t* err) {
+    const uint64_t step = (uint64_t)gridDim.x * 256;
+    for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < m; j += step) {
+        const uint32_t p = pos[j], row = tmp[j];
+        if (p >= n || row >= n) { raise(err, ERR_BYTES_RANGE); continue; }
+        idx[p] = row;
+    }
+}
+
+// ---- 5: gather --------------------------------------------------------------------------------------------------------
+struct alignas(16) Unit16 { uint64_t a, b; };
+template <typename U>
+__global__ __launch_bounds__(256) void rows_gather_kernel(const U* __restrict__ src, U* __restrict__ dst, const uint32_t* __restrict__ idx,
+                                                          uint64_t n, uint32_t units, uint32_t* err) {
+    const uint64_t total = n * units, step = (uint64_t)gridDim.x * 256;
+    for (uint64_t g = (uint64_t)blockIdx.x * 256 + threadIdx.x; g < total; g += step) {
+        const uint64_t i = g / units;
+        const uint32_t u = (uint32_t)(g - i * units);
+        const uint32_t row = idx[i];
+        if (row >= n) { if (u == 0) raise(err, ERR_BYTES_RANGE); continue; }
+        dst[g] = src[(uint64_t)row * units + u];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------------------------
+// host side
+// ------------------------------------------------------------------------------------------------------------------------
+#define BYTES_TRY(expr)                                                           \
+    do {                                                                          \
+        hipError_t e__ = (expr);                                                  \
+        if (e__ != hipSuccess) return set_error(RDST_ERR_HIP, #expr, e__);        \
+    } while (0)
+
+uint64_t align256(uint64_t x) { return (x + 255) / 256 * 256; }
+
+// Scratch of the core for n rows (n < 2^32): 8 + 8 + 5 x 4 bytes per row, the run tables (at most n / 2 runs) and the
+// scan's tile sums.
+struct Layout {
+    uint64_t keys, keys_tmp, idx, vals_tmp, tied_pos, tied_run, long_pos, run_start, run_scan, tile_sums, cnt, total;
+};
+Layout make_layout(uint64_t n) {
+    Layout L;
+    uint64_t o = 0;
+    auto take = [&](uint64_t bytes) { const uint64_t at = o; o += align256(bytes); return at; };
+    const uint64_t runs = n / 2 + 2, tiles = (n + SCAN_TILE - 1) / SCAN_TILE + 2;
+    L.keys = take(n * 8);
+    L.keys_tmp = take(n * 8);
+    L.idx = take(n * 4);
+    L.vals_tmp = take(n * 4);  // also the long rows' run ordinals between the tie step and the pair sort
+    L.tied_pos = take(n * 4);
+    L.tied_run = take(n * 4);  // also the pair sort's values in a refinement round
+    L.long_pos = take(n * 4);
+    L.run_start = take(runs * 4);
+    L.run_scan = take(runs * 8);
+    L.tile_sums = take(tiles * 8);
+    L.cnt = take(CNT_WORDS * 8);
+    L.total = o;
+    return L;
+}
+
+uint32_t grid_for(uint64_t items) {
+    uint64_t b = (items + 255) / 256;
+    if (b < 1) b = 1;
+    return (uint32_t)(b > GRID_CAP ? GRID_CAP : b);
+}
+
+// Orders the row indices (left in the scratch's idx array).  Blocking: one wait per round.
+int bytes_order(const uint8_t* rows, uint64_t n, uint32_t stride, uint32_t off, uint32_t n_bytes, char* scratch,
+                hipStream_t s, uint32_t* err) {
+    const Layout L = make_layout(n);
+    uint64_t* keys = reinterpret_cast<uint64_t*>(scratch + L.keys);
+    uint64_t* keys_tmp = reinterpret_cast<uint64_t*>(scratch + L.keys_tmp);
+    uint32_t* idx = reinterpret_cast<uint32_t*>(scratch + L.idx);
+    uint32_t* vals_tmp = reinterpret_cast<uint32_t*>(scratch + L.vals_tmp);
+    uint32_t* tied_pos = reinterpret_cast<uint32_t*>(scratch + L.tied_pos);
+    uint32_t* tied_run = reinterpret_cast<uint32_t*>(scratch + L.tied_run);
+    uint32_t* long_pos = reinterpret_cast<uint32_t*>(scratch + L.long_pos);
+    uint32_t* long_run = vals_tmp;
+    uint32_t* run_start = reinterpret_cast<uint32_t*>(scratch + L.run_start);
+    uint64_t* run_scan = reinterpret_cast<uint64_t*>(scratch + L.run_scan);
+    uint64_t* tile_sums = reinterpret_cast<uint64_t*>(scratch + L.tile_sums);
+    uint64_t* cnt = reinterpret_cast<uint64_t*>(scratch + L.cnt);
+
+    // 1. prefix
+    const uint32_t k0 = n_bytes < 8 ? n_bytes : 8;
+    hipLaunchKernelGGL(bytes_keys_kernel, dim3(grid_for(n)), dim3(256), 0, s, rows, stride, off, n_bytes, 0u, k0, 0u,
+                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, n, n, keys, idx, err);
+    BYTES_TRY(hipGetLastError());
+    int rc = rdst_hip_sort_pairs_device(keys, idx, keys_tmp, vals_tmp, n, 8, RDST_KEY_UNSIGNED, 8, 4, s);
+    if (rc) return rc;
+
+    uint32_t depth = k0;
+    uint64_t m = n;
+    const uint32_t* cpos = nullptr;
+    while (depth < n_bytes) {
+        const uint32_t words = (n_bytes - depth + 3) / 4;
+        // 2. ties, then the runs' split into short and long
+        const TieOp tie{keys, m, cpos, tied_pos, tied_run, run_start, cnt};
+        const uint32_t tie_tiles = (uint32_t)((m + SCAN_TILE - 1) / SCAN_TILE);
+        hipLaunchKernelGGL(scan_tiles_kernel<TieOp>, dim3(tie_tiles), dim3(SCAN_THREADS), 0, s, tie, tile_sums);
+        hipLaunchKernelGGL(scan_sums_kernel<TieOp>, dim3(1), dim3(SUMS_THREADS), 0, s, tie, tile_sums);
+        hipLaunchKernelGGL(scan_emit_kernel<TieOp>, dim3(tie_tiles), dim3(SCAN_THREADS), 0, s, tie, (const uint64_t*)tile_sums);
+        const RunOp runop{run_start, words, run_scan, cnt, m / 2};
+        const uint32_t run_tiles = (uint32_t)((m / 2 + SCAN_TILE) / SCAN_TILE);  // at most m / 2 runs
+        hipLaunchKernelGGL(scan_tiles_kernel<RunOp>, dim3(run_tiles), dim3(SCAN_THREADS), 0, s, runop, tile_sums);
+        hipLaunchKernelGGL(scan_sums_kernel<RunOp>, dim3(1), dim3(SUMS_THREADS), 0, s, runop, tile_sums);
+        hipLaunchKernelGGL(scan_emit_kernel<RunOp>, dim3(run_tiles), dim3(SCAN_THREADS), 0, s, runop, (const uint64_t*)tile_sums);
+        hipLaunchKernelGGL(long_rows_kernel, dim3(grid_for(m)), dim3(256), 0, s, (const uint32_t*)tied_pos, (const uint32_t*)tied_run,
+                           (const uint32_t*)run_start, (const uint64_t*)run_scan, (const uint64_t*)cnt, words, long_pos, long_run, err);
+        BYTES_TRY(hipGetLastError());
+        uint64_t h[4] = {0, 0, 0, 0};
+        BYTES_TRY(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, s));
+        BYTES_TRY(hipStreamSynchronize(s));
+        const uint64_t tied = h[CNT_TIED], runs = h[CNT_RUNS], long_rows = h[CNT_LONG_ROWS], long_runs = h[CNT_LONG_RUNS];
+        if (tied > m || 2 * runs > tied || long_rows > tied || long_runs > runs || (long_runs == 0) != (long_rows == 0))
+            return set_error(RDST_ERR_DEVICE, "[u8; N] route: inconsistent tie counts (a kernel before them failed)");
+        if (runs == 0) break;
+        // 3. short runs
+        if (runs > long_runs) {
+            uint64_t blocks = (runs + CMP_WAVES - 1) / CMP_WAVES;
+            if (blocks > (1u << 20)) blocks = 1u << 20;
+            hipLaunchKernelGGL(short_runs_kernel, dim3((uint32_t)blocks), dim3(64 * CMP_WAVES), 0, s, rows, stride, off, n_bytes, depth,
+                               words, (const uint32_t*)tied_pos, (const uint32_t*)run_start, (const uint64_t*)cnt, idx, n, err);
+            BYTES_TRY(hipGetLastError());
+        }
+        if (long_runs == 0) break;
+        // 4. long runs: (run ordinal, next bytes) pairs, one stable pair sort, slots back to positions
+        const uint32_t b = long_runs == 1 ? 0 : 64 - __builtin_clzll(long_runs - 1);
+        const uint32_t k = (64 - b) / 8;
+        hipLaunchKernelGGL(bytes_keys_kernel, dim3(grid_for(long_rows)), dim3(256), 0, s, rows, stride, off, n_bytes, depth, k, b,
+                           (const uint32_t*)idx, (const uint32_t*)long_pos, (const uint32_t*)long_run, long_rows, n, keys, tied_run, err);
+        BYTES_TRY(hipGetLastError());
+        rc = rdst_hip_sort_pairs_device(keys, tied_run, keys_tmp, vals_tmp, long_rows, 8, RDST_KEY_UNSIGNED, 8, 4, s);
+        if (rc) return rc;
+        hipLaunchKernelGGL(slots_gather_kernel, dim3(grid_for(long_rows)), dim3(256), 0, s, (const uint32_t*)tied_run,
+                           (const uint32_t*)long_pos, (const uint32_t*)idx, long_rows, n, vals_tmp, err);
+        hipLaunchKernelGGL(slots_scatter_kernel, dim3(grid_for(long_rows)), dim3(256), 0, s, (const uint32_t*)vals_tmp,
+                           (const uint32_t*)long_pos, long_rows, n, idx, err);
+        BYTES_TRY(hipGetLastError());
+        depth += k;
+        m = long_rows;
+        cpos = long_pos;
+    }
+    return RDST_OK;
+}
+
+int bytes_gather(const uint8_t* src, uint8_t* dst, const uint32_t* idx, uint64_t n, uint32_t stride, hipStream_t s, uint32_t* err) {
+    const uintptr_t a = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | stride;
+    const uint32_t unit = a % 16 == 0 ? 16 : (a % 8 == 0 ? 8 : (a % 4 == 0 ? 4 : 1));
+    const uint32_t units = stride / unit;
+    uint64_t blocks = (n * units + 255) / 256;
+    if (blocks > 256 * 32) blocks = 256 * 32;
+#define BYTES_GATHER(U) hipLaunchKernelGGL((rows_gather_kernel<U>), dim3((uint32_t)blocks), dim3(256), 0, s, reinterpret_cast<const U*>(src), \
+                                           reinterpret_cast<U*>(dst), idx, n, units, err)
+    if (unit == 16) BYTES_GATHER(Unit16);
+    else if (unit == 8) BYTES_GATHER(uint64_t);
+    else if (unit == 4) BYTES_GATHER(uint32_t);
+    else BYTES_GATHER(uint8_t);
+#undef BYTES_GATHER
+    BYTES_TRY(hipGetLastError());
+    return RDST_OK;
+}
+
+uint64_t core_scratch_bytes(uint64_t n) { return make_layout(n).total; }
+
+}  // namespace
+
+namespace rdst_internal {
+
+int sort_bytes_rows_host(void* host_rows, uint64_t len, uint32_t row_bytes, uint32_t key_offset, uint32_t key_bytes,
+                         const rdst_hip_opts* opts) {
+    int prev_dev = -1;
+    if (opts && opts->device >= 0) {
+        BYTES_TRY(hipGetDevice(&prev_dev));
+        BYTES_TRY(hipSetDevice(opts->device));
+    }
+    uint32_t* err = nullptr;
+    int rc = device_error_word(&err);
+    if (rc) { if (prev_dev >= 0) (void)hipSetDevice(prev_dev); return rc; }
+    const uint64_t bytes = len * row_bytes;
+    void *d_rows = nullptr, *d_out = nullptr, *d_scratch = nullptr;
+    hipStream_t s = nullptr;
+    auto done = [&](int code) {
+        if (s) (void)hipStreamSynchronize(s);
+        for (void* p : {d_rows, d_out, d_scratch})
+            if (p) (void)hipFree(p);
+        if (s) (void)hipStreamDestroy(s);
+        if (prev_dev >= 0) (void)hipSetDevice(prev_dev);
+        return code;
+    };
+    hipError_t e;
+#define HOST_TRY(expr) if ((e = (expr)) != hipSuccess) return done(set_error(RDST_ERR_HIP, #expr, e))
+    HOST_TRY(hipStreamCreate(&s));
+    HOST_TRY(hipMalloc(&d_rows, bytes));
+    HOST_TRY(hipMalloc(&d_out, bytes));
+    HOST_TRY(hipMalloc(&d_scratch, core_scratch_bytes(len)));
+    HOST_TRY(hipMemcpyAsync(d_rows, host_rows, bytes, hipMemcpyHostToDevice, s));
+    const uint8_t* rows = static_cast<const uint8_t*>(d_rows);
+    char* scratch = static_cast<char*>(d_scratch);
+    rc = bytes_order(rows, len, row_bytes, key_offset, key_bytes, scratch, s, err);
+    if (rc == RDST_OK)
+        rc = bytes_gather(rows, static_cast<uint8_t*>(d_out), reinterpret_cast<const uint32_t*>(scratch + make_layout(len).idx), len,
+                          row_bytes, s, err);
+    if (rc == RDST_OK) rc = rdst_hip_device_status(s);
+    if (rc != RDST_OK) return done(rc);
+    // the host buffer is written only now, after the device reported success
+    HOST_TRY(hipMemcpyAsync(host_rows, d_out, bytes, hipMemcpyDeviceToHost, s));
+    HOST_TRY(hipStreamSynchronize(s));
+#undef HOST_TRY
+    return done(RDST_OK);
+}
+
+}  // namespace rdst_internal
+
+extern "C" {
+
+uint64_t rdst_hip_sort_bytes_scratch_bytes(uint64_t len, uint32_t n_bytes) {
+    if (n_bytes == 0 || n_bytes > RDST_BYTES_MAX_N) return 0;
+    if (n_bytes <= 16) return rdst_internal::widened_scratch_bytes(len, n_bytes);
+    return core_scratch_bytes(len) + align256(len * n_bytes);
+}
+
+int rdst_hip_sort_bytes_device(void* dev_rows, uint64_t len, uint32_t n_bytes, void* dev_scratch, uint64_t scratch_bytes, void* stream) {
+    if (n_bytes == 0) return set_error(RDST_ERR_ARG, "[u8; N] needs N >= 1 (RadixKey::LEVELS == 0 panics in rdst)");
+    if (n_bytes > RDST_BYTES_MAX_N) return set_error(RDST_ERR_UNSUPPORTED, "[u8; N] keys are built for N in 1..RDST_BYTES_MAX_N");
+    if (len <= 1) return RDST_OK;  // radix_sort_builder.rs:151
+    if (dev_rows == nullptr) return set_error(RDST_ERR_ARG, "null rows pointer");
+    if (n_bytes > 16 && len >= (1ull << 32)) return set_error(RDST_ERR_UNSUPPORTED, "[u8; N] keys with N > 16 are built for len < 2^32");
+    if (dev_scratch == nullptr) return set_error(RDST_ERR_ARG, "null scratch pointer");
+    if (scratch_bytes < rdst_hip_sort_bytes_scratch_bytes(len, n_bytes))
+        return set_error(RDST_ERR_ARG, "scratch smaller than rdst_hip_sort_bytes_scratch_bytes(len, n_bytes)");
+    if (reinterpret_cast<uintptr_t>(dev_scratch) % 256) return set_error(RDST_ERR_ALIGN, "scratch not 256-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (n_bytes <= 16) return rdst_internal::sort_bytes_widened(dev_rows, len, n_bytes, dev_scratch, s);
+    uint32_t* err = nullptr;
+    int rc = rdst_internal::device_error_word(&err);
+    if (rc) return rc;
+    char* scratch = static_cast<char*>(dev_scratch);
+    const Layout L = make_layout(len);
+    uint8_t* rows = static_cast<uint8_t*>(dev_rows);
+    uint8_t* staged = reinterpret_cast<uint8_t*>(scratch + L.total);
+    rc = bytes_order(rows, len, n_bytes, 0, n_bytes, scratch, s, err);
+    if (rc) return rc;
+    rc = bytes_gather(rows, staged, reinterpret_cast<const uint32_t*>(scratch + L.idx), len, n_bytes, s, err);
+    if (rc) return rc;
+    BYTES_TRY(hipMemcpyAsync(rows, staged, len * n_bytes, hipMemcpyDeviceToDevice, s));
+    return RDST_OK;
+}
+
+}  // extern "C"

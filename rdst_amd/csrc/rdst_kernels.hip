@@ -41,6 +41,7 @@
 #include <utility>
 
 #include "rdst_hip.h"
+#include "rdst_internal.h"
 
 namespace {
 
@@ -5564,8 +5565,8 @@ int read_device_error(DeviceState& D, hipStream_t s) {
         const uint32_t word = *D.host_err;
         HIP_TRY(hipMemsetAsync(D.err_dev, 0, sizeof(uint32_t), s));  // reported once: the next check starts clean
         HIP_TRY(hipStreamSynchronize(s));
-        char b[192];
-        snprintf(b, sizeof b, "device error word = 0x%x (1 = look-back spin bound expired, 2 = scatter destination out of range, 4 = hybrid-route bucket larger than a tile)", word);
+        char b[256];
+        snprintf(b, sizeof b, "device error word = 0x%x (1 = look-back spin bound expired, 2 = scatter destination out of range, 4 = hybrid-route bucket larger than a tile, 8 = [u8; N] route: a row index or run out of range)", word);
         return fail(RDST_ERR_DEVICE, b);
     }
     return RDST_OK;
@@ -5924,11 +5925,13 @@ int sort_byte_keys_host(void* host_data, uint64_t len, uint32_t nb, const rdst_h
 int rdst_hip_sort(void* host_data, uint64_t len, uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels,
                   const rdst_hip_opts* opts) {
     if (kind == RDST_KEY_BYTES_BE) {  // [u8; N], src/radix_key_impl.rs:78-85
-        if (elem_bytes == 0 || elem_bytes > 16) return fail(RDST_ERR_UNSUPPORTED, "[u8; N] keys are built for N in 1..16");
+        if (elem_bytes == 0 || elem_bytes > RDST_BYTES_MAX_N) return fail(RDST_ERR_UNSUPPORTED, "[u8; N] keys are built for N in 1..RDST_BYTES_MAX_N");
         if (levels != elem_bytes) return fail(RDST_ERR_ARG, "levels must equal N for [u8; N]");
         if (len > 0 && host_data == nullptr) return fail(RDST_ERR_ARG, "null key pointer");
         if (len >= (1ull << 36)) return fail(RDST_ERR_ARG, "len too large");
+        if (elem_bytes > 16 && len >= (1ull << 32)) return fail(RDST_ERR_UNSUPPORTED, "[u8; N] keys with N > 16 are built for len < 2^32");
         if (len <= 1) return RDST_OK;
+        if (elem_bytes > 16) return rdst_internal::sort_bytes_rows_host(host_data, len, elem_bytes, 0, elem_bytes, opts);  // rdst_bytes.hip
         return sort_byte_keys_host(host_data, len, elem_bytes, opts);
     }
     int rc = check_common(host_data, len, elem_bytes, kind, levels);
@@ -6038,6 +6041,14 @@ int rdst_hip_host_timing(float* h2d_ms, float* sort_ms, float* d2h_ms) {
 
 int rdst_hip_sort_records(void* host_records, uint64_t len, uint32_t record_bytes, uint32_t key_offset, uint32_t key_bytes,
                           rdst_key_kind kind, const rdst_hip_opts* opts) {
+    if (kind == RDST_KEY_BYTES_BE) {  // a [u8; N] field: any offset, any row size (rdst_bytes.hip)
+        if (key_bytes == 0 || key_bytes > RDST_BYTES_MAX_N) return fail(RDST_ERR_UNSUPPORTED, "[u8; N] key fields are built for N in 1..RDST_BYTES_MAX_N");
+        if (record_bytes == 0 || (uint64_t)key_offset + key_bytes > record_bytes) return fail(RDST_ERR_ARG, "key field outside the record");
+        if (len > 0 && host_records == nullptr) return fail(RDST_ERR_ARG, "null record pointer");
+        if (len >= (1ull << 32)) return fail(RDST_ERR_UNSUPPORTED, "records with a [u8; N] key are built for len < 2^32");
+        if (len <= 1) return RDST_OK;
+        return rdst_internal::sort_bytes_rows_host(host_records, len, record_bytes, key_offset, key_bytes, opts);
+    }
     if (key_bytes != 4 && key_bytes != 8) return fail(RDST_ERR_UNSUPPORTED, "record sorts take a 4- or 8-byte key field");
     if (kind == RDST_KEY_FLOAT || kind == RDST_KEY_SIGNED || kind == RDST_KEY_UNSIGNED) {} else return fail(RDST_ERR_ARG, "unknown key kind");
     if (record_bytes == 0 || (uint64_t)key_offset + key_bytes > record_bytes) return fail(RDST_ERR_ARG, "key field outside the record");
@@ -6294,3 +6305,43 @@ int rdst_hip_level_counts(const void* dev_keys, uint64_t len, uint32_t elem_byte
 }
 
 }  // extern "C"
+
+// Hooks for rdst_bytes.hip (rdst_internal.h).
+namespace rdst_internal {
+
+int set_error(int code, const char* what, hipError_t e) { return fail(code, what, e); }
+
+int device_error_word(uint32_t** out) {
+    std::lock_guard<std::mutex> lock(g_mutex);
+    DeviceState* D;
+    int rc = current_device_state(&D);
+    if (rc) return rc;
+    *out = D->err_dev;
+    return RDST_OK;
+}
+
+static uint32_t widened_bytes(uint32_t nb) { return nb <= 4 ? 4 : (nb <= 8 ? 8 : 16); }
+
+uint64_t widened_scratch_bytes(uint64_t len, uint32_t nb) { return 2 * (uint64_t)align_up((size_t)len * widened_bytes(nb), 256); }
+
+int sort_bytes_widened(void* dev_rows, uint64_t len, uint32_t nb, void* scratch, hipStream_t s) {
+    const uint32_t w = widened_bytes(nb);
+    void* d_keys = scratch;
+    void* d_tmp = static_cast<char*>(scratch) + align_up((size_t)len * w, 256);
+    uint64_t blocks = (len + 255) / 256;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    unsigned char* raw = static_cast<unsigned char*>(dev_rows);
+    if (w == 4) hipLaunchKernelGGL((bytes_expand_kernel<uint32_t>), dim3((uint32_t)blocks), dim3(256), 0, s, raw, static_cast<uint32_t*>(d_keys), len, nb);
+    else if (w == 8) hipLaunchKernelGGL((bytes_expand_kernel<uint64_t>), dim3((uint32_t)blocks), dim3(256), 0, s, raw, static_cast<uint64_t*>(d_keys), len, nb);
+    else hipLaunchKernelGGL((bytes_expand_kernel<u128>), dim3((uint32_t)blocks), dim3(256), 0, s, raw, static_cast<u128*>(d_keys), len, nb);
+    HIP_TRY(hipGetLastError());
+    int rc = rdst_hip_sort_device(d_keys, d_tmp, len, w, RDST_KEY_UNSIGNED, w, s);
+    if (rc) return rc;
+    if (w == 4) hipLaunchKernelGGL((bytes_compact_kernel<uint32_t>), dim3((uint32_t)blocks), dim3(256), 0, s, static_cast<const uint32_t*>(d_keys), raw, len, nb);
+    else if (w == 8) hipLaunchKernelGGL((bytes_compact_kernel<uint64_t>), dim3((uint32_t)blocks), dim3(256), 0, s, static_cast<const uint64_t*>(d_keys), raw, len, nb);
+    else hipLaunchKernelGGL((bytes_compact_kernel<u128>), dim3((uint32_t)blocks), dim3(256), 0, s, static_cast<const u128*>(d_keys), raw, len, nb);
+    HIP_TRY(hipGetLastError());
+    return RDST_OK;
+}
+
+}  // namespace rdst_internal

@@ -96,6 +96,40 @@ def sort_device_tensor(keys, tmp=None, check=True, key=None):
             _lib.check(lib.rdst_hip_device_status(s))
 
 
+def _check_bytes_rows(shape, dtype_ok):
+    if len(shape) != 2 or not dtype_ok or not 1 <= shape[1] <= _lib.RDST_BYTES_MAX_N:
+        raise ValueError(f"[u8; N] keys: a uint8 container of shape (n, N) with N in 1..{_lib.RDST_BYTES_MAX_N}")
+
+
+def sort_bytes_device_tensor(rows, scratch=None, check=True):
+    """``rdst_hip_sort_bytes_device``: sort the rows of a contiguous (n, N) uint8 HIP tensor in place, each row one
+    ``[u8; N]`` key (src/radix_key_impl.rs:78-85: lexicographic order).  The row base needs no alignment.  ``scratch``:
+    optional uint8 HIP tensor of at least ``rdst_hip_sort_bytes_scratch_bytes(n, N)`` bytes (allocated when omitted).  Runs on
+    the tensor's current stream; N > 16 blocks (the tie counts come to the host), N <= 16 stays asynchronous unless
+    ``check``."""
+    import torch
+    if not rows.is_cuda:
+        raise ValueError("sort_bytes_device_tensor needs a tensor on a HIP device")
+    _check_bytes_rows(tuple(rows.shape), rows.dtype == torch.uint8)
+    if not rows.is_contiguous():
+        raise ValueError("rows must be a contiguous (n, N) tensor")
+    n, n_bytes = int(rows.shape[0]), int(rows.shape[1])
+    if n <= 1:
+        return
+    lib = _lib.load()
+    need = int(lib.rdst_hip_sort_bytes_scratch_bytes(n, n_bytes))
+    if scratch is None:
+        scratch = torch.empty(need, dtype=torch.uint8, device=rows.device)  # the caching allocator hands out 512-byte aligned blocks
+    elif scratch.device != rows.device or not scratch.is_contiguous() or scratch.numel() * scratch.element_size() < need:
+        raise ValueError(f"scratch must be a contiguous tensor on the rows' device with at least {need} bytes")
+    with torch.cuda.device(rows.device):
+        s = _stream_handle(rows)
+        _lib.check(lib.rdst_hip_sort_bytes_device(ctypes.c_void_p(rows.data_ptr()), n, n_bytes, ctypes.c_void_p(scratch.data_ptr()),
+                                                  scratch.numel() * scratch.element_size(), s))
+        if check:
+            _lib.check(lib.rdst_hip_device_status(s))
+
+
 def sort_pairs_device_tensor(keys, values, tmp_keys=None, tmp_values=None, check=True):
     """``rdst_hip_sort_pairs_device``: sort the 1-D HIP tensor ``keys`` (4- or 8-byte built-in key type) in place
     and permute ``values`` (4- or 8-byte elements, same length) with it.  Stable: equal keys keep their
@@ -195,13 +229,12 @@ def device_status(device=None):
 
 def sort_host_array(arr, device=-1, key=None):
     """``rdst_hip_sort`` on a host numpy array (H2D, device sort, D2H), in place.  ``key="bytes"``: a uint8
-    array of shape (n, N), N in 1..16, each row one ``[u8; N]`` key (src/radix_key_impl.rs:78-85: rows
-    end up in lexicographic order)."""
+    array of shape (n, N), N in 1..RDST_BYTES_MAX_N (4096), each row one ``[u8; N]`` key (src/radix_key_impl.rs:78-85:
+    rows end up in lexicographic order)."""
     if not isinstance(arr, np.ndarray) or not arr.flags.c_contiguous or not arr.flags.writeable:
         raise ValueError("need a writeable C-contiguous 1-D numpy array (rdst sorts a mutable slice)")
     if key == "bytes":
-        if arr.ndim != 2 or arr.dtype != np.uint8 or not 1 <= arr.shape[1] <= 16:
-            raise ValueError("[u8; N] keys: a uint8 array of shape (n, N) with N in 1..16")
+        _check_bytes_rows(arr.shape, arr.dtype == np.uint8)
         if arr.shape[0] <= 1:
             return
         n_bytes = int(arr.shape[1])
@@ -223,13 +256,21 @@ def sort_host_array(arr, device=-1, key=None):
 
 def sort_host_records(arr, field, device=-1):
     """``rdst_hip_sort_records`` on a numpy structured array, in place: the rows are ordered by ``field``
-    (a 4- or 8-byte integer or float field); rows with equal keys keep their order."""
+    (a 4- or 8-byte integer or float field, or a ``[u8; N]`` byte string: ``('u1', (N,))``, ``'S<N>'`` or ``'V<N>'``, N up to
+    RDST_BYTES_MAX_N, lexicographic); rows with equal keys keep their order."""
     if not isinstance(arr, np.ndarray) or arr.dtype.fields is None or arr.ndim != 1:
         raise ValueError("need a 1-D numpy structured array")
     if not arr.flags.c_contiguous or not arr.flags.writeable:
         raise ValueError("need a writeable C-contiguous array (rdst sorts a mutable slice)")
     ftype, offset = arr.dtype.fields[field][:2]
-    kind, nbytes, _levels = key_info(ftype.name)
+    byte_string = (ftype.subdtype is not None and ftype.subdtype[0] == np.uint8 and len(ftype.subdtype[1]) == 1) or \
+        (ftype.kind in "SV" and ftype.fields is None and ftype.subdtype is None)
+    if byte_string:
+        kind, nbytes = _lib.RDST_KEY_BYTES_BE, ftype.itemsize
+        if not 1 <= nbytes <= _lib.RDST_BYTES_MAX_N:
+            raise ValueError(f"[u8; N] key fields: N in 1..{_lib.RDST_BYTES_MAX_N}")
+    else:
+        kind, nbytes, _levels = key_info(ftype.name)
     if arr.shape[0] <= 1:
         return
     lib = _lib.load()
@@ -347,7 +388,8 @@ class RadixSortBuilder:
             return out
         if _is_torch_tensor(self._data):
             if self._key == "bytes":
-                raise NotImplementedError("[u8; N] keys go through the host entry point: pass a numpy array")
+                sort_bytes_device_tensor(self._data)
+                return
             sort_device_tensor(self._data, key=self._key)
         else:
             sort_host_array(self._data, key=self._key)
