@@ -7,7 +7,7 @@ src/tuners/standard_tuner.rs:46-62, src/sorts/lsb_sort.rs:39-127)."""
 import numpy as np
 import pytest
 
-from helpers import DTYPES, mapped_key, random_bits, reference_sorted, same_bits, to_device, to_host
+from helpers import DTYPES, giant_buckets_input, mapped_key, random_bits, reference_sorted, same_bits, to_device, to_host, with_prefixes
 
 pytestmark = pytest.mark.gpu
 
@@ -75,19 +75,6 @@ def _sort(rdst, a):
     return to_host(t, a.dtype), route
 
 
-def _with_prefixes(n, dtype, prefixes, seed, low_mask=None):
-    """random keys whose top 16 bits (of the raw pattern) come from `prefixes`; low bits random & low_mask"""
-    rng = np.random.default_rng(seed)
-    dt = np.dtype(dtype)
-    w = dt.itemsize * 8
-    u = random_bits(n, f"uint{w}", seed).copy()
-    if low_mask is not None:
-        u &= np.array(low_mask, dtype=u.dtype)
-    low = u & np.array((1 << (w - 16)) - 1, dtype=u.dtype)
-    top = rng.choice(np.asarray(prefixes, dtype=np.uint64), size=n).astype(u.dtype)
-    return (low | (top << np.array(w - 16, dtype=u.dtype))).view(dt)
-
-
 @pytest.mark.parametrize("dtype", DTYPES)
 def test_hybrid_matches_oracle_over_sizes(hybrid, oracle, dtype):
     for i, n in enumerate((16_385, 70_000, 300_001, 1_000_003, 5_000_011)):
@@ -106,7 +93,7 @@ def test_buckets_up_to_one_tile(hybrid, dtype):
     rng = np.random.default_rng(17)
     # ~300 buckets of ~13 k keys each: most of a tile, several 64-key rounds short of it
     prefixes = rng.choice(65536, size=300, replace=False)
-    a = _with_prefixes(300 * (tile - 3000), dtype, prefixes, seed=18)
+    a = with_prefixes(300 * (tile - 3000), dtype, prefixes, seed=18)
     got, route = _sort(hybrid, a)
     assert _fast_route(hybrid, route, dtype, strict=False)
     assert same_bits(got, reference_sorted(a)), dtype
@@ -135,7 +122,7 @@ def test_bucket_larger_than_the_routes_bound(hybrid):
     over a tile), and one key more is the LSD route's."""
     for dtype in ("uint32", "float64"):
         tile = TILE[np.dtype(dtype).itemsize]
-        a = _with_prefixes(40 * (tile + 2000), dtype, list(range(1000, 1040)), seed=5)
+        a = with_prefixes(40 * (tile + 2000), dtype, list(range(1000, 1040)), seed=5)
         got, route = _sort(hybrid, a)
         assert route == _skewed_route(hybrid, dtype, _bucket_cap(hybrid, dtype) > tile), (dtype, route)
         assert same_bits(got, reference_sorted(a))
@@ -200,27 +187,8 @@ def test_giant_buckets(hybrid):
     value, neighbours in one counter word, first and last prefix, mapped key kinds, the reference's bimodal bench shape
     (gen_inputs with shift 16, src/test_utils.rs:51-61) — are sorted by the hybrid route's giant kernels."""
     rng = np.random.default_rng(2024)
-
-    def bucket(prefix, size, kind):
-        if kind == "dense":
-            low = rng.integers(0, 1 << 16, size=size, dtype=np.uint32)
-        elif kind == "sparse":      # few distinct values far apart: long empty stretches of the count table
-            low = rng.choice(np.array([0, 1, 300, 30000, 32767, 32768, 65000, 65535], dtype=np.uint32), size=size)
-        elif kind == "two":
-            low = rng.choice(np.array([0, 65535], dtype=np.uint32), size=size)
-        elif kind == "one":
-            low = np.full(size, 0x8000, dtype=np.uint32)
-        else:                        # "narrow": every value of a small range, many times
-            low = rng.integers(1000, 1100, size=size, dtype=np.uint32)
-        return low | np.uint32(prefix << 16)
-
     for dtype in ("uint32", "int32", "float32"):
-        parts = [bucket(0x0000, 65_536, "dense"), bucket(0xFFFF, 70_001, "sparse"), bucket(0x1234, 300_000, "dense"),
-                 bucket(0x1235, 65_537, "two"), bucket(0x8000, 131_072, "one"), bucket(0x7FFF, 1_100_000, "narrow"),
-                 bucket(0x4000, 65_535, "dense"), bucket(0x4001, 20_000, "two"), random_bits(500_000, "uint32", seed=5)]
-        a = np.concatenate(parts)
-        rng.shuffle(a)
-        a = a.view(dtype)
+        a = giant_buckets_input(rng, dtype)
         got, route = _sort(hybrid, a)
         assert route == _skewed_route(hybrid, dtype, _giants_ok(hybrid, dtype)), (dtype, route)
         assert same_bits(got, reference_sorted(a)), dtype
@@ -276,12 +244,12 @@ def test_skewed_low_digits_inside_buckets(hybrid, dtype):
     full = (1 << (w - 16)) - 1
     masks = [0, 0xFF, 0xFF00, 0x1, 0x8000, 0xF0F0, full & ~0xFF, full & ~0xFFFF if w > 32 else 0x00FF, 0x0101]
     for j, m in enumerate(masks):
-        a = _with_prefixes(n, dtype, prefixes, seed=300 + j, low_mask=(m | (0xFFFF << (w - 16))))
+        a = with_prefixes(n, dtype, prefixes, seed=300 + j, low_mask=(m | (0xFFFF << (w - 16))))
         got, route = _sort(hybrid, a)
         assert _fast_route(hybrid, route, dtype, strict=False), (dtype, hex(m), route)
         assert same_bits(got, reference_sorted(a)), (dtype, hex(m))
     # every bucket already sorted / reverse sorted inside, buckets interleaved
-    a = _with_prefixes(n, dtype, prefixes, seed=400)
+    a = with_prefixes(n, dtype, prefixes, seed=400)
     s = reference_sorted(a)
     for arr in (s, s[::-1].copy()):
         arr = arr.copy()
@@ -305,7 +273,7 @@ def test_float_specials_through_the_hybrid_route(hybrid):
 
 
 def test_fast_rank_selftest_and_ballot_modes_agree(hybrid):
-    a = _with_prefixes(150 * 12000, "uint32", list(range(500, 650)), seed=21)
+    a = with_prefixes(150 * 12000, "uint32", list(range(500, 650)), seed=21)
     b = random_bits(1_500_000, "uint64", seed=22).copy()
     exp_a, exp_b = reference_sorted(a), reference_sorted(b)
     for mode in (True, 2, False):          # returning-add ranking, its fallback forced on every round, ballots only

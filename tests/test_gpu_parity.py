@@ -8,8 +8,8 @@ import os
 import numpy as np
 import pytest
 
-from helpers import (DTYPES, SMALL_DTYPES, gen_inputs, mapped_key, random_bits, reference_sorted, same_bits, to_device, to_host,
-                     u32_patterns)
+from helpers import (DTYPES, SMALL_DTYPES, gen_inputs, heavy_digit_inputs, mapped_key, random_bits, reference_sorted, same_bits, to_device,
+                     to_host, u32_patterns)
 
 pytestmark = pytest.mark.gpu
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -398,30 +398,6 @@ def test_scatter_level_hook_is_the_reference_stable_pass(gpu, oracle, dtype):
         assert same_bits(to_host(t, dtype), a)  # source untouched
 
 
-def _heavy_digit_inputs(n, dtype, level, seed):
-    """inputs that put the lr variants of out_of_place_sort to work (src/sorts/out_of_place_sort.rs:202-389: a
-    bucket written from both ends when many equal digits sit next to each other) and the heavy-digit ranking of K3"""
-    rng = np.random.default_rng(seed)
-    w = np.dtype(dtype).itemsize * 8
-    ut = f"uint{w}"
-    base = random_bits(n, ut, seed).copy()
-    sh = np.array(8 * level, dtype=ut)
-    clear = ~(np.array(0xFF, dtype=ut) << sh)
-
-    def with_digits(d):
-        return ((base & clear) | (d.astype(ut) << sh)).view(dtype)
-
-    out = {}
-    d = rng.integers(0, 256, size=n)
-    d[rng.random(n) < 0.9] = 0x5A
-    out["90% one digit"] = with_digits(d)
-    out["two digits only"] = with_digits(rng.choice([3, 200], size=n))
-    out["one digit per 64-key round"] = with_digits(np.repeat(rng.integers(0, 256, size=(n + 63) // 64), 64)[:n])
-    out["sorted by digit"] = with_digits(np.sort(rng.integers(0, 256, size=n)))
-    out["long equal runs"] = with_digits(np.repeat(rng.integers(0, 256, size=(n + 999) // 1000), 1000)[:n])
-    return out
-
-
 @pytest.mark.parametrize("dtype", ("uint32", "int64", "float32"))
 def test_scatter_level_hook_on_heavy_digits_matches_every_oracle_variant(gpu, oracle, dtype):
     """the reference's four out_of_place_sort variants (plain, with_counts, lr,
@@ -431,7 +407,7 @@ def test_scatter_level_hook_on_heavy_digits_matches_every_oracle_variant(gpu, or
     levels = np.dtype(dtype).itemsize
     for n in (70_001, 1_200_007):
         for level in (0, levels - 1):
-            for name, a in _heavy_digit_inputs(n, dtype, level, seed=n + level).items():
+            for name, a in heavy_digit_inputs(n, dtype, level, seed=n + level).items():
                 t = to_device(a)
                 dst, counts = gpu.scatter_level(t, level)
                 got = to_host(dst, dtype)
