@@ -28,6 +28,7 @@
 
 namespace {
 
+using rdst_internal::launch;
 using rdst_internal::set_error;
 
 constexpr uint32_t ERR_BYTES_RANGE = 8;  // a row index, slot or run read from memory fell out of range: never used to store
@@ -402,6 +403,14 @@ uint32_t grid_for(uint64_t items) {
     return (uint32_t)(b > GRID_CAP ? GRID_CAP : b);
 }
 
+// the three-kernel scan of one operator over `tiles` tiles
+template <typename Op>
+int launch_scan(const Op& op, uint32_t tiles, uint64_t* tile_sums, hipStream_t s) {
+    if (int rc = launch("scan_tiles_kernel", scan_tiles_kernel<Op>, dim3(tiles), dim3(SCAN_THREADS), 0, s, op, tile_sums)) return rc;
+    if (int rc = launch("scan_sums_kernel", scan_sums_kernel<Op>, dim3(1), dim3(SUMS_THREADS), 0, s, op, tile_sums)) return rc;
+    return launch("scan_emit_kernel", scan_emit_kernel<Op>, dim3(tiles), dim3(SCAN_THREADS), 0, s, op, tile_sums);
+}
+
 // Orders the row indices (left in the scratch's idx array).  Blocking: one wait per round.
 int bytes_order(const uint8_t* rows, uint64_t n, uint32_t stride, uint32_t off, uint32_t n_bytes, char* scratch,
                 hipStream_t s, uint32_t* err) {
@@ -421,11 +430,10 @@ int bytes_order(const uint8_t* rows, uint64_t n, uint32_t stride, uint32_t off, 
 
     // 1. prefix
     const uint32_t k0 = n_bytes < 8 ? n_bytes : 8;
-    hipLaunchKernelGGL(bytes_keys_kernel, dim3(grid_for(n)), dim3(256), 0, s, rows, stride, off, n_bytes, 0u, k0, 0u,
-                       (const uint32_t*)nullptr, (const uint32_t*)nullptr, (const uint32_t*)nullptr, n, n, keys, idx, err);
-    BYTES_TRY(hipGetLastError());
-    int rc = rdst_hip_sort_pairs_device(keys, idx, keys_tmp, vals_tmp, n, 8, RDST_KEY_UNSIGNED, 8, 4, s);
+    int rc = launch("bytes_keys_kernel", bytes_keys_kernel, dim3(grid_for(n)), dim3(256), 0, s, rows, stride, off, n_bytes, 0u, k0, 0u, nullptr, nullptr,
+                    nullptr, n, n, keys, idx, err);
     if (rc) return rc;
+    if ((rc = rdst_hip_sort_pairs_device(keys, idx, keys_tmp, vals_tmp, n, 8, RDST_KEY_UNSIGNED, 8, 4, s))) return rc;
 
     uint32_t depth = k0;
     uint64_t m = n;
@@ -434,18 +442,12 @@ int bytes_order(const uint8_t* rows, uint64_t n, uint32_t stride, uint32_t off, 
         const uint32_t words = (n_bytes - depth + 3) / 4;
         // 2. ties, then the runs' split into short and long
         const TieOp tie{keys, m, cpos, tied_pos, tied_run, run_start, cnt};
-        const uint32_t tie_tiles = (uint32_t)((m + SCAN_TILE - 1) / SCAN_TILE);
-        hipLaunchKernelGGL(scan_tiles_kernel<TieOp>, dim3(tie_tiles), dim3(SCAN_THREADS), 0, s, tie, tile_sums);
-        hipLaunchKernelGGL(scan_sums_kernel<TieOp>, dim3(1), dim3(SUMS_THREADS), 0, s, tie, tile_sums);
-        hipLaunchKernelGGL(scan_emit_kernel<TieOp>, dim3(tie_tiles), dim3(SCAN_THREADS), 0, s, tie, (const uint64_t*)tile_sums);
+        if ((rc = launch_scan(tie, (uint32_t)((m + SCAN_TILE - 1) / SCAN_TILE), tile_sums, s))) return rc;
         const RunOp runop{run_start, words, run_scan, cnt, m / 2};
-        const uint32_t run_tiles = (uint32_t)((m / 2 + SCAN_TILE) / SCAN_TILE);  // at most m / 2 runs
-        hipLaunchKernelGGL(scan_tiles_kernel<RunOp>, dim3(run_tiles), dim3(SCAN_THREADS), 0, s, runop, tile_sums);
-        hipLaunchKernelGGL(scan_sums_kernel<RunOp>, dim3(1), dim3(SUMS_THREADS), 0, s, runop, tile_sums);
-        hipLaunchKernelGGL(scan_emit_kernel<RunOp>, dim3(run_tiles), dim3(SCAN_THREADS), 0, s, runop, (const uint64_t*)tile_sums);
-        hipLaunchKernelGGL(long_rows_kernel, dim3(grid_for(m)), dim3(256), 0, s, (const uint32_t*)tied_pos, (const uint32_t*)tied_run,
-                           (const uint32_t*)run_start, (const uint64_t*)run_scan, (const uint64_t*)cnt, words, long_pos, long_run, err);
-        BYTES_TRY(hipGetLastError());
+        if ((rc = launch_scan(runop, (uint32_t)((m / 2 + SCAN_TILE) / SCAN_TILE), tile_sums, s))) return rc;  // at most m / 2 runs
+        if ((rc = launch("long_rows_kernel", long_rows_kernel, dim3(grid_for(m)), dim3(256), 0, s, tied_pos, tied_run, run_start, run_scan, cnt, words, long_pos,
+                         long_run, err)))
+            return rc;
         uint64_t h[4] = {0, 0, 0, 0};
         BYTES_TRY(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, s));
         BYTES_TRY(hipStreamSynchronize(s));
@@ -457,24 +459,22 @@ int bytes_order(const uint8_t* rows, uint64_t n, uint32_t stride, uint32_t off, 
         if (runs > long_runs) {
             uint64_t blocks = (runs + CMP_WAVES - 1) / CMP_WAVES;
             if (blocks > (1u << 20)) blocks = 1u << 20;
-            hipLaunchKernelGGL(short_runs_kernel, dim3((uint32_t)blocks), dim3(64 * CMP_WAVES), 0, s, rows, stride, off, n_bytes, depth,
-                               words, (const uint32_t*)tied_pos, (const uint32_t*)run_start, (const uint64_t*)cnt, idx, n, err);
-            BYTES_TRY(hipGetLastError());
+            if ((rc = launch("short_runs_kernel", short_runs_kernel, dim3((uint32_t)blocks), dim3(64 * CMP_WAVES), 0, s, rows, stride, off, n_bytes, depth, words,
+                             tied_pos, run_start, cnt, idx, n, err)))
+                return rc;
         }
         if (long_runs == 0) break;
         // 4. long runs: (run ordinal, next bytes) pairs, one stable pair sort, slots back to positions
         const uint32_t b = long_runs == 1 ? 0 : 64 - __builtin_clzll(long_runs - 1);
         const uint32_t k = (64 - b) / 8;
-        hipLaunchKernelGGL(bytes_keys_kernel, dim3(grid_for(long_rows)), dim3(256), 0, s, rows, stride, off, n_bytes, depth, k, b,
-                           (const uint32_t*)idx, (const uint32_t*)long_pos, (const uint32_t*)long_run, long_rows, n, keys, tied_run, err);
-        BYTES_TRY(hipGetLastError());
-        rc = rdst_hip_sort_pairs_device(keys, tied_run, keys_tmp, vals_tmp, long_rows, 8, RDST_KEY_UNSIGNED, 8, 4, s);
-        if (rc) return rc;
-        hipLaunchKernelGGL(slots_gather_kernel, dim3(grid_for(long_rows)), dim3(256), 0, s, (const uint32_t*)tied_run,
-                           (const uint32_t*)long_pos, (const uint32_t*)idx, long_rows, n, vals_tmp, err);
-        hipLaunchKernelGGL(slots_scatter_kernel, dim3(grid_for(long_rows)), dim3(256), 0, s, (const uint32_t*)vals_tmp,
-                           (const uint32_t*)long_pos, long_rows, n, idx, err);
-        BYTES_TRY(hipGetLastError());
+        if ((rc = launch("bytes_keys_kernel", bytes_keys_kernel, dim3(grid_for(long_rows)), dim3(256), 0, s, rows, stride, off, n_bytes, depth, k, b, idx, long_pos,
+                         long_run, long_rows, n, keys, tied_run, err)))
+            return rc;
+        if ((rc = rdst_hip_sort_pairs_device(keys, tied_run, keys_tmp, vals_tmp, long_rows, 8, RDST_KEY_UNSIGNED, 8, 4, s))) return rc;
+        if ((rc = launch("slots_gather_kernel", slots_gather_kernel, dim3(grid_for(long_rows)), dim3(256), 0, s, tied_run, long_pos, idx, long_rows, n, vals_tmp, err)))
+            return rc;
+        if ((rc = launch("slots_scatter_kernel", slots_scatter_kernel, dim3(grid_for(long_rows)), dim3(256), 0, s, vals_tmp, long_pos, long_rows, n, idx, err)))
+            return rc;
         depth += k;
         m = long_rows;
         cpos = long_pos;
@@ -488,15 +488,12 @@ int bytes_gather(const uint8_t* src, uint8_t* dst, const uint32_t* idx, uint64_t
     const uint32_t units = stride / unit;
     uint64_t blocks = (n * units + 255) / 256;
     if (blocks > 256 * 32) blocks = 256 * 32;
-#define BYTES_GATHER(U) hipLaunchKernelGGL((rows_gather_kernel<U>), dim3((uint32_t)blocks), dim3(256), 0, s, reinterpret_cast<const U*>(src), \
-                                           reinterpret_cast<U*>(dst), idx, n, units, err)
-    if (unit == 16) BYTES_GATHER(Unit16);
-    else if (unit == 8) BYTES_GATHER(uint64_t);
-    else if (unit == 4) BYTES_GATHER(uint32_t);
-    else BYTES_GATHER(uint8_t);
-#undef BYTES_GATHER
-    BYTES_TRY(hipGetLastError());
-    return RDST_OK;
+    auto gather = [&](auto u) {
+        using U = decltype(u);
+        return launch("rows_gather_kernel", rows_gather_kernel<U>, dim3((uint32_t)blocks), dim3(256), 0, s, reinterpret_cast<const U*>(src),
+                      reinterpret_cast<U*>(dst), idx, n, units, err);
+    };
+    return unit == 16 ? gather(Unit16{}) : (unit == 8 ? gather(uint64_t{}) : (unit == 4 ? gather(uint32_t{}) : gather(uint8_t{})));
 }
 
 uint64_t core_scratch_bytes(uint64_t n) { return make_layout(n).total; }
@@ -507,45 +504,33 @@ namespace rdst_internal {
 
 int sort_bytes_rows_host(void* host_rows, uint64_t len, uint32_t row_bytes, uint32_t key_offset, uint32_t key_bytes,
                          const rdst_hip_opts* opts) {
-    int prev_dev = -1;
+    HostJob job;
     if (opts && opts->device >= 0) {
-        BYTES_TRY(hipGetDevice(&prev_dev));
+        BYTES_TRY(hipGetDevice(&job.prev_dev));
         BYTES_TRY(hipSetDevice(opts->device));
     }
     uint32_t* err = nullptr;
     int rc = device_error_word(&err);
-    if (rc) { if (prev_dev >= 0) (void)hipSetDevice(prev_dev); return rc; }
+    if (rc) return rc;
     const uint64_t bytes = len * row_bytes;
     void *d_rows = nullptr, *d_out = nullptr, *d_scratch = nullptr;
-    hipStream_t s = nullptr;
-    auto done = [&](int code) {
-        if (s) (void)hipStreamSynchronize(s);
-        for (void* p : {d_rows, d_out, d_scratch})
-            if (p) (void)hipFree(p);
-        if (s) (void)hipStreamDestroy(s);
-        if (prev_dev >= 0) (void)hipSetDevice(prev_dev);
-        return code;
-    };
-    hipError_t e;
-#define HOST_TRY(expr) if ((e = (expr)) != hipSuccess) return done(set_error(RDST_ERR_HIP, #expr, e))
-    HOST_TRY(hipStreamCreate(&s));
-    HOST_TRY(hipMalloc(&d_rows, bytes));
-    HOST_TRY(hipMalloc(&d_out, bytes));
-    HOST_TRY(hipMalloc(&d_scratch, core_scratch_bytes(len)));
-    HOST_TRY(hipMemcpyAsync(d_rows, host_rows, bytes, hipMemcpyHostToDevice, s));
+    BYTES_TRY(hipStreamCreate(&job.s));
+    BYTES_TRY(job.alloc(&d_rows, bytes));
+    BYTES_TRY(job.alloc(&d_out, bytes));
+    BYTES_TRY(job.alloc(&d_scratch, core_scratch_bytes(len)));
+    BYTES_TRY(hipMemcpyAsync(d_rows, host_rows, bytes, hipMemcpyHostToDevice, job.s));
     const uint8_t* rows = static_cast<const uint8_t*>(d_rows);
     char* scratch = static_cast<char*>(d_scratch);
-    rc = bytes_order(rows, len, row_bytes, key_offset, key_bytes, scratch, s, err);
+    rc = bytes_order(rows, len, row_bytes, key_offset, key_bytes, scratch, job.s, err);
     if (rc == RDST_OK)
         rc = bytes_gather(rows, static_cast<uint8_t*>(d_out), reinterpret_cast<const uint32_t*>(scratch + make_layout(len).idx), len,
-                          row_bytes, s, err);
-    if (rc == RDST_OK) rc = rdst_hip_device_status(s);
-    if (rc != RDST_OK) return done(rc);
+                          row_bytes, job.s, err);
+    if (rc == RDST_OK) rc = rdst_hip_device_status(job.s);
+    if (rc != RDST_OK) return rc;
     // the host buffer is written only now, after the device reported success
-    HOST_TRY(hipMemcpyAsync(host_rows, d_out, bytes, hipMemcpyDeviceToHost, s));
-    HOST_TRY(hipStreamSynchronize(s));
-#undef HOST_TRY
-    return done(RDST_OK);
+    BYTES_TRY(hipMemcpyAsync(host_rows, d_out, bytes, hipMemcpyDeviceToHost, job.s));
+    BYTES_TRY(hipStreamSynchronize(job.s));
+    return RDST_OK;
 }
 
 }  // namespace rdst_internal

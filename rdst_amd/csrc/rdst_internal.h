@@ -12,6 +12,44 @@ namespace rdst_internal {
 // Records `what` (and the HIP error, if any) for rdst_hip_last_error and returns `code`.
 int set_error(int code, const char* what, hipError_t e = hipSuccess);
 
+// hipFuncSetAttribute(MaxDynamicSharedMemorySize) acts on the CURRENT device's copy of the function: remembers
+// (device, kernel) -> bytes.  Callers hold the library's mutex.
+int ensure_lds_attr(const void* fn, size_t lds);
+
+// Every kernel launch of the library: sets the dynamic-LDS attribute if the kernel has dynamic LDS, launches, and reports a
+// refused launch through set_error, naming the kernel.  Does not wait for the device.
+template <typename... P, typename... A>
+int launch(const char* name, void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, const A&... args) {
+    if (lds != 0)
+        if (int rc = ensure_lds_attr(reinterpret_cast<const void*>(kernel), lds)) return rc;
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+    const hipError_t e = hipGetLastError();
+    return e == hipSuccess ? RDST_OK : set_error(RDST_ERR_HIP, name, e);
+}
+
+// What a blocking host entry point owns: its stream, its device buffers and the device it switched away from.  All of it is
+// given back when the entry point returns, on whatever path, after the work still queued on the stream has finished.
+struct HostJob {
+    hipStream_t s = nullptr;
+    int prev_dev = -1;
+    void* bufs[8] = {};
+    int nbufs = 0;
+    hipError_t alloc(void** p, size_t bytes) {
+        if (nbufs == 8) return hipErrorOutOfMemory;
+        const hipError_t e = hipMalloc(p, bytes);
+        if (e == hipSuccess) bufs[nbufs++] = *p;
+        return e;
+    }
+    HostJob() = default;
+    HostJob(const HostJob&) = delete;
+    ~HostJob() {
+        if (s) (void)hipStreamSynchronize(s);
+        for (int i = 0; i < nbufs; ++i) (void)hipFree(bufs[i]);
+        if (s) (void)hipStreamDestroy(s);
+        if (prev_dev >= 0) (void)hipSetDevice(prev_dev);
+    }
+};
+
 // The current device's sticky error word (kernels OR bits into it; rdst_hip_device_status reports and clears it).
 int device_error_word(uint32_t** out);
 

@@ -4355,13 +4355,8 @@ constexpr int default_cfg(uint32_t elem_bytes, uint64_t n, bool mapped = false) 
 // keys per thread for a key width, from the table's 8-byte figure: same bytes per thread
 constexpr int kpt_for(int kpt8, size_t elem_bytes) { return elem_bytes <= 4 ? kpt8 * 2 : (elem_bytes == 8 ? kpt8 : (kpt8 / 2) & ~1); }
 
-struct Tuning {
-    int pass_cfg = -1;  // < 0: default_cfg()
-    int hist_bpc = 0;
-    bool profiling = false;
-    bool chains = true;
-    int fast_rank = 1;
-    bool small_sort = true;
+// What rdst_hip_set_hybrid's mode decides (kRouteModes)
+struct RouteTuning {
     bool hybrid = true;                 // consider the hybrid route at all
     bool count_sort = true;             // 4-byte keys: K4 as a counting sort by value (false: the generic ranked passes)
     bool halves = true;                 // 4-byte keys: pass L-1 hands K4 the low halves only (16-bit array in the workspace)
@@ -4374,10 +4369,18 @@ struct Tuning {
     bool chain_routes = true;           // behind a failed atomic route try the hybrid route before the LSD one
     bool expand = true;                 // 4-byte keys: buckets the counting K4 refuses go to the expanding one (any bucket below 65 536 keys)
     bool atomic_wide = true;            // ROUTE_ATOMIC for 8-byte keys too (whole keys in the slots)
-    bool persist_fallback = true;       // behind the atomic route the LSD passes run as persistent blocks (cheap to skip)
-    bool split_always = false;          // ... at every length, in eight parts (tests)
     bool split = true;                  // 8-byte keys beyond the atomic route's window: one exact pass on the top byte, then its groups as slices of their own (run_split_sort)
+    bool split_always = false;          // ... at every length, in eight parts (tests)
     bool predict = true;                // the sample may predict the LSD route (Plan::predict_lsd): neither MSD passes nor K1h are tried
+};
+struct Tuning : RouteTuning {
+    int pass_cfg = -1;  // < 0: default_cfg()
+    int hist_bpc = 0;
+    bool profiling = false;
+    bool chains = true;
+    int fast_rank = 1;
+    bool small_sort = true;
+    bool persist_fallback = true;       // behind the atomic route the LSD passes run as persistent blocks (cheap to skip)
     uint64_t hybrid_min_len = 0;        // rdst_hip_set_hybrid's min_len; 0: the measured defaults below (atomic_min_len, hybrid_min_len)
 };
 uint32_t g_ablate = 0;  // only ever set by the RDST_EXPERIMENTS build
@@ -4385,6 +4388,33 @@ uint32_t g_ablate = 0;  // only ever set by the RDST_EXPERIMENTS build
 size_t g_exp_lds_total = 0;
 #endif
 Tuning g_tuning;
+
+// rdst_hip_set_hybrid's modes (include/rdst_hip.h; rdst_amd/radix_sort.py ROUTE_MODES carries the same names): the default
+// with or without the atomic route, and at most one field changed.  Any other integer: "k1h".
+constexpr RouteTuning route_preset(bool atomic_route, bool RouteTuning::*field = nullptr, bool value = false) {
+    RouteTuning r;
+    r.atomic_route = atomic_route;
+    if (field) r.*field = value;
+    return r;
+}
+constexpr struct RouteMode { int mode; const char* name; RouteTuning preset; } kRouteModes[] = {
+    {7, "k1h", route_preset(false)},                                            // start at the K1h hybrid route, every key width (first: the fallback)
+    {0, "lsd", route_preset(false, &RouteTuning::hybrid, false)},               // LSD route always
+    {1, "default", route_preset(true)},                                         // 4- and 8-byte keys try the atomic route first
+    {2, "ranked", route_preset(false, &RouteTuning::count_sort, false)},        // hybrid route with the generic local sort for every key width
+    {3, "count_whole_keys", route_preset(false, &RouteTuning::halves, false)},  // counting K4 reading whole keys (no 16-bit hand-off)
+    {5, "no_presample", route_preset(false, &RouteTuning::presample, false)},   // every hybrid-eligible sort counts all its keys' prefixes first
+    {6, "wide_one_block", route_preset(false, &RouteTuning::wide2, false)},     // 8-byte keys with the one-block-per-CU form of K4
+    {8, "atomic_4_only", route_preset(true, &RouteTuning::atomic_wide, false)}, // 8-byte keys on the K1h hybrid route
+    {9, "no_expand", route_preset(false, &RouteTuning::expand, false)},         // buckets up to one tile; refused buckets to the ranked kernel
+    {10, "atomic_then_lsd", route_preset(true, &RouteTuning::chain_routes, false)},  // a failed atomic route falls straight to the LSD route
+    {11, "no_giants", route_preset(true, &RouteTuning::giants, false)},         // a bucket of 65 536 keys sends the sort down the LSD route
+    {12, "no_exact_msd", route_preset(true, &RouteTuning::exact_msd, false)},   // the hybrid route's passes are K3's
+    {14, "no_predict", route_preset(true, &RouteTuning::predict, false)},       // without the sample's prediction of the LSD route
+    {15, "wide2", route_preset(true, &RouteTuning::wide3, false)},              // the second form of the 8-byte K4 (local_wide2_sort_kernel)
+    {16, "no_split", route_preset(true, &RouteTuning::split, false)},           // slices beyond the atomic route's window take the LSD route
+    {17, "split_always", route_preset(true, &RouteTuning::split_always, true)}, // that split at every length, in eight parts (tests)
+};
 std::mutex g_mutex;
 
 struct DeviceState {
@@ -4626,17 +4656,23 @@ bool hybrid_eligible(uint64_t n, size_t key_bytes) {
            n < (1ull << 32);
 }
 
-// hipFuncSetAttribute acts on the CURRENT device's copy of the function: remember (device, kernel) -> bytes
-int ensure_lds_attr(const void* fn, size_t lds) {
-    static std::map<std::pair<int, const void*>, size_t> done;  // callers hold g_mutex
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    auto it = done.find({dev, fn});
-    if (it != done.end() && it->second == lds) return RDST_OK;
-    HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-    done[{dev, fn}] = lds;
-    return RDST_OK;
+using rdst_internal::launch;  // every kernel launch: LDS attribute, launch, launch error -> fail() naming the kernel
+
+// Run-time booleans to compile-time ones: with_bools(f, a, b) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}), so a
+// kernel's argument list is written once for all its variants.  Every combination of the booleans is instantiated: a variant
+// that is built for some key widths only stays behind an `if constexpr` at the call site.
+template <typename F>
+int with_bools(F&& f) { return f(); }
+template <typename F, typename... B>
+int with_bools(F&& f, bool b, B... rest) {
+    return b ? with_bools([&](auto... c) { return f(std::true_type{}, c...); }, rest...)
+             : with_bools([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
 }
+template <typename K>
+constexpr int vec_for(bool aligned) { return aligned ? 16 / (int)sizeof(K) : 1; }  // keys per 16-byte load, if the pointer allows one
+bool aligned16(const void* a, const void* b = nullptr) { return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) == 0; }
+
+uint32_t rank_flags() { return (g_tuning.fast_rank ? RDST_FAST_RANK : 0u) | (g_tuning.fast_rank == 2 ? RDST_FAST_RANK_SELFTEST : 0u); }
 
 KeyMap key_map_for(rdst_key_kind kind, uint32_t elem_bytes) {
     const u128 msb = (u128)1 << (elem_bytes * 8 - 1);
@@ -4648,258 +4684,255 @@ KeyMap key_map_for(rdst_key_kind kind, uint32_t elem_bytes) {
     }
 }
 
-template <typename K, int LEVELS, int VEC, bool PAIR>
-int launch_hist_v(const K* keys, uint64_t n, uint32_t blocks, KeyMap km, unsigned long long* hpos, unsigned long long* hpair,
-                  uint32_t* inversion, const Plan* plan, hipStream_t s, uint64_t* piece_out, int base_level = 0) {
-    *piece_out = hist_piece(n, blocks, (uint64_t)HIST_THREADS * VEC * 4);
-    constexpr size_t lds = (size_t)HistPlan<LEVELS, PAIR>::WORDS * sizeof(uint32_t);
-    if (int rc = ensure_lds_attr(reinterpret_cast<const void*>(&hist_kernel<K, LEVELS, VEC, PAIR>), lds)) return rc;
-    hipLaunchKernelGGL((hist_kernel<K, LEVELS, VEC, PAIR>), dim3(blocks), dim3(HIST_THREADS), lds, s, keys, n, (K)km.neg,
-                       (K)km.pos, hpos, hpair, inversion, plan, base_level);
-    HIP_TRY(hipGetLastError());
-    return RDST_OK;
-}
+// Words of the header at Layout::off_err, cleared with every sort (word 0 is unused: the error word itself lives in
+// DeviceState::err_dev)
+enum HeaderWord : uint32_t {
+    HDR_INVERSION = 1,     // an inversion was seen: the slice is not sorted already
+    HDR_H16_OVERFLOW = 2,  // a K1h counter overflowed
+    HDR_FBLIST_LEN = 3,    // length of K4's first hand-on list (fblist)
+    HDR_MSD_OVERFLOW = 4,  // an area or a slot of the atomic route overflowed
+    HDR_FBLIST2_LEN = 5,   // length of K4's second list (fblist2)
+};
 
-// pair == true also fills the joint tables the chain split of the later passes needs
-template <typename K, int LEVELS>
-int launch_hist(const K* keys, uint64_t n, uint32_t blocks, KeyMap km, unsigned long long* hpos, unsigned long long* hpair,
-                bool pair, uint32_t* inversion, const Plan* plan, hipStream_t s, uint64_t* piece_out, int base_level = 0) {
-    const bool aligned = (reinterpret_cast<uintptr_t>(keys) & 15u) == 0;
-    constexpr int V = 16 / sizeof(K);
-    if constexpr (LEVELS >= 2) {
-        if (pair) {
-            if (aligned) return launch_hist_v<K, LEVELS, V, true>(keys, n, blocks, km, hpos, hpair, inversion, plan, s, piece_out);
-            return launch_hist_v<K, LEVELS, 1, true>(keys, n, blocks, km, hpos, hpair, inversion, plan, s, piece_out);
-        }
+// The workspace of one pipeline as typed pointers: the only place that casts ws + Layout::off_*
+struct WsView {
+    char* ws = nullptr;
+    Layout L{};
+    uint32_t *inversion, *h16_overflow, *fblist_len, *msd_overflow, *fblist2_len;  // the header words
+    Plan* plan;
+    unsigned long long *hpos, *hpair, *hpos16, *hist;
+    uint32_t *h16, *bstart, *fblist, *fblist2, *xtile0, *cursor_a, *cursor_b;
+    uint32_t *glist, *gcount_item, *gexp_item, *gtables;  // giants of the hybrid route: buckets, first counting / expanding item, count tables
+    GiantItem* gsplit;
+    uint64_t* base;
+
+    WsView() = default;
+    WsView(char* ws_, const Layout& L_) : ws(ws_), L(L_) {
+        inversion = at<uint32_t>(L.off_err) + HDR_INVERSION;
+        h16_overflow = at<uint32_t>(L.off_err) + HDR_H16_OVERFLOW;
+        fblist_len = at<uint32_t>(L.off_err) + HDR_FBLIST_LEN;
+        msd_overflow = at<uint32_t>(L.off_err) + HDR_MSD_OVERFLOW;
+        fblist2_len = at<uint32_t>(L.off_err) + HDR_FBLIST2_LEN;
+        plan = at<Plan>(L.off_plan);
+        hpos = at<unsigned long long>(L.off_hpos);
+        hpair = at<unsigned long long>(L.off_hpair);
+        hpos16 = at<unsigned long long>(L.off_hpos16);
+        hist = at<unsigned long long>(L.off_hist);
+        h16 = at<uint32_t>(L.off_h16);
+        bstart = at<uint32_t>(L.off_bstart);
+        fblist = at<uint32_t>(L.off_fblist);
+        fblist2 = at<uint32_t>(L.off_fblist2);
+        xtile0 = at<uint32_t>(L.off_xtile0);
+        cursor_a = at<uint32_t>(L.off_cursor_a);
+        cursor_b = at<uint32_t>(L.off_cursor_b);
+        glist = at<uint32_t>(L.off_glist);
+        gcount_item = glist + GIANT_MAX + 16;
+        gexp_item = gcount_item + GIANT_MAX + 16;
+        gtables = at<uint32_t>(L.off_gtables);
+        gsplit = at<GiantItem>(L.off_gsplit);
+        base = at<uint64_t>(L.off_base);
     }
-    if (aligned) return launch_hist_v<K, LEVELS, V, false>(keys, n, blocks, km, hpos, hpair, inversion, plan, s, piece_out, base_level);
-    return launch_hist_v<K, LEVELS, 1, false>(keys, n, blocks, km, hpos, hpair, inversion, plan, s, piece_out, base_level);
+    template <typename T>
+    T* at(size_t off) const { return reinterpret_cast<T*>(ws + off); }
+    // per level (no argument: the first level's, i.e. the whole table)
+    template <typename S>
+    S* status(int level = 0) const { return at<S>(L.off_status) + (size_t)level * L.tiles * RADIX; }
+    template <typename S>
+    S* status_near(int level = 0) const { return at<S>(L.off_status_near) + (size_t)level * L.tiles * RADIX; }
+    uint64_t* cbase(int level = 0) const { return at<uint64_t>(L.off_cbase) + (size_t)level * CHAINS * RADIX; }
+    LevelChains* chains(int level = 0) const { return at<LevelChains>(L.off_chains) + level; }
+    uint32_t* tickets(int level = 0) const { return at<uint32_t>(L.off_tickets) + (size_t)level * TICKET_ROW; }
+    template <typename K>
+    K* area_a() const { return at<K>(L.off_msd_a); }  // ROUTE_ATOMIC: the areas of pass A
+    // the region at off_halves holds one of three things:
+    uint16_t* halves16() const { return at<uint16_t>(L.off_halves); }  // hybrid route, 4-byte keys: the low halves pass L-1 leaves for K4
+    uint16_t* slots16() const { return at<uint16_t>(L.off_halves); }   // atomic route, 4-byte keys: pass B's slots of low halves
+    template <typename K>
+    K* slots() const { return at<K>(L.off_halves); }                   // atomic route, 8-byte keys: pass B's slots of whole keys
+};
+
+// which routes a sort may take, its pass shape and the workspace that needs
+struct RoutePick { bool try_atomic, try_hybrid, halves, giants; int cfg; Layout L; };
+
+// What the stages of one run_pipeline share
+template <typename K, typename V>
+struct Pipe {
+    DeviceState* D;
+    hipStream_t s;
+    K *keys, *tmp;
+    V *vals, *vtmp;
+    uint64_t n;
+    uint32_t level_lo, level_hi;
+    bool allow_skip, copy_back, deliver_tmp;
+    KeyMap km;
+    bool mapped;          // signed or float keys: the kernels map them to unsigned order
+    RoutePick rp;
+    WsView w;
+    uint32_t blocks = 0;  // K1's grid; K1h and the exact pass A cut the slice the same way
+    bool pair = false;    // K1 also fills the joint tables of the chain split
+};
+
+template <int LEVELS, typename K, typename V>
+int launch_hist(const Pipe<K, V>& p, bool pair, const Plan* plan, uint64_t* piece_out, int base_level = 0) {
+    auto go = [&](auto ALIGNED, auto PAIR) {
+        constexpr int VEC = vec_for<K>(ALIGNED);
+        constexpr size_t lds = (size_t)HistPlan<LEVELS, PAIR>::WORDS * sizeof(uint32_t);
+        *piece_out = hist_piece(p.n, p.blocks, (uint64_t)HIST_THREADS * VEC * 4);
+        return launch("hist_kernel", hist_kernel<K, LEVELS, VEC, PAIR>, dim3(p.blocks), dim3(HIST_THREADS), lds, p.s, p.keys, p.n, (K)p.km.neg,
+                      (K)p.km.pos, p.w.hpos, p.w.hpair, p.w.inversion, plan, base_level);
+    };
+    // pair == true also fills the joint tables the chain split of the later passes needs
+    if constexpr (LEVELS >= 2) {
+        if (pair) return with_bools([&](auto ALIGNED) { return go(ALIGNED, std::true_type{}); }, aligned16(p.keys));
+    }
+    return with_bools([&](auto ALIGNED) { return go(ALIGNED, std::false_type{}); }, aligned16(p.keys));
 }
 
 // the look before K1h / before the atomic route's first pass
-template <typename K>
-int launch_presample(const K* keys, uint64_t n, KeyMap km, Plan* plan, hipStream_t s) {
-    if (!g_tuning.presample || n < PRESAMPLE_MIN_LEN) return RDST_OK;
-    const bool mapped = km.neg != 0 || km.pos != 0;
-    const uint32_t limit = 12u + (uint32_t)(4ull * (uint64_t)local_tile(sizeof(K)) * PRESAMPLE_KEYS / n);
-    constexpr size_t plds = presample_lds_bytes();
+template <typename K, typename V>
+int launch_presample(const Pipe<K, V>& p) {
+    if (!g_tuning.presample || p.n < PRESAMPLE_MIN_LEN) return RDST_OK;
+    const uint32_t limit = 12u + (uint32_t)(4ull * (uint64_t)local_tile(sizeof(K)) * PRESAMPLE_KEYS / p.n);
     // what route_kernel will hold against the exact counts (RouteArgs::giant_max, cap), for the sample's prediction
     const bool big4 = sizeof(K) == 4 && g_tuning.count_sort && g_tuning.expand && g_tuning.predict;
     const uint32_t giant_min = big4 ? GIANT_MIN : 0u;
-    const uint32_t giant_max = big4 && g_tuning.giants && n < (1ull << 30) ? GIANT_MAX : 0u;
+    const uint32_t giant_max = big4 && g_tuning.giants && p.n < (1ull << 30) ? GIANT_MAX : 0u;
     const uint32_t bucket_cap = sizeof(K) == 8 && g_tuning.predict ? (uint32_t)local_tile(8) : 0u;
-    if (mapped) {
-        if (int rc = ensure_lds_attr(reinterpret_cast<const void*>(&presample_kernel<K, true>), plds)) return rc;
-        hipLaunchKernelGGL((presample_kernel<K, true>), dim3(1), dim3(1024), plds, s, keys, n, (K)km.neg, (K)km.pos, plan, limit, giant_min, giant_max, bucket_cap);
-    } else {
-        if (int rc = ensure_lds_attr(reinterpret_cast<const void*>(&presample_kernel<K, false>), plds)) return rc;
-        hipLaunchKernelGGL((presample_kernel<K, false>), dim3(1), dim3(1024), plds, s, keys, n, (K)km.neg, (K)km.pos, plan, limit, giant_min, giant_max, bucket_cap);
-    }
-    HIP_TRY(hipGetLastError());
-    return RDST_OK;
+    return with_bools([&](auto MAPPED) {
+        return launch("presample_kernel", presample_kernel<K, MAPPED>, dim3(1), dim3(1024), presample_lds_bytes(), p.s, p.keys, p.n, (K)p.km.neg,
+                      (K)p.km.pos, p.w.plan, limit, giant_min, giant_max, bucket_cap);
+    }, p.mapped);
 }
 
 // K1h: the hybrid route's 65 536-bin count (same grid and pieces as K1)
-template <typename K>
-int launch_hist16(const K* keys, uint64_t n, uint32_t blocks, KeyMap km, uint32_t* h16, unsigned long long* hpos16, uint32_t* inversion,
-                  uint32_t* overflow, Plan* plan, hipStream_t s, bool sample_first = true, bool giant = false, uint32_t pre_launch = 0) {
-    const bool aligned = (reinterpret_cast<uintptr_t>(keys) & 15u) == 0;
-    const bool mapped = km.neg != 0 || km.pos != 0;
-    if (sample_first)
-        if (int rc = launch_presample<K>(keys, n, km, plan, s)) return rc;
-    constexpr int V = 16 / sizeof(K);
-    constexpr size_t lds = (size_t)H16_WORDS * sizeof(uint32_t);
-#define RDST_H16(VEC, MAPPED)                                                                                              \
-    do {                                                                                                                   \
-        if (int rc = ensure_lds_attr(reinterpret_cast<const void*>(&hist16_kernel<K, VEC, MAPPED>), lds)) return rc;       \
-        hipLaunchKernelGGL((hist16_kernel<K, VEC, MAPPED>), dim3(blocks), dim3(HIST_THREADS), lds, s, keys, n, (K)km.neg,  \
-                           (K)km.pos, h16, hpos16, inversion, overflow, plan, pre_launch);                                 \
-    } while (0)
-#define RDST_H16G(VEC, MAPPED)                                                                                             \
-    do {                                                                                                                   \
-        if (int rc = ensure_lds_attr(reinterpret_cast<const void*>(&hist16_kernel<K, VEC, MAPPED, true>), lds)) return rc; \
-        hipLaunchKernelGGL((hist16_kernel<K, VEC, MAPPED, true>), dim3(blocks), dim3(HIST_THREADS), lds, s, keys, n,       \
-                           (K)km.neg, (K)km.pos, h16, hpos16, inversion, overflow, plan, pre_launch);                      \
-    } while (0)
-    if constexpr (sizeof(K) == 4) {
-        if (giant) {
-            if (aligned) { if (mapped) RDST_H16G(V, true); else RDST_H16G(V, false); }
-            else { if (mapped) RDST_H16G(1, true); else RDST_H16G(1, false); }
-            HIP_TRY(hipGetLastError());
-            return RDST_OK;
-        }
+template <typename K, typename V>
+int launch_hist16(const Pipe<K, V>& p, uint32_t pre_launch) {
+    auto go = [&](auto ALIGNED, auto MAPPED, auto GIANT) {
+        return launch("hist16_kernel", hist16_kernel<K, vec_for<K>(ALIGNED), MAPPED, GIANT>, dim3(p.blocks), dim3(HIST_THREADS),
+                      (size_t)H16_WORDS * sizeof(uint32_t), p.s, p.keys, p.n, (K)p.km.neg, (K)p.km.pos, p.w.h16, p.w.hpos16, p.w.inversion,
+                      p.w.h16_overflow, p.w.plan, pre_launch);
+    };
+    if constexpr (sizeof(K) == 4) {  // (only 4-byte keys have giants)
+        if (p.rp.giants) return with_bools([&](auto ALIGNED, auto MAPPED) { return go(ALIGNED, MAPPED, std::true_type{}); }, aligned16(p.keys), p.mapped);
     }
-#undef RDST_H16G
-    if (aligned) { if (mapped) RDST_H16(V, true); else RDST_H16(V, false); }
-    else { if (mapped) RDST_H16(1, true); else RDST_H16(1, false); }
-#undef RDST_H16
-    HIP_TRY(hipGetLastError());
-    return RDST_OK;
+    return with_bools([&](auto ALIGNED, auto MAPPED) { return go(ALIGNED, MAPPED, std::false_type{}); }, aligned16(p.keys), p.mapped);
 }
 
 #ifndef RDST_COUNT_THREADS
 #define RDST_COUNT_THREADS 512  // three blocks per CU (48 KiB of LDS each, 80 VGPRs): 1.41 ms per 10^9 keys against 1.65 for two blocks of 1024
 #endif
 constexpr int COUNT_THREADS = RDST_COUNT_THREADS;
-// K4: one workgroup per bucket of the hybrid route.  4-byte keys: the counting kernel, then the generic one
-// over the (normally empty) list of buckets it could not take; 8-byte keys: the generic one over all buckets.
-struct GiantArgs {
-    uint32_t *glist, *gcount_item, *gexp_item, *tables;
-    GiantItem* recs;
-};
 
-template <typename K>
-int launch_local_sort(K* keys, K* tmp, const uint32_t* bstart, const Plan* plan, uint32_t* err, KeyMap km, uint32_t* list,
-                      uint32_t* list_count, const uint16_t* src16, int cus, hipStream_t s, const uint32_t* slot_count = nullptr,
-                      uint32_t slot_cap = 0, const K* src_slots = nullptr, uint32_t* list2 = nullptr, uint32_t* list2_count = nullptr,
-                      const GiantArgs* ga = nullptr) {
-    constexpr int NW = local_waves(sizeof(K)), KPT = local_kpt(sizeof(K));
-    constexpr size_t lds = local_lds_bytes(sizeof(K));
-    const bool mapped = km.neg != 0 || km.pos != 0;
-    const uint32_t flags = (g_tuning.fast_rank ? RDST_FAST_RANK : 0u) | (g_tuning.fast_rank == 2 ? RDST_FAST_RANK_SELFTEST : 0u);
-    const bool counting = sizeof(K) == 4 && g_tuning.count_sort;
-    if constexpr (sizeof(K) == 4) {
-        if (counting) {
-            constexpr size_t clds = count_lds_bytes();
-#define RDST_COUNT(MAPPED, FROM16)                                                                                                   \
-    do {                                                                                                                             \
-        if (int rc = ensure_lds_attr(reinterpret_cast<const void*>(&local_count_sort_kernel<COUNT_THREADS, MAPPED, FROM16>), clds)) return rc; \
-        hipLaunchKernelGGL((local_count_sort_kernel<COUNT_THREADS, MAPPED, FROM16>), dim3(H16_BINS), dim3(COUNT_THREADS), clds, s, keys, tmp, \
-                           src16, bstart, plan, err, (uint32_t)km.neg, (uint32_t)km.pos, list, list_count, slot_count, slot_cap); \
-    } while (0)
-            if (src16) { if (mapped) RDST_COUNT(true, true); else RDST_COUNT(false, true); }
-            else { if (mapped) RDST_COUNT(true, false); else RDST_COUNT(false, false); }
-#undef RDST_COUNT
-            HIP_TRY(hipGetLastError());
-            if (g_tuning.expand && list2) {  // what the counting kernel listed (a value 16 times, a bucket over its tile): one block per CU
-                constexpr size_t elds = expand_lds_bytes();
-#define RDST_COUNT16(MAPPED, FROM16)                                                                                                 \
-    do {                                                                                                                             \
-        if (int rc = ensure_lds_attr(reinterpret_cast<const void*>(&local_count16_sort_kernel<MAPPED, FROM16>), elds)) return rc;    \
-        hipLaunchKernelGGL((local_count16_sort_kernel<MAPPED, FROM16>), dim3((uint32_t)cus), dim3(COUNT16_THREADS), elds, s, keys, tmp, \
-                           src16, bstart, plan, (uint32_t)km.neg, (uint32_t)km.pos, list, list_count, list2, list2_count, slot_count, slot_cap); \
-    } while (0)
-                if (src16) { if (mapped) RDST_COUNT16(true, true); else RDST_COUNT16(false, true); }
-                else { if (mapped) RDST_COUNT16(true, false); else RDST_COUNT16(false, false); }
-#undef RDST_COUNT16
-                HIP_TRY(hipGetLastError());
-#define RDST_EXPAND(MAPPED, FROM16)                                                                                                  \
-    do {                                                                                                                             \
-        if (int rc = ensure_lds_attr(reinterpret_cast<const void*>(&local_expand_sort_kernel<MAPPED, FROM16>), elds)) return rc;     \
-        hipLaunchKernelGGL((local_expand_sort_kernel<MAPPED, FROM16>), dim3((uint32_t)cus), dim3(EXPAND_THREADS), elds, s, keys, tmp, \
-                           src16, bstart, plan, err, (uint32_t)km.neg, (uint32_t)km.pos, list2, list2_count, slot_count, slot_cap); \
-    } while (0)
-                if (src16) { if (mapped) RDST_EXPAND(true, true); else RDST_EXPAND(false, true); }
-                else { if (mapped) RDST_EXPAND(true, false); else RDST_EXPAND(false, false); }
-#undef RDST_EXPAND
-                HIP_TRY(hipGetLastError());
-                if (ga) {  // the giants of the hybrid route (route_kernel listed them; none: four launches that return at once)
-                    constexpr size_t clds2 = giant_count_lds_bytes();
-                    hipLaunchKernelGGL(giant_zero_kernel, dim3((uint32_t)cus * 4), dim3(256), 0, s, plan, ga->tables);
-#define RDST_GCOUNT(MAPPED, FROM16)                                                                                                  \
-    do {                                                                                                                             \
-        if (int rc = ensure_lds_attr(reinterpret_cast<const void*>(&giant_count_kernel<MAPPED, FROM16>), clds2)) return rc;          \
-        hipLaunchKernelGGL((giant_count_kernel<MAPPED, FROM16>), dim3((uint32_t)cus), dim3(GIANT_THREADS), clds2, s, keys, tmp, src16, \
-                           bstart, plan, (uint32_t)km.neg, (uint32_t)km.pos, ga->glist, ga->gcount_item, ga->tables);               \
-    } while (0)
-                    if (src16) { if (mapped) RDST_GCOUNT(true, true); else RDST_GCOUNT(false, true); }
-                    else { if (mapped) RDST_GCOUNT(true, false); else RDST_GCOUNT(false, false); }
-#undef RDST_GCOUNT
-                    hipLaunchKernelGGL(giant_scan_kernel, dim3((uint32_t)cus), dim3(GIANT_THREADS), 0, s, plan, ga->tables);
-                    hipLaunchKernelGGL(giant_split_kernel, dim3((uint32_t)cus * 2), dim3(256), 0, s, plan, bstart, ga->glist, ga->gexp_item, ga->tables, ga->recs);
-                    if (mapped) hipLaunchKernelGGL((giant_expand_kernel<true>), dim3((uint32_t)cus * 8), dim3(GIANT_XTHREADS), 0, s, keys, tmp, plan, (uint32_t)km.neg, (uint32_t)km.pos, ga->tables, ga->recs);
-                    else hipLaunchKernelGGL((giant_expand_kernel<false>), dim3((uint32_t)cus * 8), dim3(GIANT_XTHREADS), 0, s, keys, tmp, plan, (uint32_t)km.neg, (uint32_t)km.pos, ga->tables, ga->recs);
-                    HIP_TRY(hipGetLastError());
-                }
-                return RDST_OK;  // (the list is spent: nothing is left for the ranked kernel)
-            }
-        }
-    }
-    bool listed = counting;
-    if constexpr (sizeof(K) == 8) {
-        if (g_tuning.count_sort) {
-            constexpr size_t wlds = wide_lds_bytes();
-            if (g_tuning.wide2 && g_tuning.wide3) {  // two 1024-thread blocks per CU, a third fewer LDS instructions than wide2
-                constexpr size_t w3 = wide3_lds_bytes();
-                if (mapped) {
-                    if (int rc = ensure_lds_attr(reinterpret_cast<const void*>(&local_wide3_sort_kernel<true>), w3)) return rc;
-                    hipLaunchKernelGGL((local_wide3_sort_kernel<true>), dim3(H16_BINS), dim3(WIDE3_THREADS), w3, s, keys, tmp, bstart, plan, err, (uint64_t)km.neg, (uint64_t)km.pos, list, list_count, src_slots, slot_count, slot_cap);
-                } else {
-                    if (int rc = ensure_lds_attr(reinterpret_cast<const void*>(&local_wide3_sort_kernel<false>), w3)) return rc;
-                    hipLaunchKernelGGL((local_wide3_sort_kernel<false>), dim3(H16_BINS), dim3(WIDE3_THREADS), w3, s, keys, tmp, bstart, plan, err, (uint64_t)km.neg, (uint64_t)km.pos, list, list_count, src_slots, slot_count, slot_cap);
-                }
-            } else if (g_tuning.wide2) {  // the same with half the prefix table and every per-key state re-read (A/B, tests)
-                constexpr size_t w2 = wide2_lds_bytes();
-                if (mapped) {
-                    if (int rc = ensure_lds_attr(reinterpret_cast<const void*>(&local_wide2_sort_kernel<true>), w2)) return rc;
-                    hipLaunchKernelGGL((local_wide2_sort_kernel<true>), dim3(H16_BINS), dim3(WIDE2_THREADS), w2, s, keys, tmp, bstart, plan, err, (uint64_t)km.neg, (uint64_t)km.pos, list, list_count, src_slots, slot_count, slot_cap);
-                } else {
-                    if (int rc = ensure_lds_attr(reinterpret_cast<const void*>(&local_wide2_sort_kernel<false>), w2)) return rc;
-                    hipLaunchKernelGGL((local_wide2_sort_kernel<false>), dim3(H16_BINS), dim3(WIDE2_THREADS), w2, s, keys, tmp, bstart, plan, err, (uint64_t)km.neg, (uint64_t)km.pos, list, list_count, src_slots, slot_count, slot_cap);
-                }
-            } else if (mapped) {
-                if (int rc = ensure_lds_attr(reinterpret_cast<const void*>(&local_wide_sort_kernel<true>), wlds)) return rc;
-                hipLaunchKernelGGL((local_wide_sort_kernel<true>), dim3(H16_BINS), dim3(WIDE_THREADS), wlds, s, keys, tmp, bstart, plan, err, (uint64_t)km.neg, (uint64_t)km.pos, list, list_count);
-            } else {
-                if (int rc = ensure_lds_attr(reinterpret_cast<const void*>(&local_wide_sort_kernel<false>), wlds)) return rc;
-                hipLaunchKernelGGL((local_wide_sort_kernel<false>), dim3(H16_BINS), dim3(WIDE_THREADS), wlds, s, keys, tmp, bstart, plan, err, (uint64_t)km.neg, (uint64_t)km.pos, list, list_count);
-            }
-            HIP_TRY(hipGetLastError());
-            listed = true;
-        }
-    }
-    const dim3 grid(listed ? (uint32_t)((sizeof(K) == 8 ? 1 : 2) * cus) : (uint32_t)H16_BINS);
-    const uint32_t* wl = listed ? list : nullptr;
-    if (mapped) {
-        if (int rc = ensure_lds_attr(reinterpret_cast<const void*>(&local_sort_kernel<K, NW, KPT, true>), lds)) return rc;
-        hipLaunchKernelGGL((local_sort_kernel<K, NW, KPT, true>), grid, dim3(NW * 64), lds, s, keys, tmp, bstart, plan, err, (K)km.neg, (K)km.pos, flags, wl, list_count, src16, slot_count, slot_cap, src_slots);
-    } else {
-        if (int rc = ensure_lds_attr(reinterpret_cast<const void*>(&local_sort_kernel<K, NW, KPT, false>), lds)) return rc;
-        hipLaunchKernelGGL((local_sort_kernel<K, NW, KPT, false>), grid, dim3(NW * 64), lds, s, keys, tmp, bstart, plan, err, (K)km.neg, (K)km.pos, flags, wl, list_count, src16, slot_count, slot_cap, src_slots);
-    }
-    HIP_TRY(hipGetLastError());
-    return RDST_OK;
+// K4 of 4-byte keys as a counting sort by value: the counting kernel over all buckets, then what it listed (a value 16 times, a
+// bucket over its tile) one block per CU, then the giants of the hybrid route
+template <typename V>
+int launch_count_sorts(const Pipe<uint32_t, V>& p, const uint16_t* src16, const uint32_t* slot_count) {
+    const WsView& w = p.w;
+    const uint32_t neg = (uint32_t)p.km.neg, pos = (uint32_t)p.km.pos, slot_cap = w.L.slot_cap;
+    const dim3 per_cu((uint32_t)p.D->cus);
+    uint32_t* err = p.D->err_dev;
+    int rc = with_bools([&](auto MAPPED, auto FROM16) {
+        return launch("local_count_sort_kernel", local_count_sort_kernel<COUNT_THREADS, MAPPED, FROM16>, dim3(H16_BINS), dim3(COUNT_THREADS),
+                      count_lds_bytes(), p.s, p.keys, p.tmp, src16, w.bstart, w.plan, err, neg, pos, w.fblist, w.fblist_len, slot_count, slot_cap);
+    }, p.mapped, src16 != nullptr);
+    if (rc || !g_tuning.expand) return rc;  // (without the expanding kernels the list goes to the ranked one)
+    rc = with_bools([&](auto MAPPED, auto FROM16) {
+        if (int r = launch("local_count16_sort_kernel", local_count16_sort_kernel<MAPPED, FROM16>, per_cu, dim3(COUNT16_THREADS), expand_lds_bytes(),
+                           p.s, p.keys, p.tmp, src16, w.bstart, w.plan, neg, pos, w.fblist, w.fblist_len, w.fblist2, w.fblist2_len, slot_count, slot_cap))
+            return r;
+        return launch("local_expand_sort_kernel", local_expand_sort_kernel<MAPPED, FROM16>, per_cu, dim3(EXPAND_THREADS), expand_lds_bytes(), p.s,
+                      p.keys, p.tmp, src16, w.bstart, w.plan, err, neg, pos, w.fblist2, w.fblist2_len, slot_count, slot_cap);
+    }, p.mapped, src16 != nullptr);
+    if (rc || !p.rp.giants) return rc;
+    // the giants of the hybrid route (route_kernel listed them; none: launches that return at once)
+    if ((rc = launch("giant_zero_kernel", giant_zero_kernel, dim3(per_cu.x * 4), dim3(256), 0, p.s, w.plan, w.gtables))) return rc;
+    rc = with_bools([&](auto MAPPED, auto FROM16) {
+        return launch("giant_count_kernel", giant_count_kernel<MAPPED, FROM16>, per_cu, dim3(GIANT_THREADS), giant_count_lds_bytes(), p.s, p.keys,
+                      p.tmp, src16, w.bstart, w.plan, neg, pos, w.glist, w.gcount_item, w.gtables);
+    }, p.mapped, src16 != nullptr);
+    if (rc) return rc;
+    if ((rc = launch("giant_scan_kernel", giant_scan_kernel, per_cu, dim3(GIANT_THREADS), 0, p.s, w.plan, w.gtables))) return rc;
+    if ((rc = launch("giant_split_kernel", giant_split_kernel, dim3(per_cu.x * 2), dim3(256), 0, p.s, w.plan, w.bstart, w.glist, w.gexp_item,
+                     w.gtables, w.gsplit)))
+        return rc;
+    return with_bools([&](auto MAPPED) {
+        return launch("giant_expand_kernel", giant_expand_kernel<MAPPED>, dim3(per_cu.x * 8), dim3(GIANT_XTHREADS), 0, p.s, p.keys, p.tmp, w.plan, neg,
+                      pos, w.gtables, w.gsplit);
+    }, p.mapped);
 }
 
-template <typename K, typename S, int KPT, int NWAVES, int STAGES, bool MAPPED, bool NARROW, typename V = NoVal, bool OUT16 = false, bool PERSIST = false>
-int launch_pass_t(K* keys, K* tmp, uint64_t n, int level, const Layout& L, char* ws, KeyMap km, int cus, hipStream_t s,
-                  V* vals = nullptr, V* vtmp = nullptr, uint16_t* out16 = nullptr) {
+// K4 of 8-byte keys: one block per bucket, in the form the tuning asks for; refused buckets are listed for the ranked kernel
+template <typename V>
+int launch_wide_sort(const Pipe<uint64_t, V>& p, const uint32_t* slot_count, const uint64_t* src_slots) {
+    const WsView& w = p.w;
+    const uint64_t neg = (uint64_t)p.km.neg, pos = (uint64_t)p.km.pos;
+    uint32_t* err = p.D->err_dev;
+    return with_bools([&](auto MAPPED) {
+        if (g_tuning.wide2 && g_tuning.wide3)  // two 1024-thread blocks per CU, a third fewer LDS instructions than wide2
+            return launch("local_wide3_sort_kernel", local_wide3_sort_kernel<MAPPED>, dim3(H16_BINS), dim3(WIDE3_THREADS), wide3_lds_bytes(), p.s, p.keys,
+                          p.tmp, w.bstart, w.plan, err, neg, pos, w.fblist, w.fblist_len, src_slots, slot_count, w.L.slot_cap);
+        if (g_tuning.wide2)  // the same with half the prefix table and every per-key state re-read (A/B, tests)
+            return launch("local_wide2_sort_kernel", local_wide2_sort_kernel<MAPPED>, dim3(H16_BINS), dim3(WIDE2_THREADS), wide2_lds_bytes(), p.s, p.keys,
+                          p.tmp, w.bstart, w.plan, err, neg, pos, w.fblist, w.fblist_len, src_slots, slot_count, w.L.slot_cap);
+        return launch("local_wide_sort_kernel", local_wide_sort_kernel<MAPPED>, dim3(H16_BINS), dim3(WIDE_THREADS), wide_lds_bytes(), p.s, p.keys, p.tmp,
+                      w.bstart, w.plan, err, neg, pos, w.fblist, w.fblist_len);
+    }, p.mapped);
+}
+
+// K4: one workgroup per bucket, for the hybrid and the atomic route alike: the atomic route's buckets lie in the slots, the
+// hybrid route's at their final place (4-byte keys: as low halves, in the same region of the workspace either way).
+// 4-byte keys: the counting kernels; 8-byte keys: the wide kernel; then the ranked kernel over the (normally empty) list of
+// buckets they could not take — or over every bucket, if the tuning turned the others off.
+template <typename K, typename V>
+int launch_local_sort(const Pipe<K, V>& p) {
+    constexpr int NW = local_waves(sizeof(K)), KPT = local_kpt(sizeof(K));
+    const WsView& w = p.w;
+    const uint32_t* slot_count = p.rp.try_atomic ? w.cursor_b : nullptr;
+    const uint16_t* src16 = sizeof(K) != 4 ? nullptr : (p.rp.try_atomic ? w.slots16() : (p.rp.halves ? w.halves16() : nullptr));
+    const K* src_slots = sizeof(K) == 8 && p.rp.try_atomic ? w.template slots<K>() : nullptr;
+    const bool listed = g_tuning.count_sort;
+    if (listed) {
+        int rc;
+        if constexpr (sizeof(K) == 4) rc = launch_count_sorts(p, src16, slot_count);
+        else rc = launch_wide_sort(p, slot_count, src_slots);
+        if (rc || (sizeof(K) == 4 && g_tuning.expand)) return rc;  // (the expanding kernels spent the list: nothing is left for the ranked one)
+    }
+    const dim3 grid(listed ? (uint32_t)((sizeof(K) == 8 ? 1 : 2) * p.D->cus) : (uint32_t)H16_BINS);
+    const uint32_t* wl = listed ? w.fblist : nullptr;
+    return with_bools([&](auto MAPPED) {
+        return launch("local_sort_kernel", local_sort_kernel<K, NW, KPT, MAPPED>, grid, dim3(NW * 64), local_lds_bytes(sizeof(K)), p.s, p.keys, p.tmp,
+                      w.bstart, w.plan, p.D->err_dev, (K)p.km.neg, (K)p.km.pos, rank_flags(), wl, w.fblist_len, src16, slot_count, w.L.slot_cap, src_slots);
+    }, p.mapped);
+}
+
+// K3: one scatter pass, in the shape the template arguments name
+template <typename S, int KPT, int NWAVES, int STAGES, bool MAPPED, bool NARROW, bool OUT16 = false, bool PERSIST = false, typename K, typename V>
+int launch_pass_t(const Pipe<K, V>& p, int level, uint16_t* out16 = nullptr) {
     constexpr int TILE = NWAVES * 64 * KPT;
     size_t lds = (size_t)pass_lds_bytes(NWAVES, NARROW ? 4 : 8, ((int)sizeof(K) + ValBytes<V>::value) * (TILE / STAGES));
-    auto kernel = &onesweep_kernel<K, S, KPT, NWAVES, STAGES, MAPPED, NARROW, V, OUT16, PERSIST>;
 #ifdef RDST_EXPERIMENTS
     if (g_exp_lds_total > lds) lds = g_exp_lds_total;  // fewer blocks per CU
 #endif
-    if (int rc = ensure_lds_attr(reinterpret_cast<const void*>(kernel), lds)) return rc;
-    const uint64_t* cbase = reinterpret_cast<const uint64_t*>(ws + L.off_cbase) + (size_t)level * CHAINS * RADIX;
-    S* status = reinterpret_cast<S*>(ws + L.off_status) + (size_t)level * L.tiles * RADIX;
-    S* status_near = reinterpret_cast<S*>(ws + L.off_status_near) + (size_t)level * L.tiles * RADIX;
-    const LevelChains* chains = reinterpret_cast<const LevelChains*>(ws + L.off_chains) + level;
-    uint32_t* ticket = reinterpret_cast<uint32_t*>(ws + L.off_tickets) + (size_t)level * TICKET_ROW;
-    const Plan* plan = reinterpret_cast<const Plan*>(ws + L.off_plan);
-    DeviceState* D = nullptr;
-    if (int rc = current_device_state(&D)) return rc;
-    uint32_t* err = D->err_dev;
+    const WsView& w = p.w;
     // >= one block per tile of any chain split; PERSIST: as many blocks as stay resident (two per CU for the shape it is built for)
-    const uint64_t resident = (uint64_t)cus * 2;
-    const dim3 grid((uint32_t)(PERSIST && resident < L.tiles ? resident : L.tiles)), block(NWAVES * 64);
-    hipLaunchKernelGGL((onesweep_kernel<K, S, KPT, NWAVES, STAGES, MAPPED, NARROW, V, OUT16, PERSIST>), grid, block, lds, s, keys, tmp, vals, vtmp, out16, n,
-                       level, cbase, status, status_near, chains, ticket, plan, err, (K)km.neg, (K)km.pos, g_ablate | (g_tuning.fast_rank ? RDST_FAST_RANK : 0u) | (g_tuning.fast_rank == 2 ? RDST_FAST_RANK_SELFTEST : 0u));
-    HIP_TRY(hipGetLastError());
-    return RDST_OK;
+    const uint64_t resident = (uint64_t)p.D->cus * 2;
+    const dim3 grid((uint32_t)(PERSIST && resident < w.L.tiles ? resident : w.L.tiles)), block(NWAVES * 64);
+    return launch("onesweep_kernel", onesweep_kernel<K, S, KPT, NWAVES, STAGES, MAPPED, NARROW, V, OUT16, PERSIST>, grid, block, lds, p.s, p.keys, p.tmp,
+                  p.vals, p.vtmp, out16, p.n, level, w.cbase(level), w.template status<S>(level), w.template status_near<S>(level), w.chains(level),
+                  w.tickets(level), w.plan, p.D->err_dev, (K)p.km.neg, (K)p.km.pos, g_ablate | rank_flags());
 }
 
-template <typename K, typename S, bool MAPPED, bool NARROW>
-int launch_pass_s(int cfg, K* keys, K* tmp, uint64_t n, int level, const Layout& L, char* ws, KeyMap km, int cus, hipStream_t s) {
-    switch (cfg) {
+template <typename S, bool MAPPED, bool NARROW, typename K>
+int launch_pass_s(const Pipe<K, NoVal>& p, int level) {
+    switch (p.rp.cfg) {
 #ifdef RDST_EXPERIMENTS  // the two small shapes are measured in DESIGN.md and only built into the tools library
-        case 0: return launch_pass_t<K, S, kpt_for(8, sizeof(K)), 8, 1, MAPPED, NARROW>(keys, tmp, n, level, L, ws, km, cus, s);
-        case 1: return launch_pass_t<K, S, kpt_for(12, sizeof(K)), 8, 2, MAPPED, NARROW>(keys, tmp, n, level, L, ws, km, cus, s);
+        case 0: return launch_pass_t<S, kpt_for(8, sizeof(K)), 8, 1, MAPPED, NARROW>(p, level);
+        case 1: return launch_pass_t<S, kpt_for(12, sizeof(K)), 8, 2, MAPPED, NARROW>(p, level);
 #endif
-        case 2: return launch_pass_t<K, S, kpt_for(12, sizeof(K)), 12, 2, MAPPED, NARROW>(keys, tmp, n, level, L, ws, km, cus, s);
-        case 3: return launch_pass_t<K, S, kpt_for(14, sizeof(K)), 12, 2, MAPPED, NARROW>(keys, tmp, n, level, L, ws, km, cus, s);
-        case 4: return launch_pass_t<K, S, kpt_for(11, sizeof(K)), 12, 1, MAPPED, NARROW>(keys, tmp, n, level, L, ws, km, cus, s);
-        case 5: return launch_pass_t<K, S, kpt_for(10, sizeof(K)), 12, 1, MAPPED, NARROW>(keys, tmp, n, level, L, ws, km, cus, s);
+        case 2: return launch_pass_t<S, kpt_for(12, sizeof(K)), 12, 2, MAPPED, NARROW>(p, level);
+        case 3: return launch_pass_t<S, kpt_for(14, sizeof(K)), 12, 2, MAPPED, NARROW>(p, level);
+        case 4: return launch_pass_t<S, kpt_for(11, sizeof(K)), 12, 1, MAPPED, NARROW>(p, level);
+        case 5: return launch_pass_t<S, kpt_for(10, sizeof(K)), 12, 1, MAPPED, NARROW>(p, level);
     }
     return fail(RDST_ERR_ARG, "pass config not built into this library (0 and 1 exist in the tools build only)");
 }
@@ -4908,46 +4941,28 @@ int launch_pass_s(int cfg, K* keys, K* tmp, uint64_t n, int level, const Layout&
 template <typename K>
 bool halves_possible(int cfg, uint64_t n) { return sizeof(K) == 4 && cfg == 4 && n < (1ull << 30); }
 
+// A pass of a key-only sort.  out16: level L-1 of the hybrid route, whose pass hands K4 the low halves; persist: the passes
+// behind a tried atomic route, as persistent blocks.  Both exist for the default shapes only (4-byte keys: shape 4 with 32-bit
+// status words and deltas; 8-byte keys: shape 5, 64-bit deltas at every length).
 template <typename K>
-int launch_pass(int cfg, K* keys, K* tmp, uint64_t n, int level, const Layout& L, char* ws, KeyMap km, int cus, hipStream_t s,
-                uint16_t* out16 = nullptr, bool persist = false) {
-    const bool mapped = km.neg != 0 || km.pos != 0;
-    const bool narrow = n * sizeof(K) < (1ull << 32);
+int launch_pass(const Pipe<K, NoVal>& p, int level, uint16_t* out16, bool persist) {
+    const int cfg = p.rp.cfg;
+    const bool narrow = p.n * sizeof(K) < (1ull << 32), status4 = p.w.L.status_bytes == 4;
     if constexpr (sizeof(K) == 4) {
-        if (persist && out16 && cfg == 4 && L.status_bytes == 4 && narrow) {  // behind the atomic route: level L-1, whose pass feeds K4 on the hybrid route
-            constexpr int KPT = kpt_for(11, sizeof(K));
-            return mapped ? launch_pass_t<K, uint32_t, KPT, 12, 1, true, true, NoVal, true, true>(keys, tmp, n, level, L, ws, km, cus, s, nullptr, nullptr, out16)
-                          : launch_pass_t<K, uint32_t, KPT, 12, 1, false, true, NoVal, true, true>(keys, tmp, n, level, L, ws, km, cus, s, nullptr, nullptr, out16);
-        }
-        if (persist && cfg == 4 && L.status_bytes == 4 && narrow) {  // the LSD fallback behind the atomic route
-            constexpr int KPT = kpt_for(11, sizeof(K));
-            return mapped ? launch_pass_t<K, uint32_t, KPT, 12, 1, true, true, NoVal, false, true>(keys, tmp, n, level, L, ws, km, cus, s)
-                          : launch_pass_t<K, uint32_t, KPT, 12, 1, false, true, NoVal, false, true>(keys, tmp, n, level, L, ws, km, cus, s);
+        if ((persist || out16) && cfg == 4 && status4 && narrow) {  // (32-bit status words: n < 2^30, as halves_possible asks)
+            if (out16)
+                return with_bools([&](auto MAPPED, auto PERSIST) { return launch_pass_t<uint32_t, kpt_for(11, 4), 12, 1, MAPPED, true, true, PERSIST>(p, level, out16); },
+                                  p.mapped, persist);
+            return with_bools([&](auto MAPPED) { return launch_pass_t<uint32_t, kpt_for(11, 4), 12, 1, MAPPED, true, false, true>(p, level); }, p.mapped);
         }
     }
     if constexpr (sizeof(K) == 8) {
-        if (persist && cfg == 5 && L.status_bytes == 4) {  // the same for 8-byte keys (64-bit deltas at every length: one shape)
-            return mapped ? launch_pass_t<K, uint32_t, 10, 12, 1, true, false, NoVal, false, true>(keys, tmp, n, level, L, ws, km, cus, s)
-                          : launch_pass_t<K, uint32_t, 10, 12, 1, false, false, NoVal, false, true>(keys, tmp, n, level, L, ws, km, cus, s);
-        }
+        if (persist && cfg == 5 && status4)
+            return with_bools([&](auto MAPPED) { return launch_pass_t<uint32_t, 10, 12, 1, MAPPED, false, false, true>(p, level); }, p.mapped);
     }
-    if constexpr (sizeof(K) == 4) {
-        if (out16 && halves_possible<K>(cfg, n) && L.status_bytes == 4 && narrow) {
-            constexpr int KPT = kpt_for(11, sizeof(K));
-            return mapped ? launch_pass_t<K, uint32_t, KPT, 12, 1, true, true, NoVal, true>(keys, tmp, n, level, L, ws, km, cus, s, nullptr, nullptr, out16)
-                          : launch_pass_t<K, uint32_t, KPT, 12, 1, false, true, NoVal, true>(keys, tmp, n, level, L, ws, km, cus, s, nullptr, nullptr, out16);
-        }
-    }
-    if (L.status_bytes == 4) {
-        if (narrow) {
-            return mapped ? launch_pass_s<K, uint32_t, true, true>(cfg, keys, tmp, n, level, L, ws, km, cus, s)
-                          : launch_pass_s<K, uint32_t, false, true>(cfg, keys, tmp, n, level, L, ws, km, cus, s);
-        }
-        return mapped ? launch_pass_s<K, uint32_t, true, false>(cfg, keys, tmp, n, level, L, ws, km, cus, s)
-                      : launch_pass_s<K, uint32_t, false, false>(cfg, keys, tmp, n, level, L, ws, km, cus, s);
-    }
-    return mapped ? launch_pass_s<K, unsigned long long, true, false>(cfg, keys, tmp, n, level, L, ws, km, cus, s)
-                  : launch_pass_s<K, unsigned long long, false, false>(cfg, keys, tmp, n, level, L, ws, km, cus, s);
+    if (status4)
+        return with_bools([&](auto MAPPED, auto NARROW) { return launch_pass_s<uint32_t, MAPPED, NARROW>(p, level); }, p.mapped, narrow);
+    return with_bools([&](auto MAPPED) { return launch_pass_s<unsigned long long, MAPPED, false>(p, level); }, p.mapped);
 }
 
 // Key-value passes: one shape, 768 threads, the whole tile of (key, value) pairs staged in LDS.
@@ -4955,21 +4970,316 @@ constexpr int pair_kpt(size_t key_bytes, size_t val_bytes) { return key_bytes + 
 constexpr int PAIR_WAVES = 12;
 
 template <typename K, typename V>
-int launch_pass_pairs(K* keys, K* tmp, V* vals, V* vtmp, uint64_t n, int level, const Layout& L, char* ws, KeyMap km, int cus,
-                      hipStream_t s) {
+int launch_pass_pairs(const Pipe<K, V>& p, int level) {
     constexpr int KPT = pair_kpt(sizeof(K), sizeof(V));
-    const bool mapped = km.neg != 0 || km.pos != 0;
-    const bool narrow = n * (sizeof(K) > sizeof(V) ? sizeof(K) : sizeof(V)) < (1ull << 32);
-    if (L.status_bytes == 4) {
-        if (narrow) {
-            return mapped ? launch_pass_t<K, uint32_t, KPT, PAIR_WAVES, 1, true, true, V>(keys, tmp, n, level, L, ws, km, cus, s, vals, vtmp)
-                          : launch_pass_t<K, uint32_t, KPT, PAIR_WAVES, 1, false, true, V>(keys, tmp, n, level, L, ws, km, cus, s, vals, vtmp);
-        }
-        return mapped ? launch_pass_t<K, uint32_t, KPT, PAIR_WAVES, 1, true, false, V>(keys, tmp, n, level, L, ws, km, cus, s, vals, vtmp)
-                      : launch_pass_t<K, uint32_t, KPT, PAIR_WAVES, 1, false, false, V>(keys, tmp, n, level, L, ws, km, cus, s, vals, vtmp);
+    const bool narrow = p.n * (sizeof(K) > sizeof(V) ? sizeof(K) : sizeof(V)) < (1ull << 32);
+    if (p.w.L.status_bytes == 4)
+        return with_bools([&](auto MAPPED, auto NARROW) { return launch_pass_t<uint32_t, KPT, PAIR_WAVES, 1, MAPPED, NARROW>(p, level); }, p.mapped, narrow);
+    return with_bools([&](auto MAPPED) { return launch_pass_t<unsigned long long, KPT, PAIR_WAVES, 1, MAPPED, false>(p, level); }, p.mapped);
+}
+
+// ---- the stages of run_pipeline, in the order it calls them ----
+
+// a slice of at most one small tile: the one-workgroup sort, in place, no workspace
+template <typename K, int LEVELS>
+int run_small_sort(DeviceState& D, K* keys, uint64_t n, rdst_key_kind kind, hipStream_t s) {
+    const KeyMap km = key_map_for(kind, sizeof(K));
+    const size_t lds = (size_t)SMALL_WAVES * 1024 + 16 + sizeof(K) * SMALL_THREADS * small_kpt(sizeof(K));
+    const int rc = with_bools([&](auto MAPPED) {
+        return launch("small_sort_kernel", small_sort_kernel<K, LEVELS, MAPPED>, dim3(1), dim3(SMALL_THREADS), lds, s, keys, (uint32_t)n, (K)km.neg, (K)km.pos);
+    }, km.neg != 0 || km.pos != 0);
+    if (rc == RDST_OK) D.last_plan_valid = false;
+    return rc;
+}
+
+// Which routes this sort may take, and the workspace that needs.  `lean`: the LSD route only (0.13 x the slice instead of
+// 1.7 x) — what is left when the device cannot spare the space of the byte-saving routes.
+// Hybrid route (whole sorts of 4- and 8-byte keys, long enough that a bucket is worth a workgroup, short enough that 65 536
+// tiles can hold it): K1h counts the buckets, route_kernel decides.  If it says LSD, K1 runs as ever (the slice is then read
+// twice for counting); if it says hybrid, K1 returns at once.
+template <int LEVELS, typename K, typename V>
+RoutePick pick_routes(const Pipe<K, V>& p, int cfg, bool lean) {
+    constexpr bool HAS_V = ValBytes<V>::value != 0;
+    const uint64_t n = p.n;
+    const bool whole_sort = !HAS_V && p.level_lo == 0 && p.level_hi == (uint32_t)LEVELS && p.allow_skip && p.copy_back;
+    RoutePick r{};
+    r.cfg = cfg;
+    r.try_atomic = !lean && whole_sort && atomic_eligible(n, sizeof(K), r.cfg);
+    // 8-byte keys: the fallback's passes run as persistent blocks of shape 5 (eight skipped passes of one block per tile cost 0.5 ms per 10^9 keys)
+    if (r.try_atomic && sizeof(K) == 8 && g_tuning.persist_fallback && g_tuning.pass_cfg < 0) r.cfg = 5;
+    // Behind a failed atomic route (an area or a slot overflowed) the hybrid route is tried next — exact counts, any bucket
+    // the local sort takes — and the LSD route last.  One launch sequence serves all three: every kernel looks at the plan.
+    const bool halves_cfg = g_tuning.halves && g_tuning.count_sort && halves_possible<K>(r.cfg, n);
+    r.try_hybrid = !lean && whole_sort && hybrid_eligible(n, sizeof(K)) && (!r.try_atomic || (g_tuning.chain_routes && (sizeof(K) == 8 || halves_cfg)));
+    r.halves = r.try_hybrid && halves_cfg;
+    // 4-byte keys: the hybrid route takes buckets of any size (K1h counts them exactly, the giant kernels of K4 sort them)
+    r.giants = r.try_hybrid && sizeof(K) == 4 && g_tuning.giants && g_tuning.count_sort && g_tuning.expand && n < (1ull << 30);
+    r.L = make_layout(n, sizeof(K), LEVELS, r.cfg, HAS_V ? PAIR_WAVES * 64 * pair_kpt(sizeof(K), ValBytes<V>::value) : 0, r.halves, r.try_atomic, r.giants);
+    return r;
+}
+
+// route pick + workspace: fills p.rp and p.w and waits for the workspace's previous user
+template <int LEVELS, typename K, typename V>
+int pick_workspace(Pipe<K, V>& p, rdst_key_kind kind) {
+    int cfg = g_tuning.pass_cfg;
+    if (cfg < 0 || cfg >= kNumPassCfgs) cfg = default_cfg(sizeof(K), p.n, kind != RDST_KEY_UNSIGNED);
+    p.rp = pick_routes<LEVELS>(p, cfg, false);
+    if (p.rp.L.tiles >= (1ull << 31)) return fail(RDST_ERR_ARG, "len too large for one launch");
+    int rc = ensure_workspace(*p.D, p.rp.L.total);
+    if (rc && (p.rp.try_atomic || p.rp.try_hybrid)) {  // no room for the areas and slots: the LSD route needs an eighth of the slice
+        p.rp = pick_routes<LEVELS>(p, cfg, true);
+        rc = ensure_workspace(*p.D, p.rp.L.total);
     }
-    return mapped ? launch_pass_t<K, unsigned long long, KPT, PAIR_WAVES, 1, true, false, V>(keys, tmp, n, level, L, ws, km, cus, s, vals, vtmp)
-                  : launch_pass_t<K, unsigned long long, KPT, PAIR_WAVES, 1, false, false, V>(keys, tmp, n, level, L, ws, km, cus, s, vals, vtmp);
+    if (rc) return rc;
+    p.w = WsView(static_cast<char*>(p.D->ws), p.rp.L);
+    return workspace_acquire(*p.D, p.s);
+}
+
+// clear: header, count tables and the status rows of the passes that can run
+template <int LEVELS, typename K, typename V>
+int clear_workspace(Pipe<K, V>& p) {
+    DeviceState& D = *p.D;
+    const Layout& L = p.w.L;
+    char* ws = p.w.ws;
+    hipStream_t s = p.s;
+    int rc;
+    if (g_tuning.profiling) D.prof_runs.push_back({D.prof_used, 0});
+    if ((rc = prof_mark(D, s))) return rc;
+    // hybrid-eligible sorts clear the rows of the two levels that route uses now and leave the others to a conditional
+    // kernel behind the route decision (1 B u32: 0.07 ms of clearing -> half)
+    const size_t level_rows = (size_t)L.status_bytes * L.tiles * RADIX;  // one level, one copy
+    if (p.rp.try_atomic) {
+        HIP_TRY(hipMemsetAsync(ws, 0, L.off_status, s));  // the status rows are the LSD route's: cleared behind the route decision, if it fell that way
+    } else if (p.rp.try_hybrid && LEVELS > 2) {
+        HIP_TRY(hipMemsetAsync(ws, 0, L.off_status, s));
+        HIP_TRY(hipMemsetAsync(ws + L.off_status + level_rows * (LEVELS - 2), 0, level_rows * 2, s));
+        HIP_TRY(hipMemsetAsync(ws + L.off_status_near + level_rows * (LEVELS - 2), 0, level_rows * 2, s));
+    } else if (p.level_lo == 0 && p.level_hi == (uint32_t)LEVELS) {
+        HIP_TRY(hipMemsetAsync(ws, 0, L.zero_bytes, s));  // header, count tables and both copies of the status rows are contiguous
+    } else {  // only the status rows of the passes that can run need clearing
+        const size_t status_lo = L.off_status + level_rows * p.level_lo, status_hi = L.off_status + level_rows * p.level_hi;
+        HIP_TRY(hipMemsetAsync(ws, 0, L.off_status, s));
+        if (status_hi > status_lo) {
+            HIP_TRY(hipMemsetAsync(ws + status_lo, 0, status_hi - status_lo, s));
+            HIP_TRY(hipMemsetAsync(ws + status_lo + (L.off_status_near - L.off_status), 0, status_hi - status_lo, s));
+        }
+    }
+    return prof_mark(D, s, RDST_STAGE_CLEAR);
+}
+
+// the status rows of the first `levels` levels, cleared on the device unless the plan says they are not needed
+template <typename K, typename V>
+int clear_unless_hybrid(const Pipe<K, V>& p, uint32_t levels, uint32_t unless_atomic) {
+    const uint64_t vecs = (uint64_t)p.w.L.status_bytes * p.w.L.tiles * RADIX * levels / 16;  // rows are multiples of 1 KiB
+    return launch("clear_unless_hybrid_kernel", clear_unless_hybrid_kernel, dim3((uint32_t)p.D->cus * 4), dim3(256), 0, p.s, p.w.plan,
+                  p.w.template status<uint4>(), vecs, p.w.template status_near<uint4>(), vecs, unless_atomic);
+}
+
+// K1's grid: one 128-KiB-LDS block per CU (more only on request), but no more than the data needs
+template <typename K>
+uint32_t hist_blocks(uint64_t n, int cus) {
+    uint64_t blocks = (uint64_t)(g_tuning.hist_bpc > 0 ? g_tuning.hist_bpc : 1) * cus;
+    const uint64_t per_block_min = (uint64_t)HIST_THREADS * (16 / sizeof(K)) * 4;
+    const uint64_t max_useful = (n + per_block_min - 1) / per_block_min;
+    if (blocks > max_useful) blocks = max_useful;
+    // Every block pays for zeroing and folding 128 KiB of LDS and for ~7 000 global adds on shared
+    // addresses (measured: ~8 us + 0.2 us per block), against ~20 GB/s of sweep per block: below a few
+    // hundred MB the best block count is about sqrt(bytes / 4 KiB), not one per CU.
+    uint64_t balanced = 1;
+    while (balanced * balanced * 4096 < n * sizeof(K)) ++balanced;
+    if (blocks > balanced) blocks = balanced;
+    return (uint32_t)(blocks < 1 ? 1 : blocks);
+}
+
+// K1h + the route decision, launched twice behind a tried atomic route: before the MSD passes (pre_launch: they run only if the
+// sample flagged the keys; the MSD passes then take their exact form for the hybrid route) and after them (what is left)
+template <int LEVELS, typename K, typename V>
+int count_and_route(const Pipe<K, V>& p, uint32_t pre_launch, bool sample_first) {
+    const WsView& w = p.w;
+    int rc;
+    if (sample_first)
+        if ((rc = launch_presample(p))) return rc;
+    if ((rc = launch_hist16(p, pre_launch))) return rc;
+    if (!pre_launch)
+        if ((rc = prof_mark(*p.D, p.s, RDST_STAGE_HIST16))) return rc;
+    RouteArgs ra{};
+    ra.h16 = w.h16;
+    ra.hpos16 = w.hpos16;
+    ra.overflow = w.h16_overflow;
+    ra.inversion = w.inversion;
+    ra.allow_skip = p.allow_skip ? 1u : 0u;
+    ra.bstart = w.bstart;
+    ra.hpos = w.hpos;
+    ra.hpair = w.hpair;
+    ra.plan = w.plan;
+    ra.n = p.n;
+    ra.levels = (uint32_t)LEVELS;
+    ra.cap = sizeof(K) == 4 && g_tuning.count_sort && g_tuning.expand ? EXPAND_MAX : (uint32_t)local_tile(sizeof(K));
+    ra.giant_max = p.rp.giants ? GIANT_MAX : 0u;
+    ra.glist = w.glist;
+    ra.gcount_item = w.gcount_item;
+    ra.gexp_item = w.gexp_item;
+    ra.pre_launch = pre_launch;
+    ra.msd_tile = (uint32_t)(MSD_WAVES * 64 * msd_kpt(sizeof(K)));
+    ra.cursor_a = w.cursor_a;
+    ra.cursor_b = w.cursor_b;
+    ra.xtile0 = w.xtile0;
+    ra.skip_a_ok = sizeof(K) == 4 ? 1u : 0u;
+    return launch("route_kernel", route_kernel, dim3(1), dim3(1024), 0, p.s, ra);
+}
+
+// The position ranges of the exact pass A (eight ranges tiled on their own, block b -> range b % 8: K1h's ranges) and the
+// tiles that takes
+template <typename K>
+uint32_t exact_ranges(const K* keys, uint64_t n, uint32_t blocks, uint64_t tile, MsdRanges* xr) {
+    const uint64_t xpiece = hist_piece(n, blocks, (uint64_t)HIST_THREADS * vec_for<K>(aligned16(keys)) * 4);  // as launch_hist16 picks K1h's loads
+    for (int r = 0; r <= CHAINS; ++r) {
+        const uint64_t at = (uint64_t)hist_first_block((uint32_t)r, blocks) * xpiece;
+        xr->start[r] = at < n ? at : n;
+    }
+    uint32_t tiles_x = 0;
+    for (int r = 0; r < CHAINS; ++r) {
+        const uint32_t t = (uint32_t)((xr->start[r + 1] - xr->start[r] + tile - 1) / tile);
+        if (t > tiles_x) tiles_x = t;
+    }
+    return tiles_x * CHAINS;
+}
+
+// ROUTE_ATOMIC: sample, (K1h + route ahead of the passes), pass A, pass B, the decision, and the LSD route's clear if no hybrid
+// route follows
+template <int LEVELS, typename K, typename V>
+int atomic_stage(const Pipe<K, V>& p) {
+    constexpr int KPT = msd_kpt(sizeof(K)), NW = MSD_WAVES, TILE = NW * 64 * KPT, W = (int)sizeof(K) * 8;
+    constexpr bool HALF = sizeof(K) == 4;  // 4-byte keys leave pass B as their low halves
+    constexpr size_t mlds = (size_t)NW * 1024 + 1024 + 128 + sizeof(K) * TILE;
+    const WsView& w = p.w;
+    const Layout& L = w.L;
+    DeviceState& D = *p.D;
+    hipStream_t s = p.s;
+    K* area_a = w.template area_a<K>();
+    uint16_t* slots16 = HALF ? w.slots16() : nullptr;
+    K* slots = HALF ? nullptr : w.template slots<K>();
+    int rc;
+    if ((rc = launch_presample(p))) return rc;
+    if (p.rp.try_hybrid && g_tuning.exact_msd)
+        if ((rc = count_and_route<LEVELS>(p, 1u, false))) return rc;
+    if ((rc = prof_mark(D, s, RDST_STAGE_SAMPLE))) return rc;
+    MsdRanges xr{};
+    const uint32_t tiles_x = exact_ranges(p.keys, p.n, p.blocks, TILE, &xr);
+    const uint32_t tiles_a = (uint32_t)((p.n + TILE - 1) / TILE);
+    const uint32_t tpa = (L.msd_cap_a + TILE - 1) / TILE;
+    // pass A: the slice, by its top byte, into 256 x 8 areas
+    const uint32_t grid_a = tiles_a > tiles_x ? tiles_a : tiles_x;
+    rc = with_bools([&](auto MAPPED) {
+        return launch("msd_scatter_kernel (pass A)", msd_scatter_kernel<K, KPT, NW, MAPPED, false, false>, dim3(grid_a), dim3(NW * 64), mlds, s, p.keys,
+                      nullptr, p.n, 0u, grid_a, area_a, nullptr, w.cursor_a, L.msd_cap_a, W - 8, L.msd_slices, w.plan, w.msd_overflow, w.inversion,
+                      (K)p.km.neg, (K)p.km.pos, p.tmp, p.keys, w.bstart, w.xtile0, xr);
+    }, p.mapped);
+    if (rc) return rc;
+    if ((rc = prof_mark(D, s, RDST_STAGE_MSD_A))) return rc;
+    // pass B: every area, by the second byte, into the slot of its bucket
+    uint32_t grid_b = (uint32_t)RADIX * L.msd_slices * tpa;
+    if (grid_b < tiles_a + RADIX) grid_b = tiles_a + RADIX;  // (the exact form: every top digit's region ends on a partial tile)
+    rc = with_bools([&](auto MAPPED) {
+        return launch("msd_scatter_kernel (pass B)", msd_scatter_kernel<K, KPT, NW, MAPPED, true, HALF>, dim3(grid_b), dim3(NW * 64), mlds, s, area_a,
+                      w.cursor_a, 0ull, L.msd_cap_a, tpa, slots, slots16, w.cursor_b, L.slot_cap, W - 16, L.msd_slices, w.plan, w.msd_overflow,
+                      w.inversion, (K)p.km.neg, (K)p.km.pos, p.tmp, p.keys, w.bstart, w.xtile0, xr);
+    }, p.mapped);
+    if (rc) return rc;
+    if ((rc = prof_mark(D, s, RDST_STAGE_MSD_B))) return rc;
+    MsdFinishArgs fa{};
+    fa.cursor_b = w.cursor_b;
+    fa.overflow = w.msd_overflow;
+    fa.inversion = w.inversion;
+    fa.bstart = w.bstart;
+    fa.plan = w.plan;
+    fa.n = p.n;
+    fa.allow_skip = p.allow_skip ? 1u : 0u;
+    if ((rc = launch("msd_finish_kernel", msd_finish_kernel, dim3(1), dim3(1024), 0, s, fa))) return rc;
+    if ((rc = prof_mark(D, s, RDST_STAGE_ROUTE))) return rc;
+    if (!p.rp.try_hybrid) return clear_unless_hybrid(p, LEVELS, 0u);  // the LSD route's status rows, if the route fell that way
+    return RDST_OK;
+}
+
+// the hybrid route's count and decision, then the status rows the up-front clear left to it
+template <int LEVELS, typename K, typename V>
+int hybrid_stage(const Pipe<K, V>& p) {
+    int rc;
+    if ((rc = count_and_route<LEVELS>(p, 0u, !p.rp.try_atomic))) return rc;
+    if (p.rp.try_atomic) rc = clear_unless_hybrid(p, LEVELS, 1u);  // nothing was cleared up front: every level's rows, unless the atomic route took the sort
+    else if (LEVELS > 2) rc = clear_unless_hybrid(p, LEVELS - 2, 0u);
+    if (rc) return rc;
+    return prof_mark(*p.D, p.s, RDST_STAGE_ROUTE);
+}
+
+// K1 + K2: the per-level counts and everything the passes derive from them
+template <int LEVELS, typename K, typename V>
+int count_and_scan(const Pipe<K, V>& p) {
+    const WsView& w = p.w;
+    const bool routed = p.rp.try_hybrid || p.rp.try_atomic;
+    uint64_t piece = 0;
+    int rc;
+    // a single pass (the parity hook, the sharded route's split) counts its own level only: one LDS atomic per key
+    if (LEVELS > 1 && p.level_hi == p.level_lo + 1) rc = launch_hist<1>(p, false, nullptr, &piece, (int)p.level_lo);
+    else rc = launch_hist<LEVELS>(p, p.pair, routed ? w.plan : nullptr, &piece);
+    if (rc) return rc;
+    if ((rc = prof_mark(*p.D, p.s, RDST_STAGE_HIST))) return rc;
+    ScanArgs sa{};
+    sa.hpos = w.hpos;
+    sa.hpair = p.pair ? w.hpair : nullptr;
+    sa.hist = w.hist;
+    sa.base = w.base;
+    sa.cbase = w.cbase();
+    sa.chains = w.chains();
+    sa.plan = w.plan;
+    sa.tickets = w.tickets();
+    sa.inversion = w.inversion;
+    sa.n = p.n;
+    sa.hist_piece = piece;
+    sa.levels = (uint32_t)LEVELS;
+    sa.allow_skip = p.allow_skip ? 1u : 0u;
+    sa.level_lo = p.level_lo;
+    sa.level_hi = p.level_hi;
+    sa.hist_grid = p.blocks;
+    sa.tile = w.L.tile;
+    sa.use_chains = g_tuning.chains ? 1u : 0u;
+    sa.halves = p.rp.halves ? 1u : 0u;
+    sa.deliver_tmp = p.deliver_tmp ? 1u : 0u;
+    if ((rc = launch("scan_kernel", scan_kernel, dim3(1), dim3(256 * SCAN_GROUPS), 0, p.s, sa))) return rc;
+    return prof_mark(*p.D, p.s, RDST_STAGE_SCAN);
+}
+
+template <int LEVELS, typename K, typename V>
+int pass_loop(const Pipe<K, V>& p) {
+    for (uint32_t level = p.level_lo; level < p.level_hi; ++level) {
+        int rc;
+        if constexpr (ValBytes<V>::value != 0) rc = launch_pass_pairs(p, (int)level);
+        else rc = launch_pass(p, (int)level, p.rp.halves && level + 1 == (uint32_t)LEVELS ? p.w.halves16() : nullptr, p.rp.try_atomic && g_tuning.persist_fallback);
+        if (rc) return rc;
+        if ((rc = prof_mark(*p.D, p.s, RDST_STAGE_PASS | (level << 8)))) return rc;
+    }
+    return RDST_OK;
+}
+
+template <typename T>
+int launch_copyback(T* dst, const T* src, uint64_t n, const Plan* plan, uint32_t deliver_tmp, int cus, hipStream_t s) {
+    uint64_t blocks = (n * sizeof(T) / 16 + 255) / 256;
+    if (blocks > (uint64_t)cus * 16) blocks = (uint64_t)cus * 16;
+    if (blocks < 1) blocks = 1;
+    return with_bools([&](auto ALIGNED) {
+        return launch("copyback_kernel", copyback_kernel<T, vec_for<T>(ALIGNED)>, dim3((uint32_t)blocks), dim3(256), 0, s, dst, src, n, plan, deliver_tmp);
+    }, aligned16(dst, src));
+}
+
+template <typename K, typename V>
+int copy_back_stage(const Pipe<K, V>& p) {
+    int rc = p.deliver_tmp ? launch_copyback<K>(p.tmp, p.keys, p.n, p.w.plan, 1u, p.D->cus, p.s)
+                           : launch_copyback<K>(p.keys, p.tmp, p.n, p.w.plan, 0u, p.D->cus, p.s);
+    if (rc) return rc;
+    if constexpr (ValBytes<V>::value != 0) {
+        if ((rc = launch_copyback<V>(p.vals, p.vtmp, p.n, p.w.plan, 0u, p.D->cus, p.s))) return rc;
+    }
+    return prof_mark(*p.D, p.s, RDST_STAGE_COPYBACK);
 }
 
 // The whole device-side pipeline for levels [level_lo, level_hi): memset, K1, K2, passes,
@@ -4980,337 +5290,39 @@ int run_pipeline(K* keys, K* tmp, uint64_t n, rdst_key_kind kind, uint32_t level
                  bool allow_skip, bool copy_back, hipStream_t s, Layout* layout_out, char** ws_out, V* vals = nullptr,
                  V* vtmp = nullptr, bool deliver_tmp = false /* whole key-only sorts: leave the result in tmp, not in keys */) {
     constexpr bool HAS_V = ValBytes<V>::value != 0;
+    constexpr bool ROUTED = !HAS_V && (sizeof(K) == 4 || sizeof(K) == 8);  // the widths the atomic and the hybrid route are built for
     if (deliver_tmp && (HAS_V || !copy_back)) return fail(RDST_ERR_ARG, "deliver_tmp: whole key-only sorts");
     DeviceState* D;
     int rc = current_device_state(&D);
     if (rc) return rc;
     if constexpr (!HAS_V) {
-        // a slice of at most one small tile: the one-workgroup sort, in place, no workspace
         if (g_tuning.small_sort && level_lo == 0 && level_hi == (uint32_t)LEVELS && allow_skip && copy_back && !layout_out && !deliver_tmp &&
-            n <= (uint64_t)SMALL_THREADS * small_kpt(sizeof(K))) {
-            const KeyMap km = key_map_for(kind, sizeof(K));
-            const size_t lds = (size_t)SMALL_WAVES * 1024 + 16 + sizeof(K) * SMALL_THREADS * small_kpt(sizeof(K));
-            const bool mapped = km.neg != 0 || km.pos != 0;
-            const void* fn = mapped ? reinterpret_cast<const void*>(&small_sort_kernel<K, LEVELS, true>)
-                                    : reinterpret_cast<const void*>(&small_sort_kernel<K, LEVELS, false>);
-            if ((rc = ensure_lds_attr(fn, lds))) return rc;
-            if (mapped) hipLaunchKernelGGL((small_sort_kernel<K, LEVELS, true>), dim3(1), dim3(SMALL_THREADS), lds, s, keys, (uint32_t)n, (K)km.neg, (K)km.pos);
-            else hipLaunchKernelGGL((small_sort_kernel<K, LEVELS, false>), dim3(1), dim3(SMALL_THREADS), lds, s, keys, (uint32_t)n, (K)km.neg, (K)km.pos);
-            HIP_TRY(hipGetLastError());
-            D->last_plan_valid = false;
-            return RDST_OK;
-        }
+            n <= (uint64_t)SMALL_THREADS * small_kpt(sizeof(K)))
+            return run_small_sort<K, LEVELS>(*D, keys, n, kind, s);
     }
-    int cfg = g_tuning.pass_cfg;
-    if (cfg < 0 || cfg >= kNumPassCfgs) cfg = default_cfg(sizeof(K), n, kind != RDST_KEY_UNSIGNED);
-    // Hybrid route (whole sorts of 4- and 8-byte keys, long enough that a bucket is worth a workgroup, short
-    // enough that 65 536 tiles can hold it): K1h counts the buckets, route_kernel decides.  If it says LSD,
-    // K1 runs as ever (the slice is then read twice for counting); if it says hybrid, K1 returns at once.
-    const bool whole_sort = !HAS_V && level_lo == 0 && level_hi == (uint32_t)LEVELS && allow_skip && copy_back;
-    // which routes this sort may take, and the workspace that needs.  `lean`: the LSD route only (0.13 x the slice instead of
-    // 1.7 x) — what is left when the device cannot spare the space of the byte-saving routes.
-    struct RoutePick { bool try_atomic, try_hybrid, halves, giants; int cfg; Layout L; };
-    const int cfg0 = cfg;
-    auto pick_routes = [&](bool lean) -> RoutePick {
-        RoutePick r{};
-        r.cfg = cfg0;
-        r.try_atomic = !lean && whole_sort && atomic_eligible(n, sizeof(K), r.cfg);
-        // 8-byte keys: the fallback's passes run as persistent blocks of shape 5 (eight skipped passes of one block per tile cost 0.5 ms per 10^9 keys)
-        if (r.try_atomic && sizeof(K) == 8 && g_tuning.persist_fallback && g_tuning.pass_cfg < 0) r.cfg = 5;
-        // Behind a failed atomic route (an area or a slot overflowed) the hybrid route is tried next — exact counts, any bucket
-        // the local sort takes — and the LSD route last.  One launch sequence serves all three: every kernel looks at the plan.
-        const bool halves_cfg = g_tuning.halves && g_tuning.count_sort && halves_possible<K>(r.cfg, n);
-        r.try_hybrid = !lean && whole_sort && hybrid_eligible(n, sizeof(K)) && (!r.try_atomic || (g_tuning.chain_routes && (sizeof(K) == 8 || halves_cfg)));
-        r.halves = r.try_hybrid && halves_cfg;
-        // 4-byte keys: the hybrid route takes buckets of any size (K1h counts them exactly, the giant kernels of K4 sort them)
-        r.giants = r.try_hybrid && sizeof(K) == 4 && g_tuning.giants && g_tuning.count_sort && g_tuning.expand && n < (1ull << 30);
-        r.L = make_layout(n, sizeof(K), LEVELS, r.cfg, HAS_V ? PAIR_WAVES * 64 * pair_kpt(sizeof(K), ValBytes<V>::value) : 0, r.halves, r.try_atomic, r.giants);
-        return r;
-    };
-    RoutePick rp = pick_routes(false);
-    if (rp.L.tiles >= (1ull << 31)) return fail(RDST_ERR_ARG, "len too large for one launch");
-    rc = ensure_workspace(*D, rp.L.total);
-    if (rc && (rp.try_atomic || rp.try_hybrid)) {  // no room for the areas and slots: the LSD route needs an eighth of the slice
-        rp = pick_routes(true);
-        rc = ensure_workspace(*D, rp.L.total);
-    }
-    if (rc) return rc;
-    const bool try_atomic = rp.try_atomic, try_hybrid = rp.try_hybrid, halves = rp.halves, giants = rp.giants;
-    cfg = rp.cfg;
-    const Layout L = rp.L;
-    char* ws = static_cast<char*>(D->ws);
     const KeyMap km = key_map_for(kind, sizeof(K));
-    rc = workspace_acquire(*D, s);
-    if (rc) return rc;
-
-    // only the status rows of the passes that can run need clearing
-    const size_t status_lo = L.off_status + (size_t)L.status_bytes * level_lo * L.tiles * RADIX;
-    const size_t status_hi = L.off_status + (size_t)L.status_bytes * level_hi * L.tiles * RADIX;
-    if (g_tuning.profiling) D->prof_runs.push_back({D->prof_used, 0});
-    if ((rc = prof_mark(*D, s))) return rc;
-    // hybrid-eligible sorts clear the rows of the two levels that route uses now and leave the others to a conditional
-    // kernel behind the route decision (1 B u32: 0.07 ms of clearing -> half)
-    const size_t level_rows = (size_t)L.status_bytes * L.tiles * RADIX;  // one level, one copy
-    const bool split_clear = try_hybrid && !try_atomic && LEVELS > 2;
-    if (try_atomic) {
-        HIP_TRY(hipMemsetAsync(ws, 0, L.off_status, s));  // the status rows are the LSD route's: cleared behind the route decision, if it fell that way
-    } else if (split_clear) {
-        HIP_TRY(hipMemsetAsync(ws, 0, L.off_status, s));
-        HIP_TRY(hipMemsetAsync(ws + L.off_status + level_rows * (LEVELS - 2), 0, level_rows * 2, s));
-        HIP_TRY(hipMemsetAsync(ws + L.off_status_near + level_rows * (LEVELS - 2), 0, level_rows * 2, s));
-    } else if (level_lo == 0 && level_hi == (uint32_t)LEVELS) {
-        HIP_TRY(hipMemsetAsync(ws, 0, L.zero_bytes, s));  // header, count tables and both copies of the status rows are contiguous
-    } else {
-        HIP_TRY(hipMemsetAsync(ws, 0, L.off_status, s));
-        if (status_hi > status_lo) {
-            HIP_TRY(hipMemsetAsync(ws + status_lo, 0, status_hi - status_lo, s));
-            HIP_TRY(hipMemsetAsync(ws + status_lo + (L.off_status_near - L.off_status), 0, status_hi - status_lo, s));
-        }
+    Pipe<K, V> p{D, s, keys, tmp, vals, vtmp, n, level_lo, level_hi, allow_skip, copy_back, deliver_tmp, km, km.neg != 0 || km.pos != 0};
+    if ((rc = pick_workspace<LEVELS>(p, kind))) return rc;
+    if ((rc = clear_workspace<LEVELS>(p))) return rc;
+    p.blocks = hist_blocks<K>(n, D->cus);
+    p.pair = g_tuning.chains && LEVELS >= 2 && level_hi > level_lo + 1;  // the joint tables pay off only when a second pass can follow a first
+    if constexpr (ROUTED) {
+        if (p.rp.try_atomic && (rc = atomic_stage<LEVELS>(p))) return rc;
+        if (p.rp.try_hybrid && (rc = hybrid_stage<LEVELS>(p))) return rc;
     }
-    if ((rc = prof_mark(*D, s, RDST_STAGE_CLEAR))) return rc;
-
-    // K1: one 128-KiB-LDS block per CU (more only on request), but no more than the data needs
-    uint64_t blocks = (uint64_t)(g_tuning.hist_bpc > 0 ? g_tuning.hist_bpc : 1) * D->cus;
-    const uint64_t per_block_min = (uint64_t)HIST_THREADS * (16 / sizeof(K)) * 4;
-    const uint64_t max_useful = (n + per_block_min - 1) / per_block_min;
-    if (blocks > max_useful) blocks = max_useful;
-    // Every block pays for zeroing and folding 128 KiB of LDS and for ~7 000 global adds on shared
-    // addresses (measured: ~8 us + 0.2 us per block), against ~20 GB/s of sweep per block: below a few
-    // hundred MB the best block count is about sqrt(bytes / 4 KiB), not one per CU.
-    uint64_t balanced = 1;
-    while (balanced * balanced * 4096 < n * sizeof(K)) ++balanced;
-    if (blocks > balanced) blocks = balanced;
-    if (blocks < 1) blocks = 1;
-    unsigned long long* hpos = reinterpret_cast<unsigned long long*>(ws + L.off_hpos);
-    uint32_t* inversion = reinterpret_cast<uint32_t*>(ws + L.off_err) + 1;  // second word of the (cleared) header
-    uint64_t piece = 0;
-    // the joint tables pay off only when a second pass can follow a first
-    const bool pair = g_tuning.chains && LEVELS >= 2 && level_hi > level_lo + 1;
-    unsigned long long* hpair = reinterpret_cast<unsigned long long*>(ws + L.off_hpair);
-    Plan* plan = reinterpret_cast<Plan*>(ws + L.off_plan);
-    // K1h + the route decision, launched twice behind a tried atomic route: before the MSD passes (they run only if the sample
-    // flagged the keys; the MSD passes then take their exact form for the hybrid route) and after them (what is left)
-    auto count_and_route = [&](uint32_t pre_launch, bool sample_first, hipStream_t cs) -> int {
-      if constexpr (!HAS_V && (sizeof(K) == 4 || sizeof(K) == 8)) {
-        uint32_t* overflow16 = reinterpret_cast<uint32_t*>(ws + L.off_err) + 2;
-        uint32_t* h16 = reinterpret_cast<uint32_t*>(ws + L.off_h16);
-        unsigned long long* hpos16 = reinterpret_cast<unsigned long long*>(ws + L.off_hpos16);
-        if (int r = launch_hist16<K>(keys, n, (uint32_t)blocks, km, h16, hpos16, inversion, overflow16, plan, cs, sample_first, giants, pre_launch)) return r;
-        if (!pre_launch)
-            if (int r = prof_mark(*D, cs, RDST_STAGE_HIST16)) return r;
-        RouteArgs ra{};
-        ra.h16 = h16;
-        ra.hpos16 = hpos16;
-        ra.overflow = overflow16;
-        ra.inversion = inversion;
-        ra.allow_skip = allow_skip ? 1u : 0u;
-        ra.bstart = reinterpret_cast<uint32_t*>(ws + L.off_bstart);
-        ra.hpos = hpos;
-        ra.hpair = hpair;
-        ra.plan = plan;
-        ra.n = n;
-        ra.levels = (uint32_t)LEVELS;
-        ra.cap = sizeof(K) == 4 && g_tuning.count_sort && g_tuning.expand ? EXPAND_MAX : (uint32_t)local_tile(sizeof(K));
-        ra.giant_max = giants ? GIANT_MAX : 0u;
-        ra.glist = reinterpret_cast<uint32_t*>(ws + L.off_glist);
-        ra.gcount_item = ra.glist + GIANT_MAX + 16;
-        ra.gexp_item = ra.gcount_item + GIANT_MAX + 16;
-        ra.pre_launch = pre_launch;
-        ra.msd_tile = (uint32_t)(MSD_WAVES * 64 * msd_kpt(sizeof(K)));
-        ra.cursor_a = reinterpret_cast<uint32_t*>(ws + L.off_cursor_a);
-        ra.cursor_b = reinterpret_cast<uint32_t*>(ws + L.off_cursor_b);
-        ra.xtile0 = reinterpret_cast<uint32_t*>(ws + L.off_xtile0);
-        ra.skip_a_ok = sizeof(K) == 4 ? 1u : 0u;
-        hipLaunchKernelGGL(route_kernel, dim3(1), dim3(1024), 0, cs, ra);
-        HIP_TRY(hipGetLastError());
-      }
-        return RDST_OK;
-    };
-    if constexpr (!HAS_V && (sizeof(K) == 4 || sizeof(K) == 8)) {
-        if (try_atomic) {
-            constexpr int KPT = msd_kpt(sizeof(K)), NW = MSD_WAVES, TILE = NW * 64 * KPT, W = (int)sizeof(K) * 8;
-            constexpr bool HALF = sizeof(K) == 4;  // 4-byte keys leave pass B as their low halves
-            constexpr size_t mlds = (size_t)NW * 1024 + 1024 + 128 + sizeof(K) * TILE;
-            const uint32_t slot_cap = L.slot_cap;
-            uint32_t* overflow = reinterpret_cast<uint32_t*>(ws + L.off_err) + 4;
-            uint32_t* cursor_a = reinterpret_cast<uint32_t*>(ws + L.off_cursor_a);
-            uint32_t* cursor_b = reinterpret_cast<uint32_t*>(ws + L.off_cursor_b);
-            K* area_a = reinterpret_cast<K*>(ws + L.off_msd_a);
-            uint16_t* slots16 = HALF ? reinterpret_cast<uint16_t*>(ws + L.off_halves) : nullptr;
-            K* slots = HALF ? nullptr : reinterpret_cast<K*>(ws + L.off_halves);
-            const bool mapped = km.neg != 0 || km.pos != 0;
-            if ((rc = launch_presample<K>(keys, n, km, plan, s))) return rc;
-            if constexpr (sizeof(K) == 4 || sizeof(K) == 8) {
-                if (try_hybrid && g_tuning.exact_msd)
-                    if ((rc = count_and_route(1u, false, s))) return rc;
-            }
-            if ((rc = prof_mark(*D, s, RDST_STAGE_SAMPLE))) return rc;
-            MsdRanges xr{};
-            uint32_t tiles_x = 0;  // exact pass A: eight ranges tiled on their own, block b -> range b % 8
-            {
-                const uint64_t xvec = (reinterpret_cast<uintptr_t>(keys) & 15u) == 0 ? 16 / sizeof(K) : 1;  // as launch_hist16 picks K1h's loads
-                const uint64_t xpiece = hist_piece(n, (uint32_t)blocks, (uint64_t)HIST_THREADS * xvec * 4);
-                for (int r = 0; r <= CHAINS; ++r) {
-                    const uint64_t at = (uint64_t)hist_first_block((uint32_t)r, (uint32_t)blocks) * xpiece;
-                    xr.start[r] = at < n ? at : n;
-                }
-                for (int r = 0; r < CHAINS; ++r) {
-                    const uint32_t t = (uint32_t)((xr.start[r + 1] - xr.start[r] + TILE - 1) / TILE);
-                    if (t > tiles_x) tiles_x = t;
-                }
-                tiles_x *= CHAINS;
-            }
-            const uint32_t* bstart_x = reinterpret_cast<const uint32_t*>(ws + L.off_bstart);
-            const uint32_t* xtile0 = reinterpret_cast<const uint32_t*>(ws + L.off_xtile0);
-            const uint32_t tiles_a = (uint32_t)((n + TILE - 1) / TILE);
-            const uint32_t tpa = (L.msd_cap_a + TILE - 1) / TILE;
-#define RDST_MSD(MAPPED, SECOND, GRID, ...)                                                                                              \
-    do {                                                                                                                                 \
-        if ((rc = ensure_lds_attr(reinterpret_cast<const void*>(&msd_scatter_kernel<K, KPT, NW, MAPPED, SECOND, (SECOND && HALF)>), mlds))) return rc; \
-        hipLaunchKernelGGL((msd_scatter_kernel<K, KPT, NW, MAPPED, SECOND, (SECOND && HALF)>), dim3(GRID), dim3(NW * 64), mlds, s, __VA_ARGS__); \
-    } while (0)
-            // pass A: the slice, by its top byte, into 256 x 8 areas
-            const uint32_t grid_a = tiles_a > tiles_x ? tiles_a : tiles_x;
-            if (mapped) RDST_MSD(true, false, grid_a, keys, nullptr, n, 0u, grid_a, area_a, nullptr, cursor_a, L.msd_cap_a, W - 8, L.msd_slices, plan, overflow, inversion, (K)km.neg, (K)km.pos, tmp, keys, bstart_x, xtile0, xr);
-            else RDST_MSD(false, false, grid_a, keys, nullptr, n, 0u, grid_a, area_a, nullptr, cursor_a, L.msd_cap_a, W - 8, L.msd_slices, plan, overflow, inversion, (K)km.neg, (K)km.pos, tmp, keys, bstart_x, xtile0, xr);
-            HIP_TRY(hipGetLastError());
-            if ((rc = prof_mark(*D, s, RDST_STAGE_MSD_A))) return rc;
-            // pass B: every area, by the second byte, into the slot of its bucket
-            uint32_t grid_b = (uint32_t)RADIX * L.msd_slices * tpa;
-            if (grid_b < tiles_a + RADIX) grid_b = tiles_a + RADIX;  // (the exact form: every top digit's region ends on a partial tile)
-            if (mapped) RDST_MSD(true, true, grid_b, area_a, cursor_a, 0ull, L.msd_cap_a, tpa, slots, slots16, cursor_b, slot_cap, W - 16, L.msd_slices, plan, overflow, inversion, (K)km.neg, (K)km.pos, tmp, keys, bstart_x, xtile0, xr);
-            else RDST_MSD(false, true, grid_b, area_a, cursor_a, 0ull, L.msd_cap_a, tpa, slots, slots16, cursor_b, slot_cap, W - 16, L.msd_slices, plan, overflow, inversion, (K)km.neg, (K)km.pos, tmp, keys, bstart_x, xtile0, xr);
-#undef RDST_MSD
-            HIP_TRY(hipGetLastError());
-            if ((rc = prof_mark(*D, s, RDST_STAGE_MSD_B))) return rc;
-            MsdFinishArgs fa{};
-            fa.cursor_b = cursor_b;
-            fa.overflow = overflow;
-            fa.inversion = inversion;
-            fa.bstart = reinterpret_cast<uint32_t*>(ws + L.off_bstart);
-            fa.plan = plan;
-            fa.n = n;
-            fa.allow_skip = allow_skip ? 1u : 0u;
-            hipLaunchKernelGGL(msd_finish_kernel, dim3(1), dim3(1024), 0, s, fa);
-            HIP_TRY(hipGetLastError());
-            if ((rc = prof_mark(*D, s, RDST_STAGE_ROUTE))) return rc;
-            if (!try_hybrid) {  // the LSD route's status rows, if the route fell that way
-                const uint64_t vecs = level_rows * LEVELS / 16;
-                hipLaunchKernelGGL(clear_unless_hybrid_kernel, dim3((uint32_t)D->cus * 4), dim3(256), 0, s, plan, reinterpret_cast<uint4*>(ws + L.off_status),
-                                   vecs, reinterpret_cast<uint4*>(ws + L.off_status_near), vecs, 0u);
-                HIP_TRY(hipGetLastError());
-            }
-        }
-    }
-    if constexpr (!HAS_V && (sizeof(K) == 4 || sizeof(K) == 8)) {
-        if (try_hybrid) {
-            if ((rc = count_and_route(0u, !try_atomic, s))) return rc;
-            if (split_clear) {
-                const uint64_t vecs = level_rows * (LEVELS - 2) / 16;  // rows are multiples of 1 KiB
-                hipLaunchKernelGGL(clear_unless_hybrid_kernel, dim3((uint32_t)D->cus * 4), dim3(256), 0, s, plan,
-                                   reinterpret_cast<uint4*>(ws + L.off_status), vecs, reinterpret_cast<uint4*>(ws + L.off_status_near), vecs, 0u);
-                HIP_TRY(hipGetLastError());
-            } else if (try_atomic) {  // nothing was cleared up front: every level's rows, unless the atomic route took the sort
-                const uint64_t vecs = level_rows * LEVELS / 16;
-                hipLaunchKernelGGL(clear_unless_hybrid_kernel, dim3((uint32_t)D->cus * 4), dim3(256), 0, s, plan,
-                                   reinterpret_cast<uint4*>(ws + L.off_status), vecs, reinterpret_cast<uint4*>(ws + L.off_status_near), vecs, 1u);
-                HIP_TRY(hipGetLastError());
-            }
-            if ((rc = prof_mark(*D, s, RDST_STAGE_ROUTE))) return rc;
-        }
-    }
-    // a single pass (the parity hook, the sharded route's split) counts its own level only: one LDS atomic per key
-    if (LEVELS > 1 && level_hi == level_lo + 1) rc = launch_hist<K, 1>(keys, n, (uint32_t)blocks, km, hpos, hpair, false, inversion, nullptr, s, &piece, (int)level_lo);
-    else rc = launch_hist<K, LEVELS>(keys, n, (uint32_t)blocks, km, hpos, hpair, pair, inversion, (try_hybrid || try_atomic) ? plan : nullptr, s, &piece);
-    if (rc) return rc;
-    if ((rc = prof_mark(*D, s, RDST_STAGE_HIST))) return rc;
-    ScanArgs sa{};
-    sa.hpos = hpos;
-    sa.hpair = pair ? hpair : nullptr;
-    sa.hist = reinterpret_cast<unsigned long long*>(ws + L.off_hist);
-    sa.base = reinterpret_cast<uint64_t*>(ws + L.off_base);
-    sa.cbase = reinterpret_cast<uint64_t*>(ws + L.off_cbase);
-    sa.chains = reinterpret_cast<LevelChains*>(ws + L.off_chains);
-    sa.plan = plan;
-    sa.tickets = reinterpret_cast<uint32_t*>(ws + L.off_tickets);
-    sa.inversion = inversion;
-    sa.n = n;
-    sa.hist_piece = piece;
-    sa.levels = (uint32_t)LEVELS;
-    sa.allow_skip = allow_skip ? 1u : 0u;
-    sa.level_lo = level_lo;
-    sa.level_hi = level_hi;
-    sa.hist_grid = (uint32_t)blocks;
-    sa.tile = L.tile;
-    sa.use_chains = g_tuning.chains ? 1u : 0u;
-    sa.halves = halves ? 1u : 0u;
-    sa.deliver_tmp = deliver_tmp ? 1u : 0u;
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(256 * SCAN_GROUPS), 0, s, sa);
-    HIP_TRY(hipGetLastError());
-    if ((rc = prof_mark(*D, s, RDST_STAGE_SCAN))) return rc;
-    for (uint32_t level = level_lo; level < level_hi; ++level) {
-        if constexpr (HAS_V) rc = launch_pass_pairs<K, V>(keys, tmp, vals, vtmp, n, (int)level, L, ws, km, D->cus, s);
-        else rc = launch_pass<K>(cfg, keys, tmp, n, (int)level, L, ws, km, D->cus, s,
-                                 halves && level + 1 == (uint32_t)LEVELS ? reinterpret_cast<uint16_t*>(ws + L.off_halves) : nullptr,
-                                 try_atomic && g_tuning.persist_fallback);
-        if (rc) return rc;
-        if ((rc = prof_mark(*D, s, RDST_STAGE_PASS | (level << 8)))) return rc;
-    }
-    if constexpr (!HAS_V && (sizeof(K) == 4 || sizeof(K) == 8)) {
-        if (try_hybrid || try_atomic) {
-            // one K4 for both routes: the atomic route's buckets lie in the slots, the hybrid route's at their final place
-            // (4-byte keys: as low halves, in the same region of the workspace either way)
-            const bool from16 = sizeof(K) == 4 && (try_atomic || halves);
-            GiantArgs ga{};
-            ga.glist = reinterpret_cast<uint32_t*>(ws + L.off_glist);
-            ga.gcount_item = ga.glist + GIANT_MAX + 16;
-            ga.gexp_item = ga.gcount_item + GIANT_MAX + 16;
-            ga.tables = reinterpret_cast<uint32_t*>(ws + L.off_gtables);
-            ga.recs = reinterpret_cast<GiantItem*>(ws + L.off_gsplit);
-            rc = launch_local_sort<K>(keys, tmp, reinterpret_cast<const uint32_t*>(ws + L.off_bstart), plan, D->err_dev, km,
-                                      reinterpret_cast<uint32_t*>(ws + L.off_fblist), reinterpret_cast<uint32_t*>(ws + L.off_err) + 3,
-                                      from16 ? reinterpret_cast<const uint16_t*>(ws + L.off_halves) : nullptr, D->cus, s,
-                                      try_atomic ? reinterpret_cast<const uint32_t*>(ws + L.off_cursor_b) : nullptr, L.slot_cap,
-                                      try_atomic && sizeof(K) == 8 ? reinterpret_cast<const K*>(ws + L.off_halves) : nullptr,
-                                      reinterpret_cast<uint32_t*>(ws + L.off_fblist2), reinterpret_cast<uint32_t*>(ws + L.off_err) + 5,
-                                      giants ? &ga : nullptr);
-            if (rc) return rc;
+    if ((rc = count_and_scan<LEVELS>(p))) return rc;
+    if ((rc = pass_loop<LEVELS>(p))) return rc;
+    if constexpr (ROUTED) {
+        if (p.rp.try_hybrid || p.rp.try_atomic) {
+            if ((rc = launch_local_sort(p))) return rc;
             if ((rc = prof_mark(*D, s, RDST_STAGE_LOCAL))) return rc;
         }
     }
-    if (copy_back) {
-        const bool aligned = ((reinterpret_cast<uintptr_t>(keys) | reinterpret_cast<uintptr_t>(tmp)) & 15u) == 0;
-        uint64_t cblocks = (n * sizeof(K) / 16 + 255) / 256;
-        const uint64_t cap = (uint64_t)D->cus * 16;
-        if (cblocks > cap) cblocks = cap;
-        if (cblocks < 1) cblocks = 1;
-        const Plan* plan = reinterpret_cast<const Plan*>(ws + L.off_plan);
-        constexpr int VEC = 16 / sizeof(K);
-        K* cdst = deliver_tmp ? tmp : keys;
-        const K* csrc = deliver_tmp ? keys : tmp;
-        if (aligned)
-            hipLaunchKernelGGL((copyback_kernel<K, VEC>), dim3((uint32_t)cblocks), dim3(256), 0, s, cdst, csrc, n, plan, deliver_tmp ? 1u : 0u);
-        else
-            hipLaunchKernelGGL((copyback_kernel<K, 1>), dim3((uint32_t)cblocks), dim3(256), 0, s, cdst, csrc, n, plan, deliver_tmp ? 1u : 0u);
-        HIP_TRY(hipGetLastError());
-        if constexpr (HAS_V) {
-            const bool valigned = ((reinterpret_cast<uintptr_t>(vals) | reinterpret_cast<uintptr_t>(vtmp)) & 15u) == 0;
-            uint64_t vblocks = (n * sizeof(V) / 16 + 255) / 256;
-            if (vblocks > cap) vblocks = cap;
-            if (vblocks < 1) vblocks = 1;
-            constexpr int VVEC = 16 / sizeof(V);
-            if (valigned)
-                hipLaunchKernelGGL((copyback_kernel<V, VVEC>), dim3((uint32_t)vblocks), dim3(256), 0, s, vals, vtmp, n, plan, 0u);
-            else
-                hipLaunchKernelGGL((copyback_kernel<V, 1>), dim3((uint32_t)vblocks), dim3(256), 0, s, vals, vtmp, n, plan, 0u);
-            HIP_TRY(hipGetLastError());
-        }
-        if ((rc = prof_mark(*D, s, RDST_STAGE_COPYBACK))) return rc;
-    }
-    if (layout_out) *layout_out = L;
-    if (ws_out) *ws_out = ws;
+    if (copy_back && (rc = copy_back_stage(p))) return rc;
+    if (layout_out) *layout_out = p.w.L;
+    if (ws_out) *ws_out = p.w.ws;
     D->last_plan_valid = true;
-    D->last_plan_off = L.off_plan;
+    D->last_plan_off = p.w.L.off_plan;
     return workspace_release(*D, s);
 }
 
@@ -5393,9 +5405,8 @@ int split_top16_t(void* dev_keys, void* dev_tmp, uint64_t len, rdst_key_kind kin
     if constexpr (LV >= 2) {
         int rc = run_pipeline<K, LV>(static_cast<K*>(dev_keys), static_cast<K*>(dev_tmp), len, kind, LV - 2, LV, false, false, s, nullptr, nullptr);
         if (rc) return rc;
-        hipLaunchKernelGGL((top16_counts_kernel<K>), dim3(blocks), dim3(256), 0, s, static_cast<const K*>(dev_keys), len, (K)km.neg, (K)km.pos,
-                           reinterpret_cast<unsigned long long*>(dev_counts16));
-        return RDST_OK;
+        return launch("top16_counts_kernel", top16_counts_kernel<K>, dim3(blocks), dim3(256), 0, s, static_cast<const K*>(dev_keys), len, (K)km.neg,
+                      (K)km.pos, reinterpret_cast<unsigned long long*>(dev_counts16));
     } else {
         return fail(RDST_ERR_UNSUPPORTED, "a 16-bit split needs keys of at least two bytes");
     }
@@ -5495,9 +5506,9 @@ int regions_swap(K* keys, uint64_t n, uint64_t tile_len, const std::vector<uint6
         const uint64_t c0 = round_chunk[r], c1 = round_chunk[r + 1];
         for (uint64_t c = c0; c < c1; c += (1u << 30)) {  // (a grid dimension holds 2^31 - 1 blocks)
             const uint64_t m = c1 - c < (1u << 30) ? c1 - c : (1u << 30);
-            hipLaunchKernelGGL((swap_ranges_kernel<K>), dim3((uint32_t)m), dim3(256), 0, s, keys, static_cast<const SwapChunk*>(dchunks.p) + c);
+            if (int rc = launch("swap_ranges_kernel", swap_ranges_kernel<K>, dim3((uint32_t)m), dim3(256), 0, s, keys, static_cast<const SwapChunk*>(dchunks.p) + c))
+                return rc;
         }
-        HIP_TRY(hipGetLastError());
     }
     HIP_TRY(hipStreamSynchronize(s));  // `chunks` and the device list go out of scope
     return RDST_OK;
@@ -5572,6 +5583,40 @@ int read_device_error(DeviceState& D, hipStream_t s) {
     return RDST_OK;
 }
 
+// the streaming yardsticks: MODE 0 copies, 1 only reads, 2 only writes
+template <int MODE>
+int stream_run(void* dev_dst, const void* dev_src, uint64_t bytes, void* stream) {
+    if ((MODE != 1 && !dev_dst) || (MODE != 2 && !dev_src)) return fail(RDST_ERR_ARG, "null pointer");
+    if ((reinterpret_cast<uintptr_t>(dev_dst) | reinterpret_cast<uintptr_t>(dev_src) | bytes) & 15u) return fail(RDST_ERR_ALIGN, "16-byte alignment");
+    std::lock_guard<std::mutex> lock(g_mutex);
+    DeviceState* D;
+    int rc = current_device_state(&D);
+    if (rc) return rc;
+    return launch("stream_kernel", stream_kernel<MODE>, dim3((uint32_t)D->cus * 8), dim3(256), 0, static_cast<hipStream_t>(stream),
+                  static_cast<u32x4_t*>(dev_dst), static_cast<const u32x4_t*>(dev_src), bytes / 16, D->err_dev + 8);
+}
+
+// f(uint32_t{}) or f(uint64_t{}): a 4- or 8-byte key, value or index type picked at run time
+template <typename F>
+int by_uint(uint32_t bytes, F&& f) { return bytes == 4 ? f(uint32_t{}) : f(uint64_t{}); }
+
+// [u8; N] rows with N <= 16 are sorted as W-byte integers: widened (expand) before the sort, narrowed (!expand) after it
+uint32_t widened_bytes(uint32_t nb) { return nb <= 4 ? 4 : (nb <= 8 ? 8 : 16); }
+template <typename W>
+int launch_bytes_widen_t(bool expand, unsigned char* raw, void* keys, uint64_t len, uint32_t nb, hipStream_t s) {
+    uint64_t blocks = (len + 255) / 256;
+    if (blocks > 256 * 16) blocks = 256 * 16;
+    if (expand)
+        return launch("bytes_expand_kernel", bytes_expand_kernel<W>, dim3((uint32_t)blocks), dim3(256), 0, s, static_cast<const unsigned char*>(raw),
+                      static_cast<W*>(keys), len, nb);
+    return launch("bytes_compact_kernel", bytes_compact_kernel<W>, dim3((uint32_t)blocks), dim3(256), 0, s, static_cast<const W*>(keys), raw, len, nb);
+}
+int launch_bytes_widen(bool expand, void* raw, void* keys, uint64_t len, uint32_t nb, hipStream_t s) {
+    unsigned char* r = static_cast<unsigned char*>(raw);
+    return nb <= 4 ? launch_bytes_widen_t<uint32_t>(expand, r, keys, len, nb, s)
+                   : (nb <= 8 ? launch_bytes_widen_t<uint64_t>(expand, r, keys, len, nb, s) : launch_bytes_widen_t<u128>(expand, r, keys, len, nb, s));
+}
+
 }  // namespace
 
 // ------------------------------------------------------------------------------------------
@@ -5604,25 +5649,10 @@ int rdst_hip_set_small_sort(int enabled) {
 
 int rdst_hip_set_hybrid(int enabled, uint64_t min_len) {
     std::lock_guard<std::mutex> lock(g_mutex);
-    g_tuning.hybrid = enabled != 0;
-    g_tuning.count_sort = enabled != 2;  // 2: hybrid route with the generic local sort for every key width (A/B, tests)
-    g_tuning.halves = enabled != 3;      // 3: counting K4 reading whole keys (no 16-bit hand-off) (A/B, tests)
-    g_tuning.presample = enabled != 5;   // 5: no sample before K1h: every hybrid-eligible sort counts all its keys' prefixes first (tests)
-    g_tuning.wide2 = enabled != 6;       // 6: 8-byte keys with the one-block-per-CU form of K4 (A/B, tests)
-    g_tuning.wide3 = enabled != 15;      // 15: the default with the second form of the 8-byte K4 (local_wide2_sort_kernel) (A/B, tests)
-    g_tuning.atomic_route = enabled == 1 || enabled == 8;  // 1: the default (4- and 8-byte keys try the atomic route first); 2..7: the K1h hybrid route for every key width (7: with the default forms of K4)
-    g_tuning.exact_msd = enabled != 12;    // 12: the default without the exact form of the MSD passes (the hybrid route's passes are K3's) (A/B, tests)
-    g_tuning.atomic_route = g_tuning.atomic_route || enabled == 12;
-    g_tuning.giants = enabled != 11;       // 11: the default without the giant kernels (a bucket of 65 536 keys sends the sort down the LSD route) (A/B, tests)
-    g_tuning.atomic_route = g_tuning.atomic_route || enabled == 11;
-    g_tuning.chain_routes = enabled != 10; // 10: the default, but a failed atomic route falls straight to the LSD route (A/B, tests)
-    g_tuning.atomic_route = g_tuning.atomic_route || enabled == 10;
-    g_tuning.expand = enabled != 9;        // 9: the K1h hybrid route without the expanding K4 (buckets up to one tile; refused buckets to the ranked kernel) (A/B, tests)
-    g_tuning.atomic_wide = enabled != 8;   // 8: the atomic route for 4-byte keys only, 8-byte keys on the K1h hybrid route (A/B, tests)
-    g_tuning.predict = enabled != 14;      // 14: the default without the sample's prediction of the LSD route (A/B, tests)
-    g_tuning.split = enabled != 16;        // 16: the default without the split of 8-byte slices beyond the atomic route's window (they take the LSD route) (A/B, tests)
-    g_tuning.split_always = enabled == 17; // 17: the default with that split at every length, in eight parts (tests)
-    g_tuning.atomic_route = g_tuning.atomic_route || enabled == 14 || enabled == 15 || enabled == 16 || enabled == 17;
+    const RouteMode* m = kRouteModes;
+    for (const RouteMode& r : kRouteModes)
+        if (r.mode == enabled) m = &r;
+    static_cast<RouteTuning&>(g_tuning) = m->preset;
     g_tuning.hybrid_min_len = min_len;
     return RDST_OK;
 }
@@ -5658,53 +5688,16 @@ int rdst_hip_release_workspace(void) {
     return RDST_OK;
 }
 
-int rdst_hip_stream_copy(void* dev_dst, const void* dev_src, uint64_t bytes, void* stream) {
-    if (!dev_dst || !dev_src) return fail(RDST_ERR_ARG, "null pointer");
-    if ((reinterpret_cast<uintptr_t>(dev_dst) | reinterpret_cast<uintptr_t>(dev_src) | bytes) & 15u) return fail(RDST_ERR_ALIGN, "16-byte alignment");
-    std::lock_guard<std::mutex> lock(g_mutex);
-    DeviceState* D;
-    int rc = current_device_state(&D);
-    if (rc) return rc;
-    hipLaunchKernelGGL((stream_kernel<0>), dim3((uint32_t)D->cus * 8), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<u32x4_t*>(dev_dst),
-                       static_cast<const u32x4_t*>(dev_src), bytes / 16, D->err_dev + 8);
-    HIP_TRY(hipGetLastError());
-    return RDST_OK;
-}
-
-int rdst_hip_stream_read(const void* dev_src, uint64_t bytes, void* stream) {
-    if (!dev_src) return fail(RDST_ERR_ARG, "null pointer");
-    if ((reinterpret_cast<uintptr_t>(dev_src) | bytes) & 15u) return fail(RDST_ERR_ALIGN, "16-byte alignment");
-    std::lock_guard<std::mutex> lock(g_mutex);
-    DeviceState* D;
-    int rc = current_device_state(&D);
-    if (rc) return rc;
-    hipLaunchKernelGGL((stream_kernel<1>), dim3((uint32_t)D->cus * 8), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<u32x4_t*>(nullptr),
-                       static_cast<const u32x4_t*>(dev_src), bytes / 16, D->err_dev + 8);
-    HIP_TRY(hipGetLastError());
-    return RDST_OK;
-}
-
-int rdst_hip_stream_fill(void* dev_dst, uint64_t bytes, void* stream) {
-    if (!dev_dst) return fail(RDST_ERR_ARG, "null pointer");
-    if ((reinterpret_cast<uintptr_t>(dev_dst) | bytes) & 15u) return fail(RDST_ERR_ALIGN, "16-byte alignment");
-    std::lock_guard<std::mutex> lock(g_mutex);
-    DeviceState* D;
-    int rc = current_device_state(&D);
-    if (rc) return rc;
-    hipLaunchKernelGGL((stream_kernel<2>), dim3((uint32_t)D->cus * 8), dim3(256), 0, static_cast<hipStream_t>(stream), static_cast<u32x4_t*>(dev_dst),
-                       static_cast<const u32x4_t*>(nullptr), bytes / 16, D->err_dev + 8);
-    HIP_TRY(hipGetLastError());
-    return RDST_OK;
-}
+int rdst_hip_stream_copy(void* dev_dst, const void* dev_src, uint64_t bytes, void* stream) { return stream_run<0>(dev_dst, dev_src, bytes, stream); }
+int rdst_hip_stream_read(const void* dev_src, uint64_t bytes, void* stream) { return stream_run<1>(nullptr, dev_src, bytes, stream); }
+int rdst_hip_stream_fill(void* dev_dst, uint64_t bytes, void* stream) { return stream_run<2>(dev_dst, nullptr, bytes, stream); }
 
 int rdst_hip_debug_raise_device_error(uint32_t bits, void* stream) {
     std::lock_guard<std::mutex> lock(g_mutex);
     DeviceState* D;
     int rc = current_device_state(&D);
     if (rc) return rc;
-    hipLaunchKernelGGL(raise_error_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), D->err_dev, bits);
-    HIP_TRY(hipGetLastError());
-    return RDST_OK;
+    return launch("raise_error_kernel", raise_error_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), D->err_dev, bits);
 }
 
 int rdst_hip_set_chain_split(int enabled) {
@@ -5850,17 +5843,14 @@ int rdst_hip_sort_pairs_device(void* dev_keys, void* dev_vals, void* dev_tmp_key
         return fail(RDST_ERR_ALIGN, "value pointer not aligned to the value size");
     std::lock_guard<std::mutex> lock(g_mutex);
     hipStream_t s = static_cast<hipStream_t>(stream);
-#define RDST_PAIRS(KT, LV, VT)                                                                                          \
-    rc = (run_pipeline<KT, LV, VT>(static_cast<KT*>(dev_keys), static_cast<KT*>(dev_tmp_keys), len, kind, 0, LV, true, true, s, \
-                                   nullptr, nullptr, static_cast<VT*>(dev_vals), static_cast<VT*>(dev_tmp_vals)))
-    if (key_bytes == 4) {
-        if (val_bytes == 4) RDST_PAIRS(uint32_t, 4, uint32_t);
-        else RDST_PAIRS(uint32_t, 4, uint64_t);
-    } else {
-        if (val_bytes == 4) RDST_PAIRS(uint64_t, 8, uint32_t);
-        else RDST_PAIRS(uint64_t, 8, uint64_t);
-    }
-#undef RDST_PAIRS
+    rc = by_uint(key_bytes, [&](auto k) {
+        return by_uint(val_bytes, [&](auto v) {
+            using KT = decltype(k);
+            using VT = decltype(v);
+            return run_pipeline<KT, (int)sizeof(KT), VT>(static_cast<KT*>(dev_keys), static_cast<KT*>(dev_tmp_keys), len, kind, 0, sizeof(KT), true, true, s, nullptr,
+                                                         nullptr, static_cast<VT*>(dev_vals), static_cast<VT*>(dev_tmp_vals));
+        });
+    });
     return rc;
 }
 
@@ -5877,47 +5867,26 @@ int rdst_hip_device_status(void* stream) {
 namespace {
 // [u8; N] host slice: H2D of the raw bytes, expand to W-byte integers, sort those, compact, D2H
 int sort_byte_keys_host(void* host_data, uint64_t len, uint32_t nb, const rdst_hip_opts* opts) {
-    int prev_dev = -1;
+    rdst_internal::HostJob job;
     if (opts && opts->device >= 0) {
-        HIP_TRY(hipGetDevice(&prev_dev));
+        HIP_TRY(hipGetDevice(&job.prev_dev));
         HIP_TRY(hipSetDevice(opts->device));
     }
-    const uint32_t w = nb <= 4 ? 4 : (nb <= 8 ? 8 : 16);
+    const uint32_t w = widened_bytes(nb);
     void *d_raw = nullptr, *d_keys = nullptr, *d_tmp = nullptr;
-    hipStream_t s = nullptr;
-    auto cleanup = [&]() {
-        for (void* p : {d_raw, d_keys, d_tmp})
-            if (p) (void)hipFree(p);
-        if (s) (void)hipStreamDestroy(s);
-        if (prev_dev >= 0) (void)hipSetDevice(prev_dev);
-    };
-    hipError_t e;
-#define RDST_B_TRY(expr) if ((e = (expr)) != hipSuccess) { if (s) (void)hipStreamSynchronize(s); cleanup(); return fail(RDST_ERR_HIP, #expr, e); }
-    RDST_B_TRY(hipStreamCreate(&s));
-    RDST_B_TRY(hipMalloc(&d_raw, (size_t)len * nb));
-    RDST_B_TRY(hipMalloc(&d_keys, (size_t)len * w));
-    RDST_B_TRY(hipMalloc(&d_tmp, (size_t)len * w));
-    RDST_B_TRY(hipMemcpyAsync(d_raw, host_data, (size_t)len * nb, hipMemcpyHostToDevice, s));
-    uint64_t blocks = (len + 255) / 256;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    const unsigned char* raw = static_cast<const unsigned char*>(d_raw);
-    if (w == 4) hipLaunchKernelGGL((bytes_expand_kernel<uint32_t>), dim3((uint32_t)blocks), dim3(256), 0, s, raw, static_cast<uint32_t*>(d_keys), len, nb);
-    else if (w == 8) hipLaunchKernelGGL((bytes_expand_kernel<uint64_t>), dim3((uint32_t)blocks), dim3(256), 0, s, raw, static_cast<uint64_t*>(d_keys), len, nb);
-    else hipLaunchKernelGGL((bytes_expand_kernel<u128>), dim3((uint32_t)blocks), dim3(256), 0, s, raw, static_cast<u128*>(d_keys), len, nb);
-    RDST_B_TRY(hipGetLastError());
-    int rc = rdst_hip_sort_device(d_keys, d_tmp, len, w, RDST_KEY_UNSIGNED, w, s);
-    if (rc == RDST_OK) rc = rdst_hip_device_status(s);
-    if (rc != RDST_OK) { (void)hipStreamSynchronize(s); cleanup(); return rc; }
-    unsigned char* rawo = static_cast<unsigned char*>(d_raw);
-    if (w == 4) hipLaunchKernelGGL((bytes_compact_kernel<uint32_t>), dim3((uint32_t)blocks), dim3(256), 0, s, static_cast<const uint32_t*>(d_keys), rawo, len, nb);
-    else if (w == 8) hipLaunchKernelGGL((bytes_compact_kernel<uint64_t>), dim3((uint32_t)blocks), dim3(256), 0, s, static_cast<const uint64_t*>(d_keys), rawo, len, nb);
-    else hipLaunchKernelGGL((bytes_compact_kernel<u128>), dim3((uint32_t)blocks), dim3(256), 0, s, static_cast<const u128*>(d_keys), rawo, len, nb);
-    RDST_B_TRY(hipGetLastError());
+    HIP_TRY(hipStreamCreate(&job.s));
+    HIP_TRY(job.alloc(&d_raw, (size_t)len * nb));
+    HIP_TRY(job.alloc(&d_keys, (size_t)len * w));
+    HIP_TRY(job.alloc(&d_tmp, (size_t)len * w));
+    HIP_TRY(hipMemcpyAsync(d_raw, host_data, (size_t)len * nb, hipMemcpyHostToDevice, job.s));
+    int rc = launch_bytes_widen(true, d_raw, d_keys, len, nb, job.s);
+    if (rc == RDST_OK) rc = rdst_hip_sort_device(d_keys, d_tmp, len, w, RDST_KEY_UNSIGNED, w, job.s);
+    if (rc == RDST_OK) rc = rdst_hip_device_status(job.s);
+    if (rc == RDST_OK) rc = launch_bytes_widen(false, d_raw, d_keys, len, nb, job.s);
+    if (rc != RDST_OK) return rc;
     // the host buffer is written only now, after the device reported success
-    RDST_B_TRY(hipMemcpyAsync(host_data, d_raw, (size_t)len * nb, hipMemcpyDeviceToHost, s));
-    RDST_B_TRY(hipStreamSynchronize(s));
-#undef RDST_B_TRY
-    cleanup();
+    HIP_TRY(hipMemcpyAsync(host_data, d_raw, (size_t)len * nb, hipMemcpyDeviceToHost, job.s));
+    HIP_TRY(hipStreamSynchronize(job.s));
     return RDST_OK;
 }
 }  // namespace
@@ -6056,64 +6025,51 @@ int rdst_hip_sort_records(void* host_records, uint64_t len, uint32_t record_byte
     if (len > 0 && host_records == nullptr) return fail(RDST_ERR_ARG, "null record pointer");
     if (len >= (1ull << 36)) return fail(RDST_ERR_ARG, "len too large");
     if (len <= 1) return RDST_OK;
-    int prev_dev = -1;
+    rdst_internal::HostJob job;
     if (opts && opts->device >= 0) {
-        HIP_TRY(hipGetDevice(&prev_dev));
+        HIP_TRY(hipGetDevice(&job.prev_dev));
         HIP_TRY(hipSetDevice(opts->device));
     }
     const size_t bytes = (size_t)len * record_bytes;
     const uint32_t idx_bytes = len < (1ull << 32) ? 4 : 8;
     void *d_rec = nullptr, *d_out = nullptr, *d_keys = nullptr, *d_tk = nullptr, *d_idx = nullptr, *d_ti = nullptr;
-    hipStream_t s = nullptr;
-    auto cleanup = [&]() {
-        for (void* p : {d_rec, d_out, d_keys, d_tk, d_idx, d_ti})
-            if (p) (void)hipFree(p);
-        if (s) (void)hipStreamDestroy(s);
-        if (prev_dev >= 0) (void)hipSetDevice(prev_dev);
-    };
-    hipError_t e;
-#define RDST_REC_TRY(expr) if ((e = (expr)) != hipSuccess) { if (s) (void)hipStreamSynchronize(s); cleanup(); return fail(RDST_ERR_HIP, #expr, e); }
-    RDST_REC_TRY(hipStreamCreate(&s));
-    RDST_REC_TRY(hipMalloc(&d_rec, bytes));
-    RDST_REC_TRY(hipMalloc(&d_out, bytes));
-    RDST_REC_TRY(hipMalloc(&d_keys, (size_t)len * key_bytes));
-    RDST_REC_TRY(hipMalloc(&d_tk, (size_t)len * key_bytes));
-    RDST_REC_TRY(hipMalloc(&d_idx, (size_t)len * idx_bytes));
-    RDST_REC_TRY(hipMalloc(&d_ti, (size_t)len * idx_bytes));
-    RDST_REC_TRY(hipMemcpyAsync(d_rec, host_records, bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipStreamCreate(&job.s));
+    hipStream_t s = job.s;
+    HIP_TRY(job.alloc(&d_rec, bytes));
+    HIP_TRY(job.alloc(&d_out, bytes));
+    HIP_TRY(job.alloc(&d_keys, (size_t)len * key_bytes));
+    HIP_TRY(job.alloc(&d_tk, (size_t)len * key_bytes));
+    HIP_TRY(job.alloc(&d_idx, (size_t)len * idx_bytes));
+    HIP_TRY(job.alloc(&d_ti, (size_t)len * idx_bytes));
+    HIP_TRY(hipMemcpyAsync(d_rec, host_records, bytes, hipMemcpyHostToDevice, s));
     uint64_t blocks = (len + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
-    const unsigned char* rec = static_cast<const unsigned char*>(d_rec);
-    if (key_bytes == 4) {
-        if (idx_bytes == 4) hipLaunchKernelGGL((extract_key_kernel<uint32_t, uint32_t>), dim3((uint32_t)blocks), dim3(256), 0, s, rec, len, record_bytes, key_offset, static_cast<uint32_t*>(d_keys), static_cast<uint32_t*>(d_idx));
-        else hipLaunchKernelGGL((extract_key_kernel<uint32_t, uint64_t>), dim3((uint32_t)blocks), dim3(256), 0, s, rec, len, record_bytes, key_offset, static_cast<uint32_t*>(d_keys), static_cast<uint64_t*>(d_idx));
-    } else {
-        if (idx_bytes == 4) hipLaunchKernelGGL((extract_key_kernel<uint64_t, uint32_t>), dim3((uint32_t)blocks), dim3(256), 0, s, rec, len, record_bytes, key_offset, static_cast<uint64_t*>(d_keys), static_cast<uint32_t*>(d_idx));
-        else hipLaunchKernelGGL((extract_key_kernel<uint64_t, uint64_t>), dim3((uint32_t)blocks), dim3(256), 0, s, rec, len, record_bytes, key_offset, static_cast<uint64_t*>(d_keys), static_cast<uint64_t*>(d_idx));
-    }
-    RDST_REC_TRY(hipGetLastError());
-    int rc = rdst_hip_sort_pairs_device(d_keys, d_idx, d_tk, d_ti, len, key_bytes, kind, key_bytes, idx_bytes, s);
+    int rc = by_uint(key_bytes, [&](auto k) {
+        return by_uint(idx_bytes, [&](auto i) {
+            return launch("extract_key_kernel", extract_key_kernel<decltype(k), decltype(i)>, dim3((uint32_t)blocks), dim3(256), 0, s,
+                          static_cast<const unsigned char*>(d_rec), len, record_bytes, key_offset, static_cast<decltype(k)*>(d_keys), static_cast<decltype(i)*>(d_idx));
+        });
+    });
+    if (rc == RDST_OK) rc = rdst_hip_sort_pairs_device(d_keys, d_idx, d_tk, d_ti, len, key_bytes, kind, key_bytes, idx_bytes, s);
     if (rc == RDST_OK) rc = rdst_hip_device_status(s);
-    if (rc != RDST_OK) { (void)hipStreamSynchronize(s); cleanup(); return rc; }
+    if (rc != RDST_OK) return rc;
     // rows in the order of the sorted indices, in the widest units the row size allows
     const uint32_t unit = record_bytes % 16 == 0 ? 16 : (record_bytes % 8 == 0 ? 8 : 4);
     const uint64_t total_units = len * (record_bytes / unit);
     uint64_t gblocks = (total_units + 255) / 256;
     if (gblocks > 256 * 32) gblocks = 256 * 32;
     struct alignas(16) U16 { uint64_t a, b; };
-#define RDST_GATHER(UT, IT) hipLaunchKernelGGL((gather_records_kernel<UT, IT>), dim3((uint32_t)gblocks), dim3(256), 0, s, static_cast<const UT*>(d_rec), static_cast<UT*>(d_out), static_cast<const IT*>(d_idx), len, record_bytes / unit)
-    if (idx_bytes == 4) {
-        if (unit == 16) RDST_GATHER(U16, uint32_t); else if (unit == 8) RDST_GATHER(uint64_t, uint32_t); else RDST_GATHER(uint32_t, uint32_t);
-    } else {
-        if (unit == 16) RDST_GATHER(U16, uint64_t); else if (unit == 8) RDST_GATHER(uint64_t, uint64_t); else RDST_GATHER(uint32_t, uint64_t);
-    }
-#undef RDST_GATHER
-    RDST_REC_TRY(hipGetLastError());
+    auto gather = [&](auto u, auto i) {
+        using UT = decltype(u);
+        using IT = decltype(i);
+        return launch("gather_records_kernel", gather_records_kernel<UT, IT>, dim3((uint32_t)gblocks), dim3(256), 0, s, static_cast<const UT*>(d_rec),
+                      static_cast<UT*>(d_out), static_cast<const IT*>(d_idx), len, record_bytes / unit);
+    };
+    rc = by_uint(idx_bytes, [&](auto i) { return unit == 16 ? gather(U16{}, i) : (unit == 8 ? gather(uint64_t{}, i) : gather(uint32_t{}, i)); });
+    if (rc != RDST_OK) return rc;
     // the host buffer is written only now, after the device reported success
-    RDST_REC_TRY(hipMemcpyAsync(host_records, d_out, bytes, hipMemcpyDeviceToHost, s));
-    RDST_REC_TRY(hipStreamSynchronize(s));
-#undef RDST_REC_TRY
-    cleanup();
+    HIP_TRY(hipMemcpyAsync(host_records, d_out, bytes, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
     return RDST_OK;
 }
 
@@ -6246,9 +6202,7 @@ int rdst_hip_split_top16_device(void* dev_keys, void* dev_tmp, uint64_t len, uin
     if (blocks > (uint64_t)D->cus * 16) blocks = (uint64_t)D->cus * 16;
     // two stable passes on levels L-2, L-1 (keys -> tmp -> keys): the shard ends up ordered by its top 16 bits, in place
     RDST_BY_WIDTH(elem_bytes, rc = (split_top16_t<K, LV>(dev_keys, dev_tmp, len, kind, km, (uint32_t)blocks, dev_counts16, s)));
-    if (rc) return rc;
-    HIP_TRY(hipGetLastError());
-    return RDST_OK;
+    return rc;
 }
 
 int rdst_hip_level_counts(const void* dev_keys, uint64_t len, uint32_t elem_bytes, rdst_key_kind kind, uint32_t level,
@@ -6282,8 +6236,8 @@ int rdst_hip_level_counts(const void* dev_keys, uint64_t len, uint32_t elem_byte
     const uint64_t cap = (uint64_t)D->cus * 8;
     if (blocks > cap) blocks = cap;
     const int shift = (int)level * 8;
-    RDST_BY_WIDTH(elem_bytes, (void)LV; hipLaunchKernelGGL((level_counts_kernel<K>), dim3((uint32_t)blocks), dim3(256), 0, s, static_cast<const K*>(dev_keys), len, shift, (K)km.neg, (K)km.pos, d_counts, d_flag));
-    HIP_TRY(hipGetLastError());
+    RDST_BY_WIDTH(elem_bytes, (void)LV; rc = launch("level_counts_kernel", level_counts_kernel<K>, dim3((uint32_t)blocks), dim3(256), 0, s, static_cast<const K*>(dev_keys), len, shift, (K)km.neg, (K)km.pos, d_counts, d_flag));
+    if (rc) return rc;
     uint32_t flag = 0;
     u128 first = 0, last = 0;
     HIP_TRY(hipMemcpyAsync(counts, d_counts, sizeof(uint64_t) * RADIX, hipMemcpyDeviceToHost, s));
@@ -6320,27 +6274,27 @@ int device_error_word(uint32_t** out) {
     return RDST_OK;
 }
 
-static uint32_t widened_bytes(uint32_t nb) { return nb <= 4 ? 4 : (nb <= 8 ? 8 : 16); }
-
 uint64_t widened_scratch_bytes(uint64_t len, uint32_t nb) { return 2 * (uint64_t)align_up((size_t)len * widened_bytes(nb), 256); }
 
 int sort_bytes_widened(void* dev_rows, uint64_t len, uint32_t nb, void* scratch, hipStream_t s) {
     const uint32_t w = widened_bytes(nb);
     void* d_keys = scratch;
     void* d_tmp = static_cast<char*>(scratch) + align_up((size_t)len * w, 256);
-    uint64_t blocks = (len + 255) / 256;
-    if (blocks > 256 * 16) blocks = 256 * 16;
-    unsigned char* raw = static_cast<unsigned char*>(dev_rows);
-    if (w == 4) hipLaunchKernelGGL((bytes_expand_kernel<uint32_t>), dim3((uint32_t)blocks), dim3(256), 0, s, raw, static_cast<uint32_t*>(d_keys), len, nb);
-    else if (w == 8) hipLaunchKernelGGL((bytes_expand_kernel<uint64_t>), dim3((uint32_t)blocks), dim3(256), 0, s, raw, static_cast<uint64_t*>(d_keys), len, nb);
-    else hipLaunchKernelGGL((bytes_expand_kernel<u128>), dim3((uint32_t)blocks), dim3(256), 0, s, raw, static_cast<u128*>(d_keys), len, nb);
-    HIP_TRY(hipGetLastError());
-    int rc = rdst_hip_sort_device(d_keys, d_tmp, len, w, RDST_KEY_UNSIGNED, w, s);
-    if (rc) return rc;
-    if (w == 4) hipLaunchKernelGGL((bytes_compact_kernel<uint32_t>), dim3((uint32_t)blocks), dim3(256), 0, s, static_cast<const uint32_t*>(d_keys), raw, len, nb);
-    else if (w == 8) hipLaunchKernelGGL((bytes_compact_kernel<uint64_t>), dim3((uint32_t)blocks), dim3(256), 0, s, static_cast<const uint64_t*>(d_keys), raw, len, nb);
-    else hipLaunchKernelGGL((bytes_compact_kernel<u128>), dim3((uint32_t)blocks), dim3(256), 0, s, static_cast<const u128*>(d_keys), raw, len, nb);
-    HIP_TRY(hipGetLastError());
+    int rc = launch_bytes_widen(true, dev_rows, d_keys, len, nb, s);
+    if (rc == RDST_OK) rc = rdst_hip_sort_device(d_keys, d_tmp, len, w, RDST_KEY_UNSIGNED, w, s);
+    if (rc == RDST_OK) rc = launch_bytes_widen(false, dev_rows, d_keys, len, nb, s);
+    return rc;
+}
+
+// hipFuncSetAttribute acts on the CURRENT device's copy of the function: remember (device, kernel) -> bytes
+int ensure_lds_attr(const void* fn, size_t lds) {
+    static std::map<std::pair<int, const void*>, size_t> done;  // callers hold g_mutex
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    auto it = done.find({dev, fn});
+    if (it != done.end() && it->second == lds) return RDST_OK;
+    HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    done[{dev, fn}] = lds;
     return RDST_OK;
 }
 

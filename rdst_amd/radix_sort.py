@@ -519,18 +519,34 @@ def profile_run(run: int, levels: int):
     return out
 
 
+# rdst_hip_set_hybrid's modes by name (the integers include/rdst_hip.h documents; kRouteModes in csrc/rdst_kernels.hip)
+ROUTE_MODES = {
+    "lsd": 0,                # LSD only (False)
+    "default": 1,            # 4- and 8-byte keys try the atomic route, then the hybrid one, then LSD (True)
+    "ranked": 2,             # "k1h" with the generic ranked K4
+    "count_whole_keys": 3,   # "k1h" with the counting K4 fed whole keys (no 16-bit hand-off)
+    "no_presample": 5,       # "k1h" without the key sample
+    "wide_one_block": 6,     # "k1h", 8-byte keys with the one-block-per-CU K4
+    "k1h": 7,                # the K1h hybrid route for every width
+    "atomic_4_only": 8,      # the atomic route for 4-byte keys only (8-byte keys on the hybrid route)
+    "no_expand": 9,          # "k1h" without the expanding K4 (buckets up to one tile only)
+    "atomic_then_lsd": 10,   # the default without the hybrid route as the atomic route's first fallback
+    "no_giants": 11,         # the default without the giant kernels (a 4-byte bucket of 65 536 keys and more: LSD route)
+    "no_exact_msd": 12,      # the default without the exact form of the MSD passes
+    "no_predict": 14,        # the default without the sample's prediction of the LSD route
+    "wide2": 15,             # the default with the second form of the 8-byte K4 (local_wide2_sort_kernel)
+    "no_split": 16,          # the default without the split of slices beyond the atomic route's window (run_split_sort)
+    "split_always": 17,      # the default with that split at every length, in eight parts (tests)
+}
+
+
 def set_hybrid(enabled=True, min_len=0):
     """Route choice knob (rdst_hip_set_hybrid): consider the byte-saving routes for sorts of at least `min_len` keys (0 = the
-    built-in threshold).  True / 1: the default — 4- and 8-byte keys try the atomic route.  False / 0: LSD only.  A/B and
-    test modes: 7 the K1h hybrid route for every width; 2 the same with the generic ranked K4; 3 counting K4 fed with whole
-    keys (no 16-bit hand-off); 5 no presample; 6 8-byte keys with the one-block-per-CU K4; 8 the atomic route for 4-byte
-    keys only (8-byte keys on the hybrid route); 9 the hybrid route without the expanding K4 (buckets up to one tile only);
-    10 the default without the hybrid route as the atomic route's first fallback; 11 the default without the giant kernels
-    (4-byte keys: a bucket of 65 536 keys and more sends the sort down the LSD route); 12 the default without the exact form
-    of the MSD passes; 14 the default without the sample's prediction of the LSD route; 15 the default with the second form
-    of the 8-byte K4 (local_wide2_sort_kernel); 16 the default without the split of 8-byte slices beyond the atomic route's
-    window (run_split_sort); 17 the default with that split at every length, in eight parts (tests)."""
-    _lib.check(_lib.load().rdst_hip_set_hybrid(int(enabled) if enabled in (2, 3, 5, 6, 7, 8, 9, 10, 11, 12, 14, 15, 16, 17) else int(bool(enabled)), int(min_len)))
+    built-in threshold).  `enabled`: True / False, or an A/B and test mode by its name or integer (ROUTE_MODES); anything else
+    counts as its truth value."""
+    if isinstance(enabled, str):
+        enabled = ROUTE_MODES[enabled]
+    _lib.check(_lib.load().rdst_hip_set_hybrid(int(enabled) if enabled in ROUTE_MODES.values() else int(bool(enabled)), int(min_len)))
 
 
 def release_workspace(device=None) -> None:

@@ -28,6 +28,25 @@ def test_abi_version(hiplib):
     assert hiplib.rdst_hip_abi_version() == 2
 
 
+def _documented_route_modes():
+    """the integers the comment above rdst_hip_set_hybrid gives a meaning to ("enabled == 0: ...; 1: ...; 2 / 3 / 5 / 6 / 9: ...")"""
+    text = open(os.path.join(ROOT, "include", "rdst_hip.h")).read()
+    comment = re.findall(r"/\*(.*?)\*/\s*int rdst_hip_set_hybrid\(", text, flags=re.S)[-1].rsplit("/*", 1)[-1]
+    modes = comment[comment.index("enabled == "):comment.index("min_len == 0")]
+    listed = set()
+    for group in re.findall(r"((?:\d+ / )*\d+):", modes.replace("enabled == ", "")):
+        listed.update(int(m) for m in group.split(" / "))
+    return listed
+
+
+def test_route_mode_names_cover_the_documented_modes():
+    from rdst_amd import radix_sort
+    documented = _documented_route_modes()
+    assert documented == {0, 1, 2, 3, 5, 6, 7, 8, 9, 10, 11, 12, 14, 15, 16, 17}
+    assert sorted(radix_sort.ROUTE_MODES.values()) == sorted(documented)   # one name per mode, no other integers
+    assert radix_sort.ROUTE_MODES["lsd"] == 0 and radix_sort.ROUTE_MODES["default"] == 1
+
+
 def test_argument_validation_happens_before_any_device_call(hiplib):
     from rdst_amd import _lib
     buf = (ctypes.c_uint32 * 8)()
