@@ -201,6 +201,12 @@ int rdst_hip_stream_fill(void* dev_dst, uint64_t bytes, void* stream);
  * rdst_hip_device_status (or a blocking entry point) reports and clears it. */
 int rdst_hip_debug_raise_device_error(uint32_t bits, void* stream);
 
+/* Test hook: what the key sample of the most recent pipeline on the current device decided (presample_kernel; it runs from
+ * 2^26 keys up, ahead of the byte-saving routes): out = { win_shift, win_top, gross_skew, top_skew, low_dups, predict_lsd },
+ * as the sample left them (no later kernel writes these words).  All zero when no pipeline has run, when the sort was too
+ * short for a sample or took none (set_hybrid mode 5, the LSD-only setting).  Blocking, like rdst_hip_last_route. */
+int rdst_hip_debug_last_sample(void* stream, uint32_t out[6]);
+
 /* Parity hook for get_counts_with_ends (src/sort_utils.rs:109-180) /
  * par_get_counts_with_ends (:35-106): 256-bin histogram of digit `level` over a
  * device-resident slice, plus the `already_sorted` flag (digit sequence non-decreasing)

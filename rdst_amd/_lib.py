@@ -47,6 +47,7 @@ SYMBOLS = (
     "rdst_hip_set_hybrid",
     "rdst_hip_last_route",
     "rdst_hip_debug_raise_device_error",
+    "rdst_hip_debug_last_sample",
     "rdst_hip_stream_copy",
     "rdst_hip_stream_read",
     "rdst_hip_stream_fill",
@@ -124,6 +125,7 @@ def load():
     lib.rdst_hip_set_hybrid.argtypes = [ci, u64]
     lib.rdst_hip_last_route.argtypes = [vp, ctypes.POINTER(u32)]
     lib.rdst_hip_debug_raise_device_error.argtypes = [u32, vp]
+    lib.rdst_hip_debug_last_sample.argtypes = [vp, ctypes.POINTER(u32)]
     lib.rdst_hip_stream_copy.argtypes = [vp, vp, u64, vp]
     lib.rdst_hip_stream_read.argtypes = [vp, u64, vp]
     lib.rdst_hip_stream_fill.argtypes = [vp, u64, vp]

@@ -4574,7 +4574,7 @@ int current_device_state(DeviceState** out, int* dev_out = nullptr) {
             return fail(RDST_ERR_NO_DEVICE, b);
         }
         D.cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        HIP_TRY(hipHostMalloc((void**)&D.host_err, 64, hipHostMallocDefault));
+        HIP_TRY(hipHostMalloc((void**)&D.host_err, 128, hipHostMallocDefault));  // [0] the error word, [4] a route, [8..32) a span of the plan
         HIP_TRY(hipMalloc((void**)&D.err_dev, 256));
         HIP_TRY(hipMemset(D.err_dev, 0, 256));
         HIP_TRY(hipEventCreateWithFlags(&D.last_done, hipEventDisableTiming));
@@ -5698,6 +5698,33 @@ int rdst_hip_debug_raise_device_error(uint32_t bits, void* stream) {
     int rc = current_device_state(&D);
     if (rc) return rc;
     return launch("raise_error_kernel", raise_error_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), D->err_dev, bits);
+}
+
+int rdst_hip_debug_last_sample(void* stream, uint32_t out[6]) {
+    std::lock_guard<std::mutex> lock(g_mutex);
+    DeviceState* D;
+    int rc = current_device_state(&D);
+    if (rc) return rc;
+    if (!out) return fail(RDST_ERR_ARG, "null output");
+    for (int i = 0; i < 6; ++i) out[i] = 0;
+    if (!D->ws || !D->last_plan_valid) return RDST_OK;  // no pipeline yet (or the one-workgroup sort)
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if ((rc = workspace_acquire(*D, s))) return rc;  // the sort may have run on another stream
+    // presample_kernel is the only writer of these words (route_kernel and msd_finish_kernel read them): one copy of the
+    // plan's span from gross_skew to predict_lsd holds them as the sample left them
+    constexpr size_t lo = offsetof(Plan, gross_skew), hi = offsetof(Plan, predict_lsd) + sizeof(uint32_t);
+    static_assert(hi > lo && (hi - lo) / sizeof(uint32_t) <= 24, "the span fits the pinned words behind the route's");
+    uint32_t* h = D->host_err + 8;
+    HIP_TRY(hipMemcpyAsync(h, static_cast<char*>(D->ws) + D->last_plan_off + lo, hi - lo, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    auto word = [&](size_t off) { return h[(off - lo) / sizeof(uint32_t)]; };
+    out[0] = word(offsetof(Plan, win_shift));
+    out[1] = word(offsetof(Plan, win_top));
+    out[2] = word(offsetof(Plan, gross_skew));
+    out[3] = word(offsetof(Plan, top_skew));
+    out[4] = word(offsetof(Plan, low_dups));
+    out[5] = word(offsetof(Plan, predict_lsd));
+    return RDST_OK;
 }
 
 int rdst_hip_set_chain_split(int enabled) {

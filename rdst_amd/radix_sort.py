@@ -567,5 +567,19 @@ def last_route(device=None) -> str:
     return {1: "hybrid", 2: "atomic"}.get(r.value, "lsd")
 
 
+SAMPLE_WORDS = ("win_shift", "win_top", "gross_skew", "top_skew", "low_dups", "predict_lsd")
+
+
+def last_sample(device=None) -> dict:
+    """What the key sample of the most recent sort on the current stream's device decided (rdst_hip_debug_last_sample, a test
+    hook): the six plan words of SAMPLE_WORDS by name; all zero when the sort took no sample."""
+    import torch
+    lib = _lib.load()
+    out = (ctypes.c_uint32 * 6)()
+    with torch.cuda.device(device):
+        _lib.check(lib.rdst_hip_debug_last_sample(ctypes.c_void_p(torch.cuda.current_stream().cuda_stream), out))
+    return {name: int(out[i]) for i, name in enumerate(SAMPLE_WORDS)}
+
+
 def last_profile(levels: int):
     return profile_run(-1, levels) if profile_runs() else None

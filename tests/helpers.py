@@ -306,3 +306,332 @@ def banded(n, dtype, offset_bytes=0, band_bytes=BAND_BYTES, seed=0, fill="random
     band behind it; ``init``: its contents (else the fill).  Returns the :class:`Bands`: ``bands[name]`` is the view,
     ``bands.check()`` the test."""
     return Bands([(name, init if init is not None else (n, dtype), offset_bytes)], band_bytes, seed, fill, device)
+
+
+# ---- the key sample (presample_kernel) restated, and inputs built around its positions ---------------------------------
+# Every constant below is the library's own, quoted from rdst_amd/csrc/rdst_kernels.hip (the line it stands on):
+PRESAMPLE_KEYS = 8192            # :452  keys the sample reads, at the positions k * (n / 8192)
+PRESAMPLE_MIN_LEN = 1 << 26      # :453  no sample below this length
+PRESAMPLE_DUP_LIMIT = 5000       # :458  repeated low halves (4-byte keys)
+PRESAMPLE_TOP_LIMIT = 2 * PRESAMPLE_KEYS // 256   # :459  hits on one top byte: 64
+GIANT_MIN = 65536                # :760
+EXPAND_MAX = 65535               # :2862
+GIANT_MAX = 4096                 # :4481
+LOCAL_TILE = {4: 12 * 64 * 22, 8: 16 * 64 * 16}   # :2310-2312  local_tile(): K4's tile, 16 896 / 16 384 keys
+MSD_WAVES, MSD_KPT = 12, {4: 22, 8: 11}           # :4451-4461  pass A's block and keys per thread
+SAMPLE_WORDS = ("win_shift", "win_top", "gross_skew", "top_skew", "low_dups", "predict_lsd")
+
+_ROUTE_FIELDS = dict(hybrid=True, count_sort=True, halves=True, presample=True, wide2=True, wide3=True, atomic_route=True,
+                     exact_msd=True, giants=True, chain_routes=True, expand=True, atomic_wide=True, split=True,
+                     split_always=False, predict=True)                 # :4359-4375  RouteTuning's defaults
+_ROUTE_MODES = {7: (False, None), 0: (False, ("hybrid", False)), 1: (True, None), 2: (False, ("count_sort", False)),
+                3: (False, ("halves", False)), 5: (False, ("presample", False)), 6: (False, ("wide2", False)),
+                8: (True, ("atomic_wide", False)), 9: (False, ("expand", False)), 10: (True, ("chain_routes", False)),
+                11: (True, ("giants", False)), 12: (True, ("exact_msd", False)), 14: (True, ("predict", False)),
+                15: (True, ("wide3", False)), 16: (True, ("split", False)), 17: (True, ("split_always", True))}   # :4400-4417
+
+
+def route_tuning(mode=1, min_len=0):
+    """what rdst_hip_set_hybrid(mode, min_len) leaves in force: kRouteModes' preset (the default with or without the atomic
+    route, at most one field changed) and the length knob"""
+    atomic, change = _ROUTE_MODES[int(mode)]
+    t = dict(_ROUTE_FIELDS, atomic_route=atomic, min_len=int(min_len), mode=int(mode))
+    if change:
+        t[change[0]] = change[1]
+    return t
+
+
+def routes_tried(n, key_bytes, t):
+    """(try_atomic, try_hybrid) of a whole key-only sort: atomic_eligible, hybrid_eligible, pick_routes (:4642-4657, :5007-5016);
+    4-byte keys below 2^30 bytes of slice (pass shape 4, halves possible) are assumed, as every test here has them"""
+    amin = t["min_len"] or ((1 << 26) if key_bytes == 8 else (3 << 26))
+    hmin = t["min_len"] or (1 << 28)
+    mean = n / 65536
+    atomic = t["hybrid"] and t["atomic_route"] and amin <= n < (1 << 30) and mean + 8.0 * mean ** 0.5 <= LOCAL_TILE[key_bytes]
+    if key_bytes == 4:
+        assert n * 4 < (1 << 32)
+    else:
+        atomic = atomic and t["atomic_wide"] and t["count_sort"] and t["wide2"]
+    cap = EXPAND_MAX if key_bytes == 4 and t["count_sort"] and t["expand"] else LOCAL_TILE[key_bytes]
+    hybrid = t["hybrid"] and hmin <= n <= 65536 * cap and n < (1 << 32)
+    hybrid = hybrid and (not atomic or (t["chain_routes"] and (key_bytes == 8 or (t["halves"] and t["count_sort"]))))
+    return bool(atomic), bool(hybrid)
+
+
+def sample_positions(n):
+    return np.arange(PRESAMPLE_KEYS, dtype=np.int64) * (n // PRESAMPLE_KEYS)
+
+
+def unmapped(m, dtype):
+    """inverse of mapped_key: the keys of `dtype` whose mapped images are the unsigned integers `m`"""
+    dt = np.dtype(dtype)
+    w = dt.itemsize * 8
+    m = np.asarray(m, dtype=f"u{dt.itemsize}")
+    msb = np.array(1 << (w - 1), dtype=m.dtype)
+    if dt.kind == "u":
+        u = m.copy()
+    elif dt.kind == "i":
+        u = m ^ msb
+    else:                       # a mapped float with its top bit set was a non-negative one (u ^ msb), else a negative (~u)
+        u = np.where((m & msb) != 0, m ^ msb, ~m)
+    return u.view(dt)
+
+
+def sample_verdict(keys, route_tuning=None, n=None):
+    """The six plan words presample_kernel / launch_presample (:461-546, :4793-4805) leave for this slice, from numpy alone.
+    `keys`: the whole slice, or (with `n`) just its 8 192 keys at sample_positions(n), in that order."""
+    t = route_tuning or globals()["route_tuning"]()
+    if n is None:
+        n = len(keys)
+        keys = keys[sample_positions(n)] if n >= PRESAMPLE_KEYS else keys
+    out = dict.fromkeys(SAMPLE_WORDS, 0)
+    kb = keys.dtype.itemsize
+    if not t["presample"] or n < PRESAMPLE_MIN_LEN or not any(routes_tried(n, kb, t)):
+        return out
+    assert len(keys) == PRESAMPLE_KEYS
+    w = kb * 8
+    m = mapped_key(keys).astype(np.uint64)
+    top16 = m >> np.uint64(w - 16)
+    diff = int(np.bitwise_and.reduce(top16) ^ np.bitwise_or.reduce(top16)) & 0xFFFF
+    lead = 16 - diff.bit_length()                       # clz(diff) - 16 for a 16-bit diff; 16 when the prefixes agree
+    ws = min(8, lead)
+    out["win_shift"] = ws
+    out["win_top"] = int(np.bitwise_or.reduce(top16)) >> (16 - ws) if ws else 0
+    b = ((m >> np.uint64(w - 16 - ws)) & np.uint64(0xFFFF)).astype(np.int64)
+    limit = 12 + 4 * LOCAL_TILE[kb] * PRESAMPLE_KEYS // n
+    assert limit <= 64
+    # (8-bit counters: one that reaches the limit raises the flag before it could carry, and a carry only ever raises a
+    # neighbour's count while the flag is already up — the flag needs no model of the wrap)
+    out["gross_skew"] = int(np.bincount(b, minlength=65536).max() >= limit)
+    hits = np.bincount(b >> 8, minlength=256)           # (32-bit counters)
+    out["top_skew"] = int(hits.max() >= PRESAMPLE_TOP_LIMIT)
+    est = n * hits.astype(object) // (PRESAMPLE_KEYS * 256)
+    if kb == 4:
+        mult = np.bincount((m & np.uint64(0xFFFF)).astype(np.int64), minlength=65536)
+        dups = int((mult[mult > 0] - 1).sum())
+        # a low half seen 256 times wraps its 8-bit counter (one hit in 256 then counts as new, a carry may make a neighbour's
+        # first hit count as seen): at most 32 either way over 8 192 samples — the restatement stays away from that margin
+        assert mult.max() < 256 or abs(dups - PRESAMPLE_DUP_LIMIT) > 64, "low halves wrap next to the limit: not modelled"
+        out["low_dups"] = int(dups >= PRESAMPLE_DUP_LIMIT)
+        big4 = t["count_sort"] and t["expand"] and t["predict"]
+        giant_min = GIANT_MIN if big4 else 0
+        giant_max = GIANT_MAX if big4 and t["giants"] and n < (1 << 30) else 0
+        looks_giant = sum(1 for h, e in zip(hits, est) if giant_min and h >= 8 and e >= giant_min + giant_min // 4)
+        out["predict_lsd"] = int(bool(giant_min) and looks_giant * 256 > giant_max + giant_max // 2)
+    else:
+        cap = LOCAL_TILE[8] if t["predict"] else 0
+        out["predict_lsd"] = int(any(cap and h >= 16 and e > 2 * cap for h, e in zip(hits, est)))
+    return out
+
+
+def predicted_route(verdict, n, key_bytes, t, atomic_ok, giants16, bmax16):
+    """The route the code must end on (run_pipeline's kernels, each looking at the plan: msd_scatter_kernel :1856-1864,
+    msd_finish_kernel :949-960, hist16_kernel :578-585, route_kernel :777-783 and :846).  `atomic_ok`: would the atomic route's own
+    checks pass (every key inside the window, no area or slot over its room)?  None when the test cannot tell.  `giants16`,
+    `bmax16`: how many 16-bit prefixes of the mapped keys hold 65 536 keys and more, and the largest prefix count.  Returns None
+    where the inputs leave it open."""
+    try_atomic, try_hybrid = routes_tried(n, key_bytes, t)
+    flagged = verdict["gross_skew"] or verdict["top_skew"] or verdict["predict_lsd"]
+    if try_atomic and not flagged:
+        if atomic_ok is None:
+            return None
+        if atomic_ok:
+            return "atomic"
+    if not try_hybrid or verdict["predict_lsd"]:
+        return "lsd"
+    giants = key_bytes == 4 and t["giants"] and t["count_sort"] and t["expand"] and n < (1 << 30)
+    if giants:
+        return "hybrid" if giants16 <= GIANT_MAX else "lsd"
+    cap = EXPAND_MAX if key_bytes == 4 and t["count_sort"] and t["expand"] else LOCAL_TILE[key_bytes]
+    return "hybrid" if bmax16 <= cap and not verdict["gross_skew"] else "lsd"
+
+
+def pass_a_geometry(key_bytes):
+    """pass A of the atomic route (msd_scatter_kernel as atomic_stage launches it, :5152): keys per thread, the keys one wave
+    covers (index order inside a tile is wave, round, lane) and the tile"""
+    kpt = MSD_KPT[key_bytes]
+    return {"kpt": kpt, "span": 64 * kpt, "tile": MSD_WAVES * 64 * kpt}
+
+
+# Builders.  They work on torch tensors (any device) that hold MAPPED keys as the bits of int32 / int64 — the space in which the
+# window and the prefixes live — and `unmapped_bits` turns such a tensor into the bit patterns of the key type.
+
+def _signed(x, w):
+    x &= (1 << w) - 1
+    return x - (1 << w) if x >> (w - 1) else x
+
+
+def rand_mapped(torch, n, w, gen, device):
+    """uniform random bits (one pattern of 2^w never occurs: randint's upper bound is exclusive)"""
+    it = torch.int32 if w == 32 else torch.int64
+    info = torch.iinfo(it)
+    return torch.randint(info.min, info.max, (n,), dtype=it, device=device, generator=gen)
+
+
+def set_top(m, w, nbits, value):
+    """m with its top `nbits` bits replaced by `value` (a Python int or a tensor of m's type)"""
+    if nbits == 0:
+        return m
+    low = m & _signed((1 << (w - nbits)) - 1, w)
+    if isinstance(value, int):
+        return low | _signed(value << (w - nbits), w)
+    return low | (value << (w - nbits))
+
+
+def top_bits(m, w, nbits):
+    """the top `nbits` bits of every key, as non-negative int64"""
+    return (m.long() >> (w - nbits)) & ((1 << nbits) - 1)
+
+
+def unmapped_bits(torch, m, name):
+    """the bits of the keys of type `name` whose mapped images are the bits `m` (torch twin of unmapped)"""
+    kind = np.dtype(name).kind
+    mn = torch.iinfo(m.dtype).min
+    if kind == "u":
+        return m.clone()
+    if kind == "i":
+        return m ^ mn
+    return torch.where(m < 0, m ^ mn, ~m)
+
+
+def sample_index(torch, n, device):
+    return torch.arange(PRESAMPLE_KEYS, device=device, dtype=torch.int64) * (n // PRESAMPLE_KEYS)
+
+
+def plant(keys, positions, values):
+    """keys with `values` at `positions` (in place; returns keys)"""
+    keys[positions] = values
+    return keys
+
+
+def with_sample(torch, rest, sampled):
+    """`rest` with the 8 192 keys `sampled` at the sample's positions"""
+    return plant(rest, sample_index(torch, rest.numel(), rest.device), sampled)
+
+
+def not_sampled(n, positions):
+    """the positions, checked: none of them is one the sample reads"""
+    step = n // PRESAMPLE_KEYS
+    for p in positions:
+        assert 0 <= p < n and (p % step != 0 or p // step >= PRESAMPLE_KEYS), (n, p)
+    return list(positions)
+
+
+def window_pattern(kind, d):
+    """the shared top `d` bits: all zeros, all ones, or mixed (0b1011010010110100 cut to d bits)"""
+    return {"zeros": 0, "ones": (1 << d) - 1, "mixed": 0xB4B4 >> (16 - d)}[kind] if d else 0
+
+
+def window_keys(torch, n, w, d, pattern, gen, device):
+    """random mapped keys that share exactly their top d bits (value `pattern`): the bit below takes both values among the
+    SAMPLED keys (d < 16)"""
+    m = set_top(rand_mapped(torch, n, w, gen, device), w, d, pattern)
+    if d < 16:
+        pos = sample_index(torch, n, device)[:2]
+        two = set_top(m[pos], w, d + 1, torch.tensor([pattern << 1, (pattern << 1) | 1], device=device, dtype=m.dtype))
+        plant(m, pos, two)
+    return m
+
+
+def spread_sample(torch, w, gen, device):
+    """8 192 mapped keys a truthful uniform slice could show: the 16-bit prefixes 8 k (distinct, 32 on every top byte), random
+    bits below"""
+    m = rand_mapped(torch, PRESAMPLE_KEYS, w, gen, device)
+    return set_top(m, w, 16, torch.arange(PRESAMPLE_KEYS, device=device, dtype=m.dtype) * 8)
+
+
+def gross_sample(torch, w, hits, gen, device, prefix=0xF008):
+    """spread_sample with `hits` keys on one 16-bit prefix: its own holder and one key each from the top bytes 0, 1, ... (so
+    the prefix's top byte gains hits - 1 < 64 - 32)"""
+    assert prefix % 8 == 0 and 1 <= hits <= 30 < (prefix >> 8)
+    m = spread_sample(torch, w, gen, device)
+    idx = torch.arange(hits - 1, device=device) * 32 + 1      # sample 32 j + 1 holds prefix 8 (32 j + 1): top byte j
+    m[idx] = set_top(m[idx], w, 16, prefix)
+    return m
+
+
+def top_sample(torch, w, hits, gen, device, byte=0x47):
+    """spread_sample with `hits` keys on one top byte, on distinct prefixes (no prefix is hit twice)"""
+    assert 32 <= hits <= 32 + 224
+    m = spread_sample(torch, w, gen, device)
+    extra = hits - 32
+    donors = [j for j in range(256) if j != byte][:extra]
+    idx = torch.tensor([32 * j + 1 for j in donors], device=device, dtype=torch.int64)
+    pref = torch.tensor([(byte << 8) | (8 * (k % 32) + 1 + k // 32) for k in range(extra)], device=device, dtype=m.dtype)
+    if extra:
+        m[idx] = set_top(m[idx], w, 16, pref)
+    return m
+
+
+def dups_sample(torch, dups, gen, device):
+    """spread_sample (4-byte keys) whose low halves take 8 192 - dups distinct values, each at most a few times"""
+    m = spread_sample(torch, 32, gen, device)
+    distinct = PRESAMPLE_KEYS - dups
+    assert 64 <= distinct <= PRESAMPLE_KEYS and 20 * distinct + 3 < 65536
+    low = (torch.arange(PRESAMPLE_KEYS, device=device, dtype=torch.int64) % distinct) * 20 + 3
+    return (m & _signed(0xFFFF0000, 32)) | low.to(m.dtype)
+
+
+def bytes_sample(torch, w, nbytes, hits, gen, device):
+    """8 192 mapped keys with `hits` on each of the top bytes 16, 24, ... (`nbytes` of them), the rest dealt round over all
+    other top bytes; prefixes inside a byte as even as they can be"""
+    heavy = nbytes * hits
+    assert heavy <= PRESAMPLE_KEYS and nbytes <= 30
+    m = rand_mapped(torch, PRESAMPLE_KEYS, w, gen, device)
+    k = torch.arange(PRESAMPLE_KEYS, device=device, dtype=torch.int64)
+    hp = ((16 + 8 * (k // hits)) << 8) | ((k % hits) * 256 // hits)
+    others = torch.tensor([b for b in range(256) if not (b % 8 == 0 and 16 <= b < 16 + 8 * nbytes)], device=device, dtype=torch.int64)
+    rest = (k - heavy).clamp(min=0)
+    op = (others[rest % others.numel()] << 8) | ((rest // others.numel()) * 8 % 256 + 3)
+    return set_top(m, w, 16, torch.where(k < heavy, hp, op).to(m.dtype))
+
+
+def bytes_population(torch, m, w, nbytes, hits):
+    """m (in place) with the share hits / 8 192 of its keys, spread evenly, on each of the top bytes bytes_sample makes heavy"""
+    i = torch.arange(m.numel(), device=m.device, dtype=torch.int64) % PRESAMPLE_KEYS
+    on = i < nbytes * hits
+    byte = (16 + 8 * (i // hits)).to(m.dtype)
+    m[on] = set_top(m[on], w, 8, byte[on])
+    return m
+
+
+def increasing_keys(torch, n, w, gen, device, below_bits=None, dense_from=None):
+    """strictly increasing mapped keys: key i = i * K + r_i with r_i random below K = floor(range / n) — over the whole
+    range, below 2^below_bits, or (dense_from) the ids dense_from + i"""
+    it = torch.int32 if w == 32 else torch.int64
+    i = torch.arange(n, device=device, dtype=torch.int64)
+    if dense_from is not None:
+        v = i + dense_from
+    else:
+        bits = below_bits or w
+        k = (1 << bits) // n
+        assert k >= 2
+        if bits == 64:      # i * K + r - 2^63 stays inside int64; adding 2^63 back is a flip of the top bit
+            v = (i * k + torch.randint(0, k, (n,), device=device, generator=gen) + torch.iinfo(torch.int64).min) ^ torch.iinfo(torch.int64).min
+        else:
+            v = i * k + torch.randint(0, k, (n,), device=device, generator=gen)
+    if w == 32:
+        v = torch.where(v >= (1 << 31), v - (1 << 32), v).to(it)
+    return v
+
+
+def swap_spots(n, key_bytes):
+    """where pass A's own per-key checks have their borders: lanes, a wave's span, the tile, the last (partial) tile"""
+    g = pass_a_geometry(key_bytes)
+    span, tile = g["span"], g["tile"]
+    mid, last = tile * (n // tile // 2), tile * (n // tile)
+    spots = [0, 62, 63, 64, span - 2, span - 1, span, tile - 2, tile - 1, tile, tile + span - 1, mid - 2, mid - 1, mid, mid + 1,
+             last - 2, last - 1, last, n - 3, n - 2]
+    if last + 1 < n - 1:
+        spots.append(last + 1)
+    assert all(0 <= s < n - 1 for s in spots)
+    return sorted(set(spots))
+
+
+def stray_positions(n, key_bytes):
+    """where a key outside the window hides: the first tile, both sides of its border, the middle, the last full tile's last
+    key, the partial tile's last key, and the first tile of each of the eight XCDs (blocks 0..7) — none of them sampled"""
+    tile = pass_a_geometry(key_bytes)["tile"]
+    assert n % tile != 0
+    pos = [1, tile - 1, tile, n // 2 + 1, tile * (n // tile) - 1, n - 1] + [b * tile + 777 for b in range(8)]
+    return not_sampled(n, pos)

@@ -121,6 +121,7 @@ def test_skewed_full_size_inputs(gpu):
                 prof = gpu.profile_run(-1, 4)
                 gpu.set_profiling(False)
                 assert gpu.last_route() == route, (mode, name)
+                assert gpu.last_sample()["gross_skew"] == (1 if name == "bimodal" else 0), (mode, name, gpu.last_sample())   # what the sample saw, said outright
                 assert (prof[first] > 0.2) == first_runs, (mode, name, prof[first])   # >= 0.4 ms when it reads the slice, microseconds when it returns
                 assert int(keys.sum()) == int(inp.sum())
                 assert _is_sorted(torch, keys ^ torch.iinfo(torch.int32).min), (mode, name)
@@ -173,6 +174,14 @@ def test_keys_that_share_their_top_bits_take_the_atomic_route_through_a_lowered_
         assert (route == want) if want else (route != "atomic"), (name, route)
         assert int(keys.sum()) == s1 and int((keys ^ (keys >> 11)).sum()) == s2, name
         assert _is_sorted(torch, _mapped(torch, keys, np.dtype(name).kind)), name
+        if want is None:        # the one full-size input whose sample lies (window 2, a key outside it): element for element as well
+            sample = gpu.last_sample()
+            assert (sample["win_shift"], sample["win_top"]) == (2, 0), sample
+            exp = torch.sort(_mapped(torch, src, np.dtype(name).kind)).values
+            got = _mapped(torch, keys, np.dtype(name).kind)
+            for s in range(0, n, 1 << 27):   # (chunks: no n-sized temporaries of the comparison)
+                assert bool(torch.equal(exp[s:s + (1 << 27)], got[s:s + (1 << 27)])), (name, s)
+            del exp, got
         del keys
 
 

@@ -91,7 +91,7 @@ while time.time() - t0 < budget:
     runs += 1
     if not ok:
         fails += 1
-        print(f"FAIL {name} n={n} kind={kind} split={split} fast={fast} mode={mode} route={rdst_amd.last_route()}", flush=True)
+        print(f"FAIL {name} n={n} kind={kind} split={split} fast={fast} mode={mode} route={rdst_amd.last_route()} sample={'/'.join(str(v) for v in rdst_amd.last_sample().values())}", flush=True)
     del src, keys, m, exp
 rs.set_tuning()
 rdst_amd.set_hybrid(True)
