@@ -5,6 +5,7 @@
 //
 //   rdst::radix_sort_unstable(v)                        RadixSort::radix_sort_unstable     src/radix_sort.rs:21-45
 //   rdst::radix_sort_unstable_by_field(v, &T::key)      the same on structs keyed by a field benches/struct_sort.rs:11-27
+//   rdst::sort_records_by(v, {RDST_FIELD(T, a, kind), ...})  `impl RadixKey for T` stated as a field table  src/radix_key.rs, examples/impl_radix_key.rs:32-56
 //   rdst::radix_sort_builder(v).with_*().sort()         RadixSortBuilder                   src/radix_sort_builder.rs:8-158
 //   rdst::RadixKey<T>::LEVELS / kind                    RadixKey for the built-in types    src/radix_key_impl.rs:1-185
 //   rdst::tuner::{Tuner, TuningParams, Algorithm, ...}  pub mod tuner                      src/tuner.rs:1-40, src/tuners/*.rs
@@ -19,6 +20,7 @@
 
 #include <cstddef>
 #include <cstdint>
+#include <initializer_list>
 #include <stdexcept>
 #include <string>
 #include <type_traits>
@@ -173,6 +175,25 @@ void radix_sort_unstable_by_field(T* data, std::size_t len, KeyT T::*field) {
 }
 template <typename T, typename KeyT>
 void radix_sort_unstable_by_field(std::vector<T>& v, KeyT T::*field) { radix_sort_unstable_by_field(v.data(), v.size(), field); }
+
+// A slice of structs ordered by a described key: what `impl RadixKey for T` states with LEVELS and get_level
+// (src/radix_key.rs; examples/impl_radix_key.rs:32-56), as a table of fields, most significant first — several fields,
+// any built-in width (u8..i128, f32, f64, [u8; N]), any offset (packed structs), descending fields, chosen bytes.  Rows
+// with equal keys keep their order (rdst_hip_sort_records_by_fields).
+//     struct Event { std::uint16_t tenant; std::int64_t ts; ... };
+//     rdst::sort_records_by(v, {RDST_FIELD(Event, tenant, RDST_KEY_UNSIGNED), RDST_FIELD(Event, ts, RDST_KEY_SIGNED)});
+#define RDST_FIELD(T, member, kind) \
+    rdst_key_field { static_cast<std::uint32_t>(offsetof(T, member)), static_cast<std::uint32_t>(sizeof(static_cast<T*>(nullptr)->member)), static_cast<std::uint32_t>(kind), 0u }
+#define RDST_FIELD_DESC(T, member, kind) \
+    rdst_key_field { static_cast<std::uint32_t>(offsetof(T, member)), static_cast<std::uint32_t>(sizeof(static_cast<T*>(nullptr)->member)), static_cast<std::uint32_t>(kind), RDST_FIELD_DESCENDING }
+template <typename T>
+void sort_records_by(T* data, std::size_t n, std::initializer_list<rdst_key_field> fields) {
+    static_assert(std::is_trivially_copyable<T>::value, "rows are moved as bytes");
+    const int rc = rdst_hip_sort_records_by_fields(data, n, sizeof(T), fields.begin(), static_cast<std::uint32_t>(fields.size()), nullptr);
+    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+}
+template <typename T>
+void sort_records_by(std::vector<T>& v, std::initializer_list<rdst_key_field> fields) { sort_records_by(v.data(), v.size(), fields); }
 
 }  // namespace rdst
 #endif  // RDST_HPP

@@ -152,7 +152,9 @@ int rdst_hip_sort_device(void* dev_keys, void* dev_tmp, uint64_t len, uint32_t e
  * (key, row index) pairs are sorted there, the rows gathered and copied back.  Rows with equal
  * keys keep their input order (rdst promises none).  Blocking; on failure the slice is untouched.
  * kind == RDST_KEY_BYTES_BE: the key is a [u8; N] field, key_bytes = N in 1..RDST_BYTES_MAX_N, at any
- * offset in rows of any size (no alignment rule), len < 2^32; ordered as rdst_hip_sort_bytes_device orders rows. */
+ * offset in rows of any size (no alignment rule), len < 2^32; ordered as rdst_hip_sort_bytes_device orders rows.
+ * Keys of several fields, of other widths (u8, u16, i128), of chosen bytes or at unaligned offsets:
+ * rdst_hip_sort_records_by_fields below. */
 int rdst_hip_sort_records(void* host_records, uint64_t len, uint32_t record_bytes, uint32_t key_offset,
                           uint32_t key_bytes, rdst_key_kind kind, const rdst_hip_opts* opts);
 
@@ -182,6 +184,57 @@ int rdst_hip_sort_pairs_device(void* dev_keys, void* dev_vals, void* dev_tmp_key
 int rdst_hip_sort_bytes_device(void* dev_rows, uint64_t len, uint32_t n_bytes,
                                void* dev_scratch, uint64_t scratch_bytes, void* stream);
 uint64_t rdst_hip_sort_bytes_scratch_bytes(uint64_t len, uint32_t n_bytes);   /* 0 for n_bytes outside 1..RDST_BYTES_MAX_N */
+
+/* ---- records ordered by a described key ------------------------------------------------------
+ * `impl RadixKey for MyStruct` as data (src/radix_key.rs: `const LEVELS` and `get_level`; examples/impl_radix_key.rs:32-56
+ * sorts one four-byte struct by all of its bytes, by its even bytes and by its odd bytes).  A key is a table of fields,
+ * fields[0] the most significant.  For a record r the mapped key string K(r) is the concatenation, in field order, of every
+ * field's mapped value written big-endian: integers are read little-endian from the record at `offset` (no alignment
+ * rule), UNSIGNED values are taken as they are, SIGNED values are ^ MIN, FLOAT values get rdst's sign-magnitude flip
+ * (src/radix_key_impl.rs:162-185: negative -> every bit flipped, else ^ MIN), BYTES_BE bytes are taken as stored; a
+ * descending field has every byte of its mapped value complemented.  Records are ordered by K lexicographically and
+ * records with equal K keep their input order.  This is the RadixKey with LEVELS = L = the sum of the fields' widths
+ * and get_level(l) = K[L - 1 - l].  A one-byte UNSIGNED field at any offset is the raw level map: the example's "even
+ * bytes" key is { {1, 1, RDST_KEY_UNSIGNED, 0}, {3, 1, RDST_KEY_UNSIGNED, 0} }.  Fields may overlap.  L <= RDST_BYTES_MAX_N.
+ *
+ * Errors, all before any device work: n_fields == 0 -> RDST_ERR_ARG (LEVELS == 0 panics in rdst); n_fields >
+ * RDST_KEY_FIELDS_MAX, L > RDST_BYTES_MAX_N or a width not listed for the kind -> RDST_ERR_UNSUPPORTED; an unknown kind, an
+ * unknown flag bit, a null table or a field that ends past record_bytes -> RDST_ERR_ARG.  len <= 1 (with a valid
+ * description) is a no-op before any pointer check; len >= 2^32 -> RDST_ERR_UNSUPPORTED (row indices are u32). */
+#define RDST_FIELD_DESCENDING 1u      /* complement the field's mapped bytes */
+#define RDST_KEY_FIELDS_MAX   16u
+typedef struct {
+    uint32_t offset;  /* byte offset of the field inside the record; no alignment rule */
+    uint32_t bytes;   /* UNSIGNED/SIGNED: 1,2,4,8,16   FLOAT: 4,8   BYTES_BE: 1..RDST_BYTES_MAX_N */
+    uint32_t kind;    /* rdst_key_kind */
+    uint32_t flags;   /* RDST_FIELD_DESCENDING or 0; any other bit: RDST_ERR_ARG */
+} rdst_key_field;
+
+/* Host slice of `len` records of `record_bytes` bytes, sorted in place.  Blocking; on failure the slice is untouched.
+ * The rows travel to the device, pack_fields_kernel writes K, then: L <= 4 a (u32 key, u32 row) pair sort, L <= 8 a
+ * (u64 key, u32 row) pair sort, L > 8 the order core of the [u8; N > 16] route on the packed keys; the rows are gathered
+ * by the resulting order and copied back. */
+int rdst_hip_sort_records_by_fields(void* host_records, uint64_t len, uint32_t record_bytes,
+                                    const rdst_key_field* fields, uint32_t n_fields, const rdst_hip_opts* opts);
+
+/* The same on device-resident records, IN PLACE; the conventions are those of rdst_hip_sort_bytes_device: no alignment
+ * rule on dev_records, dev_scratch 256-byte aligned and at least rdst_hip_sort_records_by_fields_scratch_bytes(...) long
+ * (the key and index arrays, the packed keys when L > 8, and a staging copy of the rows for the in-place gather), kernel
+ * failures are reported by rdst_hip_device_status.  L <= 8: ASYNCHRONOUS on `stream`.  L > 8: BLOCKING, because the tie
+ * counts of every refinement round come to the host exactly as on the [u8; N > 16] route. */
+int rdst_hip_sort_records_by_fields_device(void* dev_records, uint64_t len, uint32_t record_bytes,
+                                           const rdst_key_field* fields, uint32_t n_fields,
+                                           void* dev_scratch, uint64_t scratch_bytes, void* stream);
+uint64_t rdst_hip_sort_records_by_fields_scratch_bytes(uint64_t len, uint32_t record_bytes,
+                                                       const rdst_key_field* fields, uint32_t n_fields);  /* 0 for an invalid description */
+
+/* Parity and timing hook: pack_fields_kernel alone.  dev_keys receives K for every record in the form the route sorts:
+ * L <= 4: len u32 keys, L <= 8: len u64 keys (K left-justified, zero-filled; aligned to their size), L > 8: len dense
+ * [u8; L] rows (4-byte aligned).  dev_rows (len x u32; may be NULL when L > 8) receives the row indices 0..len-1.
+ * Asynchronous on `stream`. */
+int rdst_hip_pack_fields_device(const void* dev_records, uint64_t len, uint32_t record_bytes,
+                                const rdst_key_field* fields, uint32_t n_fields,
+                                void* dev_keys, uint32_t* dev_rows, void* stream);
 
 /* Blocks until everything queued on `stream` by this library has finished and returns
  * RDST_ERR_DEVICE if any kernel raised the device error word since the last check.  The word is kept

@@ -14,6 +14,8 @@ LIB_PATH = os.environ.get("RDST_HIP_LIB") or os.path.join(_HERE, "librdst_hip.so
 RDST_KEY_UNSIGNED, RDST_KEY_SIGNED, RDST_KEY_FLOAT, RDST_KEY_BYTES_BE = 0, 1, 2, 3
 RDST_OK = 0
 RDST_BYTES_MAX_N = 4096  # longest [u8; N] key the device route takes (include/rdst_hip.h)
+RDST_FIELD_DESCENDING = 1  # rdst_key_field.flags: complement the field's mapped bytes
+RDST_KEY_FIELDS_MAX = 16   # fields in one key description
 
 # every symbol include/rdst_hip.h declares; tests check that the library exports all of them
 SYMBOLS = (
@@ -27,6 +29,10 @@ SYMBOLS = (
     "rdst_hip_sort_records",
     "rdst_hip_sort_bytes_device",
     "rdst_hip_sort_bytes_scratch_bytes",
+    "rdst_hip_sort_records_by_fields",
+    "rdst_hip_sort_records_by_fields_device",
+    "rdst_hip_sort_records_by_fields_scratch_bytes",
+    "rdst_hip_pack_fields_device",
     "rdst_hip_device_status",
     "rdst_hip_level_counts",
     "rdst_hip_all_level_counts",
@@ -70,6 +76,11 @@ class HipOptsC(ctypes.Structure):
     _fields_ = [("device", ctypes.c_int32), ("low_memory", ctypes.c_int32), ("reserved1", ctypes.c_uint64)]
 
 
+class KeyFieldC(ctypes.Structure):
+    """rdst_key_field: one field of a described key (offset, bytes, kind, flags)."""
+    _fields_ = [("offset", ctypes.c_uint32), ("bytes", ctypes.c_uint32), ("kind", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
+
+
 class RdstHipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"rdst_hip call failed with status {code}: {msg}")
@@ -105,6 +116,12 @@ def load():
     lib.rdst_hip_sort_bytes_device.argtypes = [vp, u64, u32, vp, u64, vp]
     lib.rdst_hip_sort_bytes_scratch_bytes.argtypes = [u64, u32]
     lib.rdst_hip_sort_bytes_scratch_bytes.restype = u64
+    kfp = ctypes.POINTER(KeyFieldC)
+    lib.rdst_hip_sort_records_by_fields.argtypes = [vp, u64, u32, kfp, u32, ctypes.POINTER(HipOptsC)]
+    lib.rdst_hip_sort_records_by_fields_device.argtypes = [vp, u64, u32, kfp, u32, vp, u64, vp]
+    lib.rdst_hip_sort_records_by_fields_scratch_bytes.argtypes = [u64, u32, kfp, u32]
+    lib.rdst_hip_sort_records_by_fields_scratch_bytes.restype = u64
+    lib.rdst_hip_pack_fields_device.argtypes = [vp, u64, u32, kfp, u32, vp, vp, vp]
     lib.rdst_hip_device_status.argtypes = [vp]
     lib.rdst_hip_level_counts.argtypes = [vp, u64, u32, ci, u32, u64p, u8p, u8p, u8p, vp]
     lib.rdst_hip_all_level_counts.argtypes = [vp, u64, u32, ci, u32, u64p, vp]
@@ -131,7 +148,8 @@ def load():
     lib.rdst_hip_stream_fill.argtypes = [vp, u64, vp]
     lib.rdst_hip_last_error.restype = ctypes.c_char_p
     for name in SYMBOLS:
-        if name not in ("rdst_hip_workspace_bytes", "rdst_hip_sort_bytes_scratch_bytes", "rdst_hip_last_error"):
+        if name not in ("rdst_hip_workspace_bytes", "rdst_hip_sort_bytes_scratch_bytes", "rdst_hip_sort_records_by_fields_scratch_bytes",
+                        "rdst_hip_last_error"):
             getattr(lib, name).restype = ctypes.c_int
     _lib = lib
     return lib

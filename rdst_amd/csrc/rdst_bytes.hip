@@ -18,10 +18,15 @@
 //
 // Stability: the prefix sort is stable on row indices, every later sort is stable on positions that are in row order
 // within a run, and the comparison kernel breaks ties on the row index — equal keys keep their input order.
+//
+// The second half of the file is the records route for keys described by a field table (rdst_key_field): one kernel
+// that packs the mapped key bytes, then the pair sort or the core above, then the same gather.
 
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+
+#include <type_traits>
 
 #include "rdst_hip.h"
 #include "rdst_internal.h"
@@ -568,6 +573,277 @@ int rdst_hip_sort_bytes_device(void* dev_rows, uint64_t len, uint32_t n_bytes, v
     if (rc) return rc;
     BYTES_TRY(hipMemcpyAsync(rows, staged, len * n_bytes, hipMemcpyDeviceToDevice, s));
     return RDST_OK;
+}
+
+}  // extern "C"
+
+// ------------------------------------------------------------------------------------------------------------------------
+// Records ordered by a described key: rdst_key_field tables (include/rdst_hip.h)
+// ------------------------------------------------------------------------------------------------------------------------
+// The description states a RadixKey with LEVELS = L = sum of the fields' widths and get_level(l) = K[L - 1 - l], K the
+// concatenation of the fields' mapped values, big-endian (src/radix_key.rs; examples/impl_radix_key.rs:32-56).
+// pack_fields_kernel turns records into K; everything after it is the code above: L <= 8 is one stable (key, row) pair
+// sort, L > 8 hands dense [u8; L] rows to bytes_order; bytes_gather moves the records.
+
+namespace {
+
+constexpr uint32_t PACK_TILE = 256;         // records per workgroup trip: four waves of 64 consecutive records
+constexpr uint32_t PACK_LDS_BYTES = 32768;  // a tile of records up to this size is staged through LDS
+
+struct FieldTable {  // travels by value in the kernel arguments
+    rdst_key_field f[RDST_KEY_FIELDS_MAX];
+    uint32_t n;
+};
+
+// byte j (0 = most significant) of a field's mapped value: integers and floats are stored little-endian, byte strings as
+// they are; signed: ^ MIN; float: negative -> every bit flipped, else ^ MIN (src/radix_key_impl.rs:162-185); descending:
+// every bit flipped
+__device__ __forceinline__ uint32_t field_flip(const uint8_t* rec, const rdst_key_field& f, uint32_t& top) {
+    uint32_t all = (f.flags & RDST_FIELD_DESCENDING) ? 0xFFu : 0u;
+    top = 0;
+    if (f.kind == RDST_KEY_SIGNED) top = 0x80u;
+    else if (f.kind == RDST_KEY_FLOAT) {
+        if (rec[f.offset + f.bytes - 1] & 0x80u) all ^= 0xFFu;
+        else top = 0x80u;
+    }
+    return all;
+}
+__device__ __forceinline__ uint32_t field_byte(const uint8_t* rec, const rdst_key_field& f, uint32_t j, uint32_t all, uint32_t top) {
+    const uint32_t src = f.kind == RDST_KEY_BYTES_BE ? f.offset + j : f.offset + f.bytes - 1 - j;
+    return rec[src] ^ all ^ (j == 0 ? top : 0u);
+}
+
+// MODE 0: u32 key (L <= 4), 1: u64 key (L <= 8), both left-justified and zero-filled, plus the row index; 2: dense
+// [u8; L] rows (out must be 4-byte aligned).  STAGED: the tile's records, one contiguous span, come to LDS in 16-byte
+// coalesced loads (bytes before the span's first and after its last are never read) and the fields are picked out of
+// LDS; otherwise (a tile beyond PACK_LDS_BYTES) the field bytes are read from memory directly.
+template <int MODE, bool STAGED>
+__global__ __launch_bounds__(256) void pack_fields_kernel(const uint8_t* __restrict__ rows, uint64_t n, uint32_t R, FieldTable d,
+                                                          void* __restrict__ out, uint32_t* __restrict__ idx) {
+    __shared__ rdst_key_field s_f[RDST_KEY_FIELDS_MAX];
+    __shared__ uint4 s_tile[STAGED ? PACK_LDS_BYTES / 16 + 1 : 1];
+    if (threadIdx.x == 0) {
+#pragma unroll
+        for (uint32_t k = 0; k < RDST_KEY_FIELDS_MAX; ++k) s_f[k] = d.f[k];
+    }
+    __syncthreads();
+    const uint32_t nf = d.n, tid = threadIdx.x;
+    uint32_t L = 0;
+    for (uint32_t k = 0; k < nf; ++k) L += s_f[k].bytes;
+    const uint64_t tiles = (n + PACK_TILE - 1) / PACK_TILE;
+    for (uint64_t t = blockIdx.x; t < tiles; t += gridDim.x) {
+        const uint64_t first = t * PACK_TILE;
+        const uint32_t cnt = n - first < PACK_TILE ? (uint32_t)(n - first) : PACK_TILE;
+        const uint8_t* base = rows + first * R;  // the tile's first record
+        if constexpr (STAGED) {
+            const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(base) & 15);
+            const uint8_t* g0 = base - mis;      // 16-byte aligned; [mis, span) is the tile
+            const uint32_t span = mis + cnt * R;
+            uint8_t* lds = reinterpret_cast<uint8_t*>(s_tile);
+            for (uint32_t c = tid * 16; c < span; c += 256 * 16) {
+                if (c >= mis && c + 16 <= span) s_tile[c / 16] = *reinterpret_cast<const uint4*>(g0 + c);
+                else
+                    for (uint32_t q = c < mis ? mis : c; q < c + 16 && q < span; ++q) lds[q] = g0[q];
+            }
+            __syncthreads();
+            base = lds + mis;
+        }
+        if constexpr (MODE == 2) {
+            const uint32_t total = cnt * L;  // at most 256 x 4096 bytes
+            uint8_t* o = static_cast<uint8_t*>(out) + first * L;
+            for (uint32_t b0 = tid * 4; b0 < total; b0 += 256 * 4) {
+                const uint32_t nb = total - b0 < 4 ? total - b0 : 4;
+                uint32_t r = b0 / L, p = b0 - r * L, k = 0, at = 0, word = 0;
+                while (p >= at + s_f[k].bytes) at += s_f[k++].bytes;  // p < L: ends inside the table
+                for (uint32_t q = 0; q < nb; ++q) {
+                    const uint8_t* rec = base + (size_t)r * R;
+                    uint32_t top;
+                    const uint32_t all = field_flip(rec, s_f[k], top);
+                    word |= field_byte(rec, s_f[k], p - at, all, top) << (8 * q);
+                    if (++p == at + s_f[k].bytes) at += s_f[k++].bytes;
+                    if (p == L) { p = 0; k = 0; at = 0; ++r; }
+                }
+                if (nb == 4) *reinterpret_cast<uint32_t*>(o + b0) = word;
+                else
+                    for (uint32_t q = 0; q < nb; ++q) o[b0 + q] = (uint8_t)(word >> (8 * q));
+            }
+        } else if (tid < cnt) {
+            using KT = typename std::conditional<MODE == 0, uint32_t, uint64_t>::type;
+            const uint8_t* rec = base + (size_t)tid * R;
+            uint64_t key = 0;
+            for (uint32_t k = 0; k < nf; ++k) {
+                const rdst_key_field f = s_f[k];
+                uint32_t top;
+                const uint32_t all = field_flip(rec, f, top);
+                for (uint32_t j = 0; j < f.bytes; ++j) key = (key << 8) | field_byte(rec, f, j, all, top);
+            }
+            static_cast<KT*>(out)[first + tid] = (KT)(key << (8 * (sizeof(KT) - L)));
+            idx[first + tid] = (uint32_t)(first + tid);
+        }
+        if constexpr (STAGED) __syncthreads();  // the next trip overwrites the tile
+    }
+}
+
+// The description's rules (rdst_hip.h); *L_out = the key's length in bytes.
+int check_fields(uint32_t record_bytes, const rdst_key_field* fields, uint32_t n_fields, uint32_t* L_out) {
+    if (n_fields == 0) return set_error(RDST_ERR_ARG, "a key needs at least one field (RadixKey::LEVELS == 0 panics in rdst)");
+    if (n_fields > RDST_KEY_FIELDS_MAX) return set_error(RDST_ERR_UNSUPPORTED, "key descriptions are built for at most RDST_KEY_FIELDS_MAX fields");
+    if (fields == nullptr) return set_error(RDST_ERR_ARG, "null field table");
+    uint64_t L = 0;
+    for (uint32_t k = 0; k < n_fields; ++k) {
+        const rdst_key_field& f = fields[k];
+        if (f.kind > RDST_KEY_BYTES_BE) return set_error(RDST_ERR_ARG, "unknown key kind in a key field");
+        if (f.flags & ~RDST_FIELD_DESCENDING) return set_error(RDST_ERR_ARG, "unknown flag bit in a key field");
+        const uint32_t b = f.bytes;
+        const bool pow2 = b == 1 || b == 2 || b == 4 || b == 8 || b == 16;
+        const bool ok = f.kind == RDST_KEY_BYTES_BE ? (b >= 1 && b <= RDST_BYTES_MAX_N) : (f.kind == RDST_KEY_FLOAT ? (b == 4 || b == 8) : pow2);
+        if (!ok)
+            return set_error(RDST_ERR_UNSUPPORTED, "key field width not built for its kind (integers: 1, 2, 4, 8, 16; floats: 4, 8; byte strings: 1..RDST_BYTES_MAX_N)");
+        if ((uint64_t)f.offset + b > record_bytes) return set_error(RDST_ERR_ARG, "key field outside the record");
+        L += b;
+    }
+    if (L > RDST_BYTES_MAX_N) return set_error(RDST_ERR_UNSUPPORTED, "described keys are built for at most RDST_BYTES_MAX_N bytes in all");
+    *L_out = (uint32_t)L;
+    return RDST_OK;
+}
+
+// Scratch of the records route: the key / index arrays (L <= 8) or the order core's arrays and the packed keys (L > 8),
+// then the staging copy of the rows.
+struct FieldsLayout {
+    uint64_t keys, keys_tmp, idx, idx_tmp, packed, staged, total;
+};
+FieldsLayout make_fields_layout(uint64_t n, uint32_t R, uint32_t L) {
+    FieldsLayout F{};
+    uint64_t o = 0;
+    auto take = [&](uint64_t bytes) { const uint64_t at = o; o += align256(bytes); return at; };
+    if (L <= 8) {
+        const uint32_t kb = L <= 4 ? 4 : 8;
+        F.keys = take(n * kb);
+        F.keys_tmp = take(n * kb);
+        F.idx = take(n * 4);
+        F.idx_tmp = take(n * 4);
+    } else {
+        const Layout C = make_layout(n);
+        F.idx = C.idx;
+        (void)take(C.total);
+        F.packed = take(n * L);
+    }
+    F.staged = take(n * R);
+    F.total = o;
+    return F;
+}
+
+int launch_pack(const uint8_t* rows, uint64_t n, uint32_t R, const FieldTable& d, uint32_t L, void* out, uint32_t* idx, hipStream_t s) {
+    uint64_t blocks = (n + PACK_TILE - 1) / PACK_TILE;
+    if (blocks > GRID_CAP) blocks = GRID_CAP;
+    const bool staged = (uint64_t)PACK_TILE * R <= PACK_LDS_BYTES;
+    auto go = [&](auto kernel) { return launch("pack_fields_kernel", kernel, dim3((uint32_t)blocks), dim3(256), 0, s, rows, n, R, d, out, idx); };
+    if (L <= 4) return staged ? go(pack_fields_kernel<0, true>) : go(pack_fields_kernel<0, false>);
+    if (L <= 8) return staged ? go(pack_fields_kernel<1, true>) : go(pack_fields_kernel<1, false>);
+    return staged ? go(pack_fields_kernel<2, true>) : go(pack_fields_kernel<2, false>);
+}
+
+FieldTable make_table(const rdst_key_field* fields, uint32_t n_fields) {
+    FieldTable d{};
+    for (uint32_t k = 0; k < n_fields; ++k) d.f[k] = fields[k];
+    d.n = n_fields;
+    return d;
+}
+
+// Packs, orders and gathers into the scratch's staging area; `rows` is only read.  Asynchronous for L <= 8.
+int fields_sort_staged(const uint8_t* rows, uint64_t n, uint32_t R, const rdst_key_field* fields, uint32_t n_fields, uint32_t L,
+                       char* scratch, hipStream_t s, uint32_t* err) {
+    const FieldsLayout F = make_fields_layout(n, R, L);
+    const FieldTable d = make_table(fields, n_fields);
+    uint32_t* idx = reinterpret_cast<uint32_t*>(scratch + F.idx);
+    int rc;
+    if (L <= 8) {
+        const uint32_t kb = L <= 4 ? 4 : 8;
+        if ((rc = launch_pack(rows, n, R, d, L, scratch + F.keys, idx, s))) return rc;
+        if ((rc = rdst_hip_sort_pairs_device(scratch + F.keys, idx, scratch + F.keys_tmp, scratch + F.idx_tmp, n, kb, RDST_KEY_UNSIGNED, kb, 4, s))) return rc;
+    } else {
+        uint8_t* packed = reinterpret_cast<uint8_t*>(scratch + F.packed);
+        if ((rc = launch_pack(rows, n, R, d, L, packed, nullptr, s))) return rc;
+        if ((rc = bytes_order(packed, n, L, 0, L, scratch, s, err))) return rc;
+    }
+    return bytes_gather(rows, reinterpret_cast<uint8_t*>(scratch + F.staged), idx, n, R, s, err);
+}
+
+}  // namespace
+
+extern "C" {
+
+uint64_t rdst_hip_sort_records_by_fields_scratch_bytes(uint64_t len, uint32_t record_bytes, const rdst_key_field* fields, uint32_t n_fields) {
+    uint32_t L = 0;
+    if (check_fields(record_bytes, fields, n_fields, &L)) return 0;
+    return make_fields_layout(len, record_bytes, L).total;
+}
+
+int rdst_hip_sort_records_by_fields_device(void* dev_records, uint64_t len, uint32_t record_bytes, const rdst_key_field* fields,
+                                           uint32_t n_fields, void* dev_scratch, uint64_t scratch_bytes, void* stream) {
+    uint32_t L = 0;
+    int rc = check_fields(record_bytes, fields, n_fields, &L);
+    if (rc) return rc;
+    if (len <= 1) return RDST_OK;  // radix_sort_builder.rs:151
+    if (dev_records == nullptr) return set_error(RDST_ERR_ARG, "null record pointer");
+    if (len >= (1ull << 32)) return set_error(RDST_ERR_UNSUPPORTED, "records with a described key are built for len < 2^32 (row indices are u32)");
+    if (dev_scratch == nullptr) return set_error(RDST_ERR_ARG, "null scratch pointer");
+    const FieldsLayout F = make_fields_layout(len, record_bytes, L);
+    if (scratch_bytes < F.total) return set_error(RDST_ERR_ARG, "scratch smaller than rdst_hip_sort_records_by_fields_scratch_bytes(...)");
+    if (reinterpret_cast<uintptr_t>(dev_scratch) % 256) return set_error(RDST_ERR_ALIGN, "scratch not 256-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint32_t* err = nullptr;
+    if ((rc = rdst_internal::device_error_word(&err))) return rc;
+    char* scratch = static_cast<char*>(dev_scratch);
+    if ((rc = fields_sort_staged(static_cast<const uint8_t*>(dev_records), len, record_bytes, fields, n_fields, L, scratch, s, err))) return rc;
+    BYTES_TRY(hipMemcpyAsync(dev_records, scratch + F.staged, len * record_bytes, hipMemcpyDeviceToDevice, s));
+    return RDST_OK;
+}
+
+int rdst_hip_sort_records_by_fields(void* host_records, uint64_t len, uint32_t record_bytes, const rdst_key_field* fields, uint32_t n_fields,
+                                    const rdst_hip_opts* opts) {
+    uint32_t L = 0;
+    int rc = check_fields(record_bytes, fields, n_fields, &L);
+    if (rc) return rc;
+    if (len <= 1) return RDST_OK;
+    if (host_records == nullptr) return set_error(RDST_ERR_ARG, "null record pointer");
+    if (len >= (1ull << 32)) return set_error(RDST_ERR_UNSUPPORTED, "records with a described key are built for len < 2^32 (row indices are u32)");
+    rdst_internal::HostJob job;
+    if (opts && opts->device >= 0) {
+        BYTES_TRY(hipGetDevice(&job.prev_dev));
+        BYTES_TRY(hipSetDevice(opts->device));
+    }
+    uint32_t* err = nullptr;
+    if ((rc = rdst_internal::device_error_word(&err))) return rc;
+    const uint64_t bytes = len * record_bytes;
+    const FieldsLayout F = make_fields_layout(len, record_bytes, L);
+    void *d_rows = nullptr, *d_scratch = nullptr;
+    BYTES_TRY(hipStreamCreate(&job.s));
+    BYTES_TRY(job.alloc(&d_rows, bytes));
+    BYTES_TRY(job.alloc(&d_scratch, F.total));
+    BYTES_TRY(hipMemcpyAsync(d_rows, host_records, bytes, hipMemcpyHostToDevice, job.s));
+    char* scratch = static_cast<char*>(d_scratch);
+    rc = fields_sort_staged(static_cast<const uint8_t*>(d_rows), len, record_bytes, fields, n_fields, L, scratch, job.s, err);
+    if (rc == RDST_OK) rc = rdst_hip_device_status(job.s);
+    if (rc != RDST_OK) return rc;
+    // the host buffer is written only now, after the device reported success: straight from the staging area
+    BYTES_TRY(hipMemcpyAsync(host_records, scratch + F.staged, bytes, hipMemcpyDeviceToHost, job.s));
+    BYTES_TRY(hipStreamSynchronize(job.s));
+    return RDST_OK;
+}
+
+int rdst_hip_pack_fields_device(const void* dev_records, uint64_t len, uint32_t record_bytes, const rdst_key_field* fields, uint32_t n_fields,
+                                void* dev_keys, uint32_t* dev_rows, void* stream) {
+    uint32_t L = 0;
+    int rc = check_fields(record_bytes, fields, n_fields, &L);
+    if (rc) return rc;
+    if (len == 0) return RDST_OK;
+    if (dev_records == nullptr || dev_keys == nullptr || (L <= 8 && dev_rows == nullptr)) return set_error(RDST_ERR_ARG, "null pointer");
+    if (len >= (1ull << 32)) return set_error(RDST_ERR_UNSUPPORTED, "records with a described key are built for len < 2^32 (row indices are u32)");
+    if (reinterpret_cast<uintptr_t>(dev_keys) % (L <= 4 || L > 8 ? 4 : 8) || reinterpret_cast<uintptr_t>(dev_rows) % 4)
+        return set_error(RDST_ERR_ALIGN, "key or row output not aligned");
+    return launch_pack(static_cast<const uint8_t*>(dev_records), len, record_bytes, make_table(fields, n_fields), L, dev_keys, dev_rows,
+                       static_cast<hipStream_t>(stream));
 }
 
 }  // extern "C"

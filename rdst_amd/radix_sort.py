@@ -254,17 +254,114 @@ def sort_host_array(arr, device=-1, key=None):
     _lib.check(lib.rdst_hip_sort(ctypes.c_void_p(arr.ctypes.data), arr.nbytes // nbytes, nbytes, kind, levels, ctypes.byref(opts)))
 
 
+class KeyField:
+    """One field of a described key (``rdst_key_field``, include/rdst_hip.h): ``bytes`` bytes at ``offset`` inside the
+    record, mapped as ``kind`` (``"unsigned"``, ``"signed"``, ``"float"``, ``"bytes"`` or an ``RDST_KEY_*`` integer);
+    ``descending`` complements the mapped bytes.  A sequence of them, most significant first, is the ``RadixKey`` with
+    ``LEVELS`` = the sum of the widths (examples/impl_radix_key.rs:32-56)."""
+    KINDS = {"unsigned": _lib.RDST_KEY_UNSIGNED, "signed": _lib.RDST_KEY_SIGNED, "float": _lib.RDST_KEY_FLOAT,
+             "bytes": _lib.RDST_KEY_BYTES_BE}
+    __slots__ = ("offset", "bytes", "kind", "descending")
+
+    def __init__(self, offset, bytes, kind, descending=False):  # noqa: A002  (the C field's name)
+        self.offset, self.bytes = int(offset), int(bytes)
+        self.kind = self.KINDS[kind] if isinstance(kind, str) else int(kind)
+        self.descending = bool(descending)
+
+    def __repr__(self):
+        return f"KeyField({self.offset}, {self.bytes}, {self.kind}, descending={self.descending})"
+
+    def __eq__(self, other):
+        return isinstance(other, KeyField) and self.as_tuple() == other.as_tuple()
+
+    def __hash__(self):
+        return hash(self.as_tuple())
+
+    def as_tuple(self):
+        """(offset, bytes, kind, flags) as the C struct holds them"""
+        return self.offset, self.bytes, self.kind, _lib.RDST_FIELD_DESCENDING if self.descending else 0
+
+
+def _field_table(fields):
+    fields = list(fields)
+    if not all(isinstance(f, KeyField) for f in fields):
+        raise TypeError("a key description is a sequence of KeyField")
+    return (_lib.KeyFieldC * max(1, len(fields)))(*[_lib.KeyFieldC(*f.as_tuple()) for f in fields]), len(fields)
+
+
+def sort_records_device_tensor(records, fields, scratch=None, check=True):
+    """``rdst_hip_sort_records_by_fields_device``: sort the rows of a contiguous (n, R) uint8 HIP tensor in place by the key
+    ``fields`` describes (a sequence of :class:`KeyField`, most significant first); rows with equal keys keep their order.
+    The row base needs no alignment.  ``scratch``: optional uint8 HIP tensor of at least
+    ``rdst_hip_sort_records_by_fields_scratch_bytes`` bytes, 256-byte aligned (allocated when omitted).  Runs on the
+    tensor's current stream: keys of up to 8 bytes stay asynchronous unless ``check``, longer ones block (the tie counts
+    come to the host)."""
+    import torch
+    if not records.is_cuda:
+        raise ValueError("sort_records_device_tensor needs a tensor on a HIP device")
+    if records.dim() != 2 or records.dtype != torch.uint8 or not records.is_contiguous():
+        raise ValueError("records must be a contiguous (n, R) uint8 tensor, one row per record")
+    n, rec_bytes = int(records.shape[0]), int(records.shape[1])
+    table, nf = _field_table(fields)
+    lib = _lib.load()
+    need = int(lib.rdst_hip_sort_records_by_fields_scratch_bytes(n, rec_bytes, table, nf))
+    if scratch is None:
+        scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=records.device)  # the caching allocator hands out 512-byte aligned blocks
+    elif scratch.device != records.device or not scratch.is_contiguous() or scratch.numel() * scratch.element_size() < need:
+        raise ValueError(f"scratch must be a contiguous tensor on the records' device with at least {need} bytes")
+    with torch.cuda.device(records.device):
+        s = _stream_handle(records)
+        _lib.check(lib.rdst_hip_sort_records_by_fields_device(ctypes.c_void_p(records.data_ptr()), n, rec_bytes, table, nf,
+                                                              ctypes.c_void_p(scratch.data_ptr()), scratch.numel() * scratch.element_size(), s))
+        if check and n > 1:
+            _lib.check(lib.rdst_hip_device_status(s))
+
+
+def _is_byte_string(ftype):
+    return (ftype.subdtype is not None and ftype.subdtype[0] == np.uint8 and len(ftype.subdtype[1]) == 1) or \
+        (ftype.kind in "SV" and ftype.fields is None and ftype.subdtype is None)
+
+
+def key_fields_of(dtype, names):
+    """The :class:`KeyField` table of a numpy structured dtype for the fields ``names``: each a field name or a
+    ``(name, "desc")`` / ``(name, "asc")`` pair, most significant first.  Offsets, widths and kinds come from the dtype:
+    integers and floats of any built-in width, and byte strings (``('u1', (N,))``, ``'S<N>'``, ``'V<N>'``)."""
+    out = []
+    for item in names:
+        name, direction = (item, "asc") if isinstance(item, str) else item
+        if direction not in ("asc", "desc"):
+            raise ValueError(f"field direction is 'asc' or 'desc', not {direction!r}")
+        ftype, offset = dtype.fields[name][:2]
+        if _is_byte_string(ftype):
+            kind, nbytes = _lib.RDST_KEY_BYTES_BE, ftype.itemsize
+        else:
+            if ftype.byteorder == ">":
+                raise TypeError(f"field {name!r} is big-endian; built-in key fields are read little-endian")
+            kind, nbytes, _levels = key_info(ftype.name)
+        out.append(KeyField(int(offset), nbytes, kind, direction == "desc"))
+    return out
+
+
 def sort_host_records(arr, field, device=-1):
     """``rdst_hip_sort_records`` on a numpy structured array, in place: the rows are ordered by ``field``
     (a 4- or 8-byte integer or float field, or a ``[u8; N]`` byte string: ``('u1', (N,))``, ``'S<N>'`` or ``'V<N>'``, N up to
-    RDST_BYTES_MAX_N, lexicographic); rows with equal keys keep their order."""
+    RDST_BYTES_MAX_N, lexicographic); rows with equal keys keep their order.  ``field`` may also be a sequence of field
+    names or ``(name, "desc")`` pairs, most significant first (``rdst_hip_sort_records_by_fields``): any built-in width,
+    any offset; or a sequence of :class:`KeyField`."""
     if not isinstance(arr, np.ndarray) or arr.dtype.fields is None or arr.ndim != 1:
         raise ValueError("need a 1-D numpy structured array")
     if not arr.flags.c_contiguous or not arr.flags.writeable:
         raise ValueError("need a writeable C-contiguous array (rdst sorts a mutable slice)")
+    if not isinstance(field, str):
+        field = list(field)
+        fields = field if field and all(isinstance(f, KeyField) for f in field) else key_fields_of(arr.dtype, field)
+        table, nf = _field_table(fields)
+        opts = _lib.HipOptsC(int(device), 0, 0)
+        _lib.check(_lib.load().rdst_hip_sort_records_by_fields(ctypes.c_void_p(arr.ctypes.data), arr.shape[0], arr.dtype.itemsize, table, nf,
+                                                               ctypes.byref(opts)))
+        return
     ftype, offset = arr.dtype.fields[field][:2]
-    byte_string = (ftype.subdtype is not None and ftype.subdtype[0] == np.uint8 and len(ftype.subdtype[1]) == 1) or \
-        (ftype.kind in "SV" and ftype.fields is None and ftype.subdtype is None)
+    byte_string = _is_byte_string(ftype)
     if byte_string:
         kind, nbytes = _lib.RDST_KEY_BYTES_BE, ftype.itemsize
         if not 1 <= nbytes <= _lib.RDST_BYTES_MAX_N:
