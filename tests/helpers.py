@@ -635,3 +635,161 @@ def stray_positions(n, key_bytes):
     assert n % tile != 0
     pos = [1, tile - 1, tile, n // 2 + 1, tile * (n // tile) - 1, n - 1] + [b * tile + 777 for b in range(8)]
     return not_sampled(n, pos)
+
+
+# ---- key-value sorts: the pair tile, values that name their position, the reference, and the inputs of the pairs tests ------
+
+PAIR_THREADS = 768               # :4970  PAIR_WAVES = 12 waves of 64 lanes
+PAIR_KPT = {8: 11, 12: 7, 16: 5}  # :4969  constexpr int pair_kpt(size_t key_bytes, size_t val_bytes) { return key_bytes + val_bytes <= 8 ? 11 : (key_bytes + val_bytes <= 12 ? 7 : 5); }
+PAIR_WIDTHS = ((4, 4), (4, 8), (8, 4), (8, 8))
+VALUE_ODD = {4: 0x9E3779B1, 8: 0x9E3779B97F4A7C15}
+
+
+def pair_kpt(key_bytes, val_bytes):
+    return PAIR_KPT[key_bytes + val_bytes]
+
+
+def pair_tile(key_bytes, val_bytes):
+    """pairs per tile of launch_pass_pairs: 8 448, 5 376 or 3 840"""
+    return PAIR_THREADS * pair_kpt(key_bytes, val_bytes)
+
+
+def pair_lengths(key_bytes, val_bytes):
+    """a few tiles with a single pair in the last one; several tiles on every one of the 8 chains and a partial last tile"""
+    t = pair_tile(key_bytes, val_bytes)
+    return 3 * t + 1, 37 * t + t // 2 + 3
+
+
+def key_dtype(key_bytes, kind):
+    """numpy dtype name of a `key_bytes`-wide key of kind "u", "i" or "f" """
+    return {"u": "uint", "i": "int", "f": "float"}[kind] + str(8 * key_bytes)
+
+
+def position_values(n, vdtype):
+    """value i = i * an odd constant modulo 2^w: a bijection of the index, so a value names the position it came from, and
+    every bit of the value is in play"""
+    dt = np.dtype(vdtype)
+    ut = np.dtype(f"u{dt.itemsize}")
+    return (np.arange(n, dtype=ut) * ut.type(VALUE_ODD[dt.itemsize])).view(dt)
+
+
+def value_positions(vals):
+    """inverse of position_values: the positions the values came from (int64)"""
+    w = vals.dtype.itemsize
+    ut = np.dtype(f"u{w}")
+    inv = pow(VALUE_ODD[w], -1, 1 << (8 * w))
+    return (uint_view(vals) * ut.type(inv)).astype(np.int64)
+
+
+def expected_pairs(keys, vals):
+    """THE output of a stable key-value sort: the stable order of the mapped keys is the single permitted one"""
+    order = np.argsort(mapped_key(keys), kind="stable")
+    return keys[order], vals[order]
+
+
+def keys_with_constant_levels(n, dtype, levels, seed, digit=0x5A):
+    """random keys whose MAPPED bytes at `levels` all hold `digit` (built in mapped space: a constant raw byte of a float is
+    not constant once the negatives are complemented); every other level stays random"""
+    dt = np.dtype(dtype)
+    m = uint_view(random_bits(n, f"uint{8 * dt.itemsize}", seed).copy())
+    for l in levels:
+        sh = np.array(8 * l, dtype=m.dtype)
+        m = (m & ~(np.array(0xFF, dtype=m.dtype) << sh)) | (np.array(digit, dtype=m.dtype) << sh)
+    return unmapped(m, dtype)
+
+
+def constant_levels(keys):
+    """the set of levels at which the mapped digit of `keys` takes one value (the levels a sort with level skipping skips)"""
+    m = mapped_key(keys)
+    out = set()
+    for l in range(keys.dtype.itemsize):
+        d = (m >> np.array(8 * l, dtype=m.dtype)) & np.array(0xFF, dtype=m.dtype)
+        if (d == d[0]).all():
+            out.add(l)
+    return out
+
+
+def constant_level_sets(key_bytes):
+    """the level sets of the skipped-level cases: (name, levels, passes left)"""
+    top, mid = key_bytes - 1, {4: 1, 8: 3}[key_bytes]
+    every = set(range(key_bytes))
+    sets = [("level 0", {0}), ("level 1", {1}), ("top level", {top})]
+    if key_bytes == 8:
+        sets.append(("a middle level", {mid}))
+    sets += [("levels 0 and 1", {0, 1}), ("level 0 and top", {0, top}), ("all but level 0", every - {0}),
+             ("all but the top", every - {top}), ("all but a middle level", every - {mid}), ("none", set())]
+    return [(f"{name} constant", levels, key_bytes - len(levels)) for name, levels in sets]
+
+
+def constant_level_inputs(key_bytes, val_bytes, kind):
+    """(name, levels, passes, keys) of every skipped-level case of the pairs tests, at both pair lengths: `levels` the
+    constant ones, `passes` the number left to execute.  Float keys: one more case whose keys share one sign (the top level
+    stays busy, but on half of its digits)"""
+    dtype = key_dtype(key_bytes, kind)
+    for j, n in enumerate(pair_lengths(key_bytes, val_bytes)):
+        for i, (name, levels, passes) in enumerate(constant_level_sets(key_bytes)):
+            yield f"{name}, n={n}", levels, passes, keys_with_constant_levels(n, dtype, sorted(levels), seed=9000 + 100 * j + i)
+        if kind == "f":
+            m = uint_view(random_bits(n, f"uint{8 * key_bytes}", seed=9090 + j).copy())
+            m |= np.array(1 << (8 * key_bytes - 1), dtype=m.dtype)   # mapped top bit set: the non-negative floats
+            yield f"one sign, n={n}", set(), key_bytes, unmapped(m, dtype)
+
+
+COPY_BACK_LEVELS = {1}   # level 1 constant: 3 or 7 passes, the result ends in the tmps
+
+
+def copy_back_inputs(key_bytes, val_bytes):
+    """the keys of the copy-back tests: level 1 constant (an odd number of passes) at four consecutive lengths from the
+    short pair length, so that n * sizeof(V) leaves every remainder modulo 16 a value width allows"""
+    n0 = pair_lengths(key_bytes, val_bytes)[0]
+    for r in range(4):
+        yield keys_with_constant_levels(n0 + r, key_dtype(key_bytes, "u"), sorted(COPY_BACK_LEVELS), seed=9500 + r)
+
+
+def mask_other_bytes(a, level):
+    """`a` with every byte but the one at `level` cut to its two low bits: many whole keys are equal"""
+    u = uint_view(a)
+    mask = sum((0xFF if b == level else 0x03) << (8 * b) for b in range(u.dtype.itemsize))
+    return (u & np.array(mask, dtype=u.dtype)).view(a.dtype)
+
+
+def pair_digit_levels(key_bytes):
+    return 0, 1, key_bytes - 1
+
+
+def pair_heavy_digit_inputs(key_bytes, val_bytes):
+    """(name, level, keys) of heavy_digit_inputs at pair sizes: unsigned keys, both pair lengths, the levels 0, 1 and top"""
+    dtype = key_dtype(key_bytes, "u")
+    for n in pair_lengths(key_bytes, val_bytes):
+        for level in pair_digit_levels(key_bytes):
+            for name, a in heavy_digit_inputs(n, dtype, level, seed=n + level).items():
+                yield name, level, a
+
+
+def increasing_mapped(n, dtype, seed):
+    """strictly increasing keys (in mapped order) with every level busy: mapped key i = i * K + r_i, r_i random below K"""
+    w = 8 * np.dtype(dtype).itemsize
+    k = (1 << w) // n
+    assert k >= 2
+    r = np.random.default_rng(seed).integers(0, k, size=n, dtype=np.uint64)
+    return unmapped((np.arange(n, dtype=np.uint64) * np.uint64(k) + r).astype(f"u{w // 8}"), dtype)
+
+
+def chain_split_cases(n, dtype, seed=77, short=40_000, tiny=700):
+    """inputs that bend the split of a pass's source into 8 chain segments (unsigned bit patterns of the width of `dtype`): a
+    skipped middle level, previous digits crowded into one group or missing from most, segments shorter than a tile"""
+    u = np.dtype(f"uint{8 * np.dtype(dtype).itemsize}")
+    bits = u.itemsize * 8
+    rng = np.random.default_rng(seed)
+    full = rng.integers(0, 1 << 63, size=n, dtype=np.uint64).astype(u) if bits == 32 else rng.integers(0, 1 << 64, size=n, dtype=np.uint64)
+    return {
+        "level 1 constant": (full & ~u.type(0xFF00)) | u.type(0x4200),
+        "level 0 in one group": (full & ~u.type(0xE0)),
+        "level 0 90% in group 7": np.where(rng.random(n) < 0.9, full | u.type(0xE0), full),
+        "level 1 only two digits": (full & ~u.type(0xFE00)),
+        "levels 0-1 constant": (full & ~u.type(0xFFFF)) | u.type(0x1234),
+        "top levels only": full & (u.type(0xFF) << u.type(bits - 8)),
+        "uniform": full,
+        "short": full[:short],
+        "tiny": full[:tiny],
+    }

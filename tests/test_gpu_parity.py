@@ -8,7 +8,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import (DTYPES, SMALL_DTYPES, gen_inputs, heavy_digit_inputs, mapped_key, random_bits, reference_sorted, same_bits, to_device,
+from helpers import (DTYPES, SMALL_DTYPES, chain_split_cases, gen_inputs, heavy_digit_inputs, mapped_key, random_bits, reference_sorted, same_bits, to_device,
                      to_host, u32_patterns)
 
 pytestmark = pytest.mark.gpu
@@ -115,22 +115,7 @@ def test_chain_split_shapes(gpu, dtype):
     Inputs that bend that: a skipped middle level, previous digits crowded into one group or
     missing from most, segments shorter than a tile — each sorted with the split on and off and
     against numpy on the mapped keys."""
-    u = np.dtype({"float32": "uint32"}.get(dtype, dtype))
-    bits = u.itemsize * 8
-    rng = np.random.default_rng(77)
-    n = 2_000_003
-    full = rng.integers(0, 1 << 63, size=n, dtype=np.uint64).astype(u) if bits == 32 else rng.integers(0, 1 << 64, size=n, dtype=np.uint64)
-    cases = {
-        "level 1 constant": (full & ~u.type(0xFF00)) | u.type(0x4200),
-        "level 0 in one group": (full & ~u.type(0xE0)),
-        "level 0 90% in group 7": np.where(rng.random(n) < 0.9, full | u.type(0xE0), full),
-        "level 1 only two digits": (full & ~u.type(0xFE00)),
-        "levels 0-1 constant": (full & ~u.type(0xFFFF)) | u.type(0x1234),
-        "top levels only": full & (u.type(0xFF) << u.type(bits - 8)),
-        "uniform": full,
-        "short": full[:40_000],
-        "tiny": full[:700],
-    }
+    cases = chain_split_cases(2_000_003, dtype)
     try:
         for name, a in cases.items():
             a = np.ascontiguousarray(a).view(dtype)
