@@ -195,5 +195,18 @@ void sort_records_by(T* data, std::size_t n, std::initializer_list<rdst_key_fiel
 template <typename T>
 void sort_records_by(std::vector<T>& v, std::initializer_list<rdst_key_field> fields) { sort_records_by(v.data(), v.size(), fields); }
 
+// Many independent slices of one DEVICE-resident array in one call: segment s is [offsets[s], offsets[s + 1]) (host
+// table of n_segments + 1 non-decreasing indices), each sorted as radix_sort_unstable would sort it
+// (rdst_hip_sort_segments_device).  dev_tmp / tmp_elems: scratch for segments longer than the block class
+// (rdst_hip_sort_segments_limits), at least as long as the longest of them; may be null / 0 when there is none.
+// Asynchronous on `stream`; failures of the kernels surface in rdst_hip_device_status.
+template <typename T>
+void sort_segments(T* dev_keys, std::size_t len, const std::uint64_t* offsets, std::size_t n_segments, T* dev_tmp = nullptr,
+                   std::size_t tmp_elems = 0, void* stream = nullptr) {
+    const int rc = rdst_hip_sort_segments_device(dev_keys, dev_tmp, tmp_elems, len, offsets, n_segments, sizeof(T), RadixKey<T>::kind,
+                                                 static_cast<std::uint32_t>(RadixKey<T>::LEVELS), stream);
+    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+}
+
 }  // namespace rdst
 #endif  // RDST_HPP

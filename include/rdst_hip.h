@@ -98,7 +98,8 @@ typedef enum {
     RDST_STAGE_LOCAL = 8,    /* K4: per-bucket sort of the remaining levels inside LDS (hybrid and atomic routes) */
     RDST_STAGE_MSD_A = 10,   /* atomic route: scatter by the top byte into over-provisioned areas (claims instead of counts) */
     RDST_STAGE_MSD_B = 11,   /* atomic route: scatter of every area by the second byte into the bucket slots (low halves) */
-    RDST_STAGE_SAMPLE = 12   /* the 8 192-key sample (and, if it flags the keys, K1h + the route decision) before the MSD passes */
+    RDST_STAGE_SAMPLE = 12,  /* the 8 192-key sample (and, if it flags the keys, K1h + the route decision) before the MSD passes */
+    RDST_STAGE_SEGMENTS = 13 /* segmented sort: the item table's copy and the batched wave-class and block-class launches */
 } rdst_stage;
 
 /* Device routes (rdst_hip_last_route). */
@@ -170,6 +171,53 @@ int rdst_hip_sort_records(void* host_records, uint64_t len, uint32_t record_byte
 int rdst_hip_sort_pairs_device(void* dev_keys, void* dev_vals, void* dev_tmp_keys, void* dev_tmp_vals,
                                uint64_t len, uint32_t key_bytes, rdst_key_kind kind, uint32_t levels,
                                uint32_t val_bytes, void* stream);
+
+/* ---- many independent slices in one call ---------------------------------------------------------
+ * The reference sorts the 256 buckets of a chunk as slices of their own, in parallel (src/sorter.rs:131-138), and a
+ * caller may do the same with `chunks_mut(..).par_for_each(|c| c.radix_sort_unstable())`.  The device form: one array
+ * and a table of segment borders.
+ *
+ * Sorts every segment [offsets[s], offsets[s+1]) of dev_keys on its own; s in [0, n_segments).  offsets: HOST array of
+ * n_segments + 1 non-decreasing element indices, offsets[n_segments] <= len; n_segments < 2^32.  Keys before offsets[0]
+ * and from offsets[n_segments] on are not touched.  Every segment ends in the order rdst_hip_sort_device would give that
+ * slice on its own, bit for bit; pairs with equal keys keep their input order, as rdst_hip_sort_pairs_device keeps them.
+ * Key widths, kinds and `levels`: those of rdst_hip_sort_device (pairs: of rdst_hip_sort_pairs_device), with the same
+ * error codes; n_segments == 0 is RDST_OK and does nothing.
+ *
+ * Segments are served by length (rdst_hip_sort_segments_limits gives the borders; length 0 and 1: nothing to do):
+ *   2 .. wave_max            one wave per segment, keys in registers, four segments per workgroup — one launch for all;
+ *   wave_max+1 .. block_max  one workgroup per segment (the one-workgroup LDS sort, with a value array for pairs),
+ *                            longest first — one launch for all;
+ *   longer                   the whole-slice route, one segment after another on `stream`, with dev_tmp (pairs:
+ *                            dev_tmp_keys, dev_tmp_vals) as scratch: tmp_elems must be at least the longest such segment
+ *                            (rdst_segments_plan's *tmp_elems_out).  With no segment over block_max, tmp_elems may be 0
+ *                            and the tmp pointers NULL; otherwise RDST_ERR_ARG before any device work.
+ * Segment starts need the alignment of the element only.
+ *
+ * `offsets` is read before the call returns: the caller may free or change it at once.  The work list travels through a
+ * pinned staging buffer the library keeps per device: a call WAITS (on an event, not on the stream) only while the list
+ * of the previous segmented call on that device has not reached the device yet.  Apart from that, and from what
+ * rdst_hip_sort_device documents for slices beyond the window (long segments take that route), the call is asynchronous
+ * on `stream`; kernel failures surface in rdst_hip_device_status. */
+int rdst_hip_sort_segments_device(void* dev_keys, void* dev_tmp, uint64_t tmp_elems, uint64_t len,
+                                  const uint64_t* offsets, uint64_t n_segments,
+                                  uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels, void* stream);
+int rdst_hip_sort_segments_pairs_device(void* dev_keys, void* dev_vals, void* dev_tmp_keys, void* dev_tmp_vals,
+                                        uint64_t tmp_elems, uint64_t len, const uint64_t* offsets, uint64_t n_segments,
+                                        uint32_t key_bytes, rdst_key_kind kind, uint32_t levels, uint32_t val_bytes, void* stream);
+/* out = { wave_max, block_max }: longest segment of the wave class and of the block class, for this key and value width
+ * (val_bytes 0 = keys only).  Pure.  Unsupported widths: RDST_ERR_UNSUPPORTED. */
+int rdst_hip_sort_segments_limits(uint32_t elem_bytes, uint32_t val_bytes, uint32_t out[2]);
+/* Host only, like rdst_regions_plan: the work list the entry runs.  One item per segment of at least two keys: wave
+ * class first, in segment order; then block class, longest first, ties in segment order; then long class, in segment
+ * order (a long item's `len` saturates at 2^32 - 1: its length is offsets[seg + 1] - offsets[seg]).  class_counts_out:
+ * the three counts; *tmp_elems_out: the longest long segment, or 0.  A `capacity` below their sum: RDST_ERR_ARG, with the
+ * counts and *tmp_elems_out still written.  Decreasing offsets, a last offset past `len`, NULL offsets with
+ * n_segments > 0: RDST_ERR_ARG. */
+typedef struct { uint64_t start; uint32_t len; uint32_t seg; } rdst_segment_item;
+int rdst_segments_plan(const uint64_t* offsets, uint64_t n_segments, uint64_t len, uint32_t elem_bytes, uint32_t val_bytes,
+                       rdst_segment_item* items_out, uint64_t capacity, uint64_t class_counts_out[3],
+                       uint64_t* tmp_elems_out);
 
 /* [u8; N] rows (N = n_bytes in 1..RDST_BYTES_MAX_N), device-resident, sorted IN PLACE in lexicographic order
  * (src/radix_key_impl.rs:78-85).  No alignment requirement on dev_rows.  dev_scratch: at least

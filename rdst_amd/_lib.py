@@ -16,6 +16,7 @@ RDST_OK = 0
 RDST_BYTES_MAX_N = 4096  # longest [u8; N] key the device route takes (include/rdst_hip.h)
 RDST_FIELD_DESCENDING = 1  # rdst_key_field.flags: complement the field's mapped bytes
 RDST_KEY_FIELDS_MAX = 16   # fields in one key description
+RDST_STAGE_SEGMENTS = 13   # rdst_stage: the batched launches of the segmented sort
 
 # every symbol include/rdst_hip.h declares; tests check that the library exports all of them
 SYMBOLS = (
@@ -26,6 +27,10 @@ SYMBOLS = (
     "rdst_regions_plan",
     "rdst_hip_host_timing",
     "rdst_hip_sort_pairs_device",
+    "rdst_hip_sort_segments_device",
+    "rdst_hip_sort_segments_pairs_device",
+    "rdst_hip_sort_segments_limits",
+    "rdst_segments_plan",
     "rdst_hip_sort_records",
     "rdst_hip_sort_bytes_device",
     "rdst_hip_sort_bytes_scratch_bytes",
@@ -81,6 +86,11 @@ class KeyFieldC(ctypes.Structure):
     _fields_ = [("offset", ctypes.c_uint32), ("bytes", ctypes.c_uint32), ("kind", ctypes.c_uint32), ("flags", ctypes.c_uint32)]
 
 
+class SegmentItemC(ctypes.Structure):
+    """rdst_segment_item: one entry of the segmented sort's work list (start, len, segment index)."""
+    _fields_ = [("start", ctypes.c_uint64), ("len", ctypes.c_uint32), ("seg", ctypes.c_uint32)]
+
+
 class RdstHipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"rdst_hip call failed with status {code}: {msg}")
@@ -112,6 +122,10 @@ def load():
     lib.rdst_hip_partition_device.argtypes = [vp, u64, u32, ci, u32, u32, vp, u64, u64p, vp]
     lib.rdst_hip_sort_device.argtypes = [vp, vp, u64, u32, ci, u32, vp]
     lib.rdst_hip_sort_pairs_device.argtypes = [vp, vp, vp, vp, u64, u32, ci, u32, u32, vp]
+    lib.rdst_hip_sort_segments_device.argtypes = [vp, vp, u64, u64, u64p, u64, u32, ci, u32, vp]
+    lib.rdst_hip_sort_segments_pairs_device.argtypes = [vp, vp, vp, vp, u64, u64, u64p, u64, u32, ci, u32, u32, vp]
+    lib.rdst_hip_sort_segments_limits.argtypes = [u32, u32, ctypes.POINTER(u32)]
+    lib.rdst_segments_plan.argtypes = [u64p, u64, u64, u32, u32, ctypes.POINTER(SegmentItemC), u64, u64p, u64p]
     lib.rdst_hip_sort_records.argtypes = [vp, u64, u32, u32, u32, ci, ctypes.POINTER(HipOptsC)]
     lib.rdst_hip_sort_bytes_device.argtypes = [vp, u64, u32, vp, u64, vp]
     lib.rdst_hip_sort_bytes_scratch_bytes.argtypes = [u64, u32]

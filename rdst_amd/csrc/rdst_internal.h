@@ -5,6 +5,8 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include <mutex>
+
 #include "rdst_hip.h"
 
 namespace rdst_internal {
@@ -57,6 +59,31 @@ int device_error_word(uint32_t** out);
 // route, narrowed back (the path rdst_hip_sort takes for these widths).  Asynchronous.
 uint64_t widened_scratch_bytes(uint64_t len, uint32_t nb);
 int sort_bytes_widened(void* dev_rows, uint64_t len, uint32_t nb, void* scratch, hipStream_t s);
+
+// The same for host-only translation units (rdst_segments.cpp), which do not see HIP's types.
+int note_error(int code, const char* what);
+
+// ---- hooks for rdst_segments.hip -------------------------------------------------------------------------------------
+// The library's mutex; every hook below this line is called with it held.
+std::mutex& library_mutex();
+// The argument checks shared by the device entry points (width, kind, levels, pointer, alignment, length); no lock needed.
+int check_key_args(const void* p, uint64_t len, uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels);
+// The xor masks of the order-preserving key map (applied when the sign bit is set / clear), in the low elem_bytes bytes.
+void key_xor_masks(rdst_key_kind kind, uint32_t elem_bytes, unsigned __int128* neg, unsigned __int128* pos);
+// One whole slice (pairs: one pair slice) by the route rdst_hip_sort_device (rdst_hip_sort_pairs_device) takes.
+int sort_slice_locked(void* keys, void* tmp, uint64_t n, uint32_t elem_bytes, rdst_key_kind kind, hipStream_t s);
+int sort_pairs_slice_locked(void* keys, void* vals, void* tmp_keys, void* tmp_vals, uint64_t n, uint32_t key_bytes, rdst_key_kind kind,
+                            uint32_t val_bytes, hipStream_t s);
+// Bytes of workspace such a slice asks for (an upper bound over its routes).
+size_t slice_workspace_bytes(uint64_t n, uint32_t key_bytes, rdst_key_kind kind, uint32_t val_bytes);
+// The current device's workspace, grown to `bytes` if need be and handed over to stream `s` (workspace_acquire); every
+// slice sorted afterwards that asks for no more than `bytes` leaves it where it is.  workspace_handback records that `s`
+// used it (workspace_release).
+int workspace_take(size_t bytes, hipStream_t s, void** ws_out, int* device_out);
+int workspace_handback(hipStream_t s);
+// Profiling (rdst_hip_set_profiling): open a run of its own / close the stage that ends here.  No-ops when profiling is off.
+int profile_open_run(hipStream_t s);
+int profile_stage_end(hipStream_t s, uint32_t stage);
 
 // rdst_bytes.hip: a host slice of `len` rows of `row_bytes` bytes ordered by the byte string at (key_offset, key_bytes),
 // equal keys in input order.  Blocking; the slice is written only after the device reported success.  Arguments are

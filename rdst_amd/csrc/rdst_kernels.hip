@@ -42,6 +42,7 @@
 
 #include "rdst_hip.h"
 #include "rdst_internal.h"
+#include "rdst_device.h"
 
 namespace {
 
@@ -165,27 +166,7 @@ struct LevelChains {  // written by K2 for every executed level, read by K3's ti
     uint32_t pad[3];
 };
 
-typedef unsigned __int128 u128;  // u128 / i128 keys (src/radix_key_impl.rs:39-46, :123-130)
-
-struct KeyMap {  // order-preserving map as two xor masks (src/radix_key_impl.rs)
-    u128 neg;  // xor applied when the sign bit is set
-    u128 pos;  // xor applied when it is clear
-};
-
-template <typename K>
-__device__ __forceinline__ K map_key(K k, K neg, K pos) {
-    constexpr int W = sizeof(K) * 8;
-    return (K)(k ^ ((K)(k >> (W - 1)) ? neg : pos));
-}
-template <typename K>
-__device__ __forceinline__ K unmap_key(K m, K neg, K pos) {
-    constexpr int W = sizeof(K) * 8;
-    return (K)(m ^ ((K)(m >> (W - 1)) ? pos : neg));
-}
-template <typename K>
-__device__ __forceinline__ uint32_t digit_of(K mapped, int shift) {
-    return (uint32_t)(mapped >> shift) & 0xFFu;
-}
+// u128, KeyMap, map_key, unmap_key, digit_of: rdst_device.h
 
 template <typename S>
 __device__ __forceinline__ S ld_relaxed(const S* p) {
@@ -241,20 +222,7 @@ __device__ __forceinline__ K lane63_of(K x) {
     }
 }
 
-// lanes of this wave holding the same 8-bit digit (all 64 lanes must be active)
-__device__ __forceinline__ uint64_t match_any8(uint32_t d) {
-    uint64_t m = ~0ull;
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-        const bool bit = (d >> b) & 1u;
-        const uint64_t bal = __ballot(bit);
-        m &= bit ? bal : ~bal;
-    }
-    return m;
-}
-__device__ __forceinline__ uint32_t lanes_below(uint64_t mask) {  // popcount(mask & lanes < me)
-    return __builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
-}
+// match_any8, lanes_below: rdst_device.h
 
 // ------------------------------------------------------------------------------------------
 // K1: every level's histogram from one read.  One 1024-thread block per CU (grid = #CUs), each
@@ -1163,24 +1131,9 @@ __device__ uint32_t g_exp_timeline_kernel = 0;  // whose stamps: 0 K3 (level 0),
 #define RDST_TL_END(row) do {} while (0)
 #endif
 
-// lanes below me holding my digit, 4 VALU per bit: my bit as a 0 / -1 mask (v_bfe_i32), the
-// wave's ballot of that bit (v_cmp), then per 32-lane half ONE v_bitop3_b32 that keeps in `same`
-// only the lanes whose bit equals mine:  same &= ~(ballot ^ my_bit)   (truth table 0x90).
-__device__ __forceinline__ uint32_t peers_below(uint32_t word, int bit0) {
-    // bit by bit (ballot, then the two mask updates that read it): computing the eight ballots first
-    // removes the wait states after each ballot but measured 4-6 % slower (64-bit encodings, 16 more SGPRs live)
-    uint32_t same_lo = ~0u, same_hi = ~0u;
-#pragma unroll
-    for (int b = 0; b < 8; ++b) {
-        const int m = __builtin_amdgcn_sbfe((int)word, (unsigned)(bit0 + b), 1u);  // 0 or -1
-        const uint64_t bal = __builtin_amdgcn_ballot_w64(m != 0);
-        same_lo = __builtin_amdgcn_bitop3_b32(same_lo, (uint32_t)bal, (uint32_t)m, 0x90);
-        same_hi = __builtin_amdgcn_bitop3_b32(same_hi, (uint32_t)(bal >> 32), (uint32_t)m, 0x90);
-    }
-    return __builtin_amdgcn_mbcnt_hi(same_hi, __builtin_amdgcn_mbcnt_lo(same_lo, 0u));
-}
+// peers_below (lanes below me holding my digit) and digit_word: rdst_device.h
 
-// the same, plus the size of my digit's group in this wave (heavy-digit path)
+// peers_below, plus the size of my digit's group in this wave (heavy-digit path)
 __device__ __forceinline__ uint32_t peers_below_total(uint32_t word, int bit0, uint32_t& total) {
     uint32_t same_lo = ~0u, same_hi = ~0u;
 #pragma unroll
@@ -1192,12 +1145,6 @@ __device__ __forceinline__ uint32_t peers_below_total(uint32_t word, int bit0, u
     }
     total = (uint32_t)__builtin_popcount(same_lo) + (uint32_t)__builtin_popcount(same_hi);
     return __builtin_amdgcn_mbcnt_hi(same_hi, __builtin_amdgcn_mbcnt_lo(same_lo, 0u));
-}
-
-template <typename K>
-__device__ __forceinline__ uint32_t digit_word(K mapped, int shift) {  // 32-bit half that holds the digit
-    if constexpr (sizeof(K) > 4) return (uint32_t)(mapped >> (shift & ~31));
-    else return (uint32_t)mapped;
 }
 
 // Decoupled look-back: thread d walks digit d's status words of rows t-1, t-2, ... and returns in
@@ -6291,6 +6238,100 @@ int rdst_hip_level_counts(const void* dev_keys, uint64_t len, uint32_t elem_byte
 namespace rdst_internal {
 
 int set_error(int code, const char* what, hipError_t e) { return fail(code, what, e); }
+int note_error(int code, const char* what) { return fail(code, what); }
+
+// Hooks for rdst_segments.hip.
+std::mutex& library_mutex() { return g_mutex; }
+
+int check_key_args(const void* p, uint64_t len, uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels) {
+    return check_common(p, len, elem_bytes, kind, levels);
+}
+
+void key_xor_masks(rdst_key_kind kind, uint32_t elem_bytes, unsigned __int128* neg, unsigned __int128* pos) {
+    const KeyMap km = key_map_for(kind, elem_bytes);
+    *neg = km.neg;
+    *pos = km.pos;
+}
+
+int sort_slice_locked(void* keys, void* tmp, uint64_t n, uint32_t elem_bytes, rdst_key_kind kind, hipStream_t s) {
+    int rc = RDST_OK;
+    RDST_BY_WIDTH(elem_bytes, rc = (sort_whole<K, LV>(static_cast<K*>(keys), static_cast<K*>(tmp), n, kind, s)));
+    return rc;
+}
+
+int sort_pairs_slice_locked(void* keys, void* vals, void* tmp_keys, void* tmp_vals, uint64_t n, uint32_t key_bytes, rdst_key_kind kind,
+                            uint32_t val_bytes, hipStream_t s) {
+    return by_uint(key_bytes, [&](auto k) {
+        return by_uint(val_bytes, [&](auto v) {
+            using KT = decltype(k);
+            using VT = decltype(v);
+            return run_pipeline<KT, (int)sizeof(KT), VT>(static_cast<KT*>(keys), static_cast<KT*>(tmp_keys), n, kind, 0, sizeof(KT), true, true, s, nullptr,
+                                                         nullptr, static_cast<VT*>(vals), static_cast<VT*>(tmp_vals));
+        });
+    });
+}
+
+namespace {
+template <typename K, int LV, typename V>
+size_t pipeline_workspace_bytes(uint64_t n, rdst_key_kind kind) {  // what pick_workspace asks for first
+    Pipe<K, V> p{};
+    p.n = n;
+    p.level_lo = 0;
+    p.level_hi = LV;
+    p.allow_skip = p.copy_back = true;
+    int cfg = g_tuning.pass_cfg;
+    if (cfg < 0 || cfg >= kNumPassCfgs) cfg = default_cfg(sizeof(K), n, kind != RDST_KEY_UNSIGNED);
+    return pick_routes<LV>(p, cfg, false).L.total;
+}
+}  // namespace
+
+size_t slice_workspace_bytes(uint64_t n, uint32_t key_bytes, rdst_key_kind kind, uint32_t val_bytes) {
+    size_t bytes = 0;
+    if (val_bytes == 0) {
+        RDST_BY_WIDTH(key_bytes, bytes = (pipeline_workspace_bytes<K, LV, NoVal>(n, kind)));
+        const size_t bound = (size_t)rdst_hip_workspace_bytes(n, key_bytes);  // covers the split of slices beyond the window
+        return bytes > bound ? bytes : bound;
+    }
+    by_uint(key_bytes, [&](auto k) {
+        return by_uint(val_bytes, [&](auto v) {
+            bytes = pipeline_workspace_bytes<decltype(k), (int)sizeof(k), decltype(v)>(n, kind);
+            return 0;
+        });
+    });
+    return bytes;
+}
+
+int workspace_take(size_t bytes, hipStream_t s, void** ws_out, int* device_out) {
+    DeviceState* D;
+    int rc = current_device_state(&D, device_out);
+    if (rc) return rc;
+    if ((rc = ensure_workspace(*D, bytes))) return rc;
+    *ws_out = D->ws;
+    D->last_plan_valid = false;
+    return workspace_acquire(*D, s);
+}
+
+int workspace_handback(hipStream_t s) {
+    DeviceState* D;
+    int rc = current_device_state(&D);
+    if (rc) return rc;
+    return workspace_release(*D, s);
+}
+
+int profile_open_run(hipStream_t s) {
+    DeviceState* D;
+    int rc = current_device_state(&D);
+    if (rc) return rc;
+    if (g_tuning.profiling) D->prof_runs.push_back({D->prof_used, 0});
+    return prof_mark(*D, s);
+}
+
+int profile_stage_end(hipStream_t s, uint32_t stage) {
+    DeviceState* D;
+    int rc = current_device_state(&D);
+    if (rc) return rc;
+    return prof_mark(*D, s, stage);
+}
 
 int device_error_word(uint32_t** out) {
     std::lock_guard<std::mutex> lock(g_mutex);

@@ -161,6 +161,111 @@ def sort_pairs_device_tensor(keys, values, tmp_keys=None, tmp_values=None, check
             _lib.check(lib.rdst_hip_device_status(s))
 
 
+def segments_limits(dtype, val_bytes=0):
+    """``rdst_hip_sort_segments_limits``: (wave_max, block_max) of the segmented sort for keys of ``dtype`` (a numpy / torch
+    dtype or its name, ``"u128"`` / ``"i128"``) and values of ``val_bytes`` bytes (0: keys only) — the longest segment one
+    wave takes and the longest one workgroup takes; longer ones go the whole-slice route and need ``tmp``."""
+    _kind, nbytes, _levels = key_info(dtype)
+    out = (ctypes.c_uint32 * 2)()
+    _lib.check(_lib.load().rdst_hip_sort_segments_limits(nbytes, int(val_bytes), out))
+    return int(out[0]), int(out[1])
+
+
+def _host_offsets(offsets):
+    """the segment borders as a contiguous uint64 numpy array on the host"""
+    if _is_torch_tensor(offsets):
+        offsets = offsets.detach().cpu().numpy()   # a device tensor: ONE copy to the host (the plan is made there)
+    a = np.asarray(offsets)
+    if a.ndim != 1 or a.size == 0:
+        raise ValueError("offsets: a 1-D sequence of n_segments + 1 element indices")
+    if a.dtype.kind not in "iu" or (a.dtype.kind == "i" and a.size and int(a.min()) < 0):
+        raise ValueError("offsets must be non-negative integers")
+    return np.ascontiguousarray(a, dtype=np.uint64)
+
+
+def segments_plan(offsets, n, dtype, val_bytes=0):
+    """``rdst_segments_plan`` (host only): the work list of a segmented sort over ``n`` elements — ``(items, counts,
+    tmp_elems)`` with ``items`` a list of (start, len, segment) in the order the entry runs them, ``counts`` the numbers
+    of wave-, block- and long-class items and ``tmp_elems`` the longest long segment (0: no ``tmp`` needed)."""
+    off = _host_offsets(offsets)
+    _kind, nbytes, _levels = key_info(dtype)
+    lib = _lib.load()
+    items = (_lib.SegmentItemC * max(1, off.size - 1))()
+    counts = (ctypes.c_uint64 * 3)()
+    tmp_elems = ctypes.c_uint64(0)
+    _lib.check(lib.rdst_segments_plan(off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), off.size - 1, int(n), nbytes, int(val_bytes),
+                                      items, off.size - 1, counts, ctypes.byref(tmp_elems)))
+    total = int(counts[0] + counts[1] + counts[2])
+    return [(int(it.start), int(it.len), int(it.seg)) for it in items[:total]], tuple(int(c) for c in counts), int(tmp_elems.value)
+
+
+def sort_segments_device_tensor(keys, offsets, tmp=None, values=None, tmp_values=None, check=True, key=None):
+    """``rdst_hip_sort_segments_device`` (with ``values``: ``rdst_hip_sort_segments_pairs_device``): sort every segment
+    ``keys[offsets[s]:offsets[s + 1]]`` of a contiguous 1-D HIP tensor on its own, in one call (``key="u128"/"i128"``: shape
+    (n, 2), offsets count keys).  ``offsets``: a sequence, a numpy array or a torch tensor of n_segments + 1 non-decreasing
+    element indices; the library reads it on the HOST, so a device tensor is copied to the host once, here.  Elements
+    outside [offsets[0], offsets[-1]) stay as they are.  ``values`` (4- or 8-byte elements, same length as ``keys``) are
+    permuted with their keys; equal keys keep their input order.  ``tmp`` (and ``tmp_values``) are needed only when a segment
+    is longer than ``segments_limits(...)[1]``: at least as many elements as the longest such segment; they are allocated
+    when omitted and needed, and not at all otherwise.  Runs on the tensor's current stream; with ``check`` the call
+    blocks and raises if a kernel reported failure."""
+    import torch
+    if not keys.is_cuda:
+        raise ValueError("sort_segments_device_tensor needs a tensor on a HIP device")
+    if _wide(key):
+        _check_wide_shape(tuple(keys.shape), keys.element_size())
+    elif keys.dim() != 1:
+        raise ValueError("keys must be a contiguous 1-D tensor")
+    if not keys.is_contiguous():
+        raise ValueError("keys must be a contiguous 1-D tensor")
+    kind, nbytes, levels = key_info(key if key else keys.dtype)
+    n = keys.numel() * keys.element_size() // nbytes
+    vbytes = 0
+    if values is not None:
+        if not values.is_cuda or values.device != keys.device or values.dim() != 1 or values.numel() != n or not values.is_contiguous():
+            raise ValueError("values must be a contiguous 1-D tensor of the keys' length on the keys' device")
+        vbytes = values.element_size()
+    off = _host_offsets(offsets)
+    n_segments = off.size - 1
+    lib = _lib.load()
+    offp = off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))
+    counts = (ctypes.c_uint64 * 3)()
+    need = ctypes.c_uint64(0)
+    rc = lib.rdst_segments_plan(offp, n_segments, n, nbytes, vbytes, None, 0, counts, ctypes.byref(need))
+    if rc != _lib.RDST_OK and counts[0] + counts[1] + counts[2] == 0:   # (a list that does not fit capacity 0 is the expected answer)
+        _lib.check(rc)
+    need = int(need.value)
+    per_key = keys.numel() // n if n else 1      # container elements per key (2 for the 128-bit limbs)
+    tmp_elems = 0
+    if need:
+        if tmp is None:
+            tmp = torch.empty(need * per_key, dtype=keys.dtype, device=keys.device)
+        elif tmp.dtype != keys.dtype or not tmp.is_contiguous() or tmp.device != keys.device or tmp.numel() < need * per_key:
+            raise ValueError(f"tmp must be a contiguous tensor of the keys' dtype and device with at least {need} keys")
+        tmp_elems = tmp.numel() // per_key
+        if values is not None:
+            if tmp_values is None:
+                tmp_values = torch.empty(need, dtype=values.dtype, device=values.device)
+            elif tmp_values.dtype != values.dtype or not tmp_values.is_contiguous() or tmp_values.device != values.device or tmp_values.numel() < need:
+                raise ValueError(f"tmp_values must be a contiguous tensor of the values' dtype and device with at least {need} elements")
+            tmp_elems = min(tmp_elems, tmp_values.numel())
+    elif tmp is not None:
+        tmp_elems = tmp.numel() // per_key
+
+    def ptr(t):
+        return ctypes.c_void_p(t.data_ptr() if t is not None else None)
+
+    with torch.cuda.device(keys.device):
+        s = _stream_handle(keys)
+        if values is None:
+            _lib.check(lib.rdst_hip_sort_segments_device(ptr(keys), ptr(tmp), tmp_elems, n, offp, n_segments, nbytes, kind, levels, s))
+        else:
+            _lib.check(lib.rdst_hip_sort_segments_pairs_device(ptr(keys), ptr(values), ptr(tmp), ptr(tmp_values), tmp_elems, n, offp,
+                                                               n_segments, nbytes, kind, levels, vbytes, s))
+        if check:
+            _lib.check(lib.rdst_hip_device_status(s))
+
+
 def sort_records_by_key(records, key_field):
     """Device route for a slice of structs whose ``RadixKey`` is one built-in field
     (benches/struct_sort.rs:11-27, examples/impl_radix_key.rs:32-56): ``records`` is a 2-D
@@ -585,7 +690,7 @@ def profile_runs() -> int:
     return int(_lib.load().rdst_hip_profile_runs())
 
 
-STAGE_NAMES = {1: "clear", 2: "histogram", 3: "scan", 4: "pass", 5: "copy_back", 6: "histogram16", 7: "route", 8: "local_sort", 10: "msd_pass_a", 11: "msd_pass_b", 12: "sample"}
+STAGE_NAMES = {1: "clear", 2: "histogram", 3: "scan", 4: "pass", 5: "copy_back", 6: "histogram16", 7: "route", 8: "local_sort", 10: "msd_pass_a", 11: "msd_pass_b", 12: "sample", 13: "segments"}
 
 
 def profile_run(run: int, levels: int):

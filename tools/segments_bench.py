@@ -1,0 +1,146 @@
+"""Development aid: the segmented sort (rdst_hip_sort_segments_device / _pairs_device) against a loop of the slice entry
+(rdst_hip_sort_device / rdst_hip_sort_pairs_device) over the same segments — the only way to sort many slices before the
+segmented entries existed.  Both are timed on the host clock from the first call to the end of the stream (the loop is
+launch-bound: its cost is the host's), five repeats each on fresh copies of the same input; the loop calls the C entry
+through ctypes with precomputed pointers.  Writes profiles/segments_bench.json: median and spread (min, max) per shape
+and type, and the two conditions DESIGN.md §2f reports:
+  all-long shape: the segmented entry's median lies within the loop's own run-to-run spread (it runs the same launches);
+  every shape with at least 1 024 batched segments: the segmented entry is faster than the loop.
+usage: python tools/segments_bench.py [--quick] [--out profiles/segments_bench.json]"""
+import argparse
+import ctypes
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np
+import torch
+
+import rdst_amd
+from rdst_amd import _lib
+from rdst_amd.radix_sort import key_info
+
+REPEATS = 5
+
+
+def shapes(quick):
+    rng = np.random.default_rng(0x5E6)
+    lognormal = np.maximum(0, np.exp(rng.normal(np.log(500.0), 1.0, size=1 << 14))).astype(np.int64)
+    out = [("2^16 x 16", np.full(1 << 16, 16, dtype=np.int64)),
+           ("2^14 x 1024", np.full(1 << 14, 1024, dtype=np.int64)),
+           ("2^12 x 16384", np.full(1 << 12, 16384, dtype=np.int64)),
+           ("2^14 log-normal (median 500)", lognormal),
+           ("64 x 2^24", np.full(64, 1 << 24, dtype=np.int64))]
+    if quick:
+        out = [(name, l[:max(4, len(l) // 64)]) for name, l in out]
+    return out
+
+
+def timed(fn, restore):
+    times = []
+    for _ in range(REPEATS):
+        restore()
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        times.append((time.perf_counter() - t0) * 1e3)
+        rdst_amd.device_status()
+    return {"median_ms": statistics.median(times), "min_ms": min(times), "max_ms": max(times), "all_ms": times}
+
+
+def run(name, lengths, kdtype, vdtype):
+    off = np.concatenate([[0], np.cumsum(lengths)]).astype(np.uint64)
+    n = int(off[-1])
+    gen = torch.Generator(device="cuda")
+    gen.manual_seed(7)
+    it = {4: torch.int32, 8: torch.int64}[torch.empty(0, dtype=kdtype).element_size()]
+    info = torch.iinfo(it)
+    src = torch.randint(info.min, info.max, (n,), dtype=it, device="cuda", generator=gen).view(kdtype)
+    keys = torch.empty_like(src)
+    vals = base = None
+    vb = 0
+    if vdtype is not None:
+        base = torch.arange(n, dtype=torch.int32, device="cuda").view(vdtype)
+        vals = torch.empty_like(base)
+        vb = base.element_size()
+    kind, kb, levels = key_info(kdtype)
+    _items, counts, need = rdst_amd.segments_plan(off, n, kdtype, vb)
+    longest = int(lengths.max())
+    tmp = torch.empty(longest, dtype=kdtype, device="cuda")          # scratch for the loop's longest slice and for the long class
+    tmpv = torch.empty(longest, dtype=vdtype, device="cuda") if vdtype is not None else None
+    lib = _lib.load()
+    vp = ctypes.c_void_p
+    stream = vp(torch.cuda.current_stream().cuda_stream)
+    kp, tp = keys.data_ptr(), vp(tmp.data_ptr())
+    starts = [int(x) for x in off[:-1]]
+    lens = [int(x) for x in lengths]
+
+    def restore():
+        keys.copy_(src)
+        if vals is not None:
+            vals.copy_(base)
+
+    def new():
+        rdst_amd.sort_segments_device_tensor(keys, off, tmp=tmp, values=vals, tmp_values=tmpv, check=False)
+
+    if vdtype is None:
+        def loop():
+            f = lib.rdst_hip_sort_device
+            for s, l in zip(starts, lens):
+                rc = f(vp(kp + s * kb), tp, l, kb, kind, levels, stream)
+                if rc:
+                    _lib.check(rc)
+    else:
+        vptr, tvp = vals.data_ptr(), vp(tmpv.data_ptr())
+
+        def loop():
+            f = lib.rdst_hip_sort_pairs_device
+            for s, l in zip(starts, lens):
+                rc = f(vp(kp + s * kb), vp(vptr + s * vb), tp, tvp, l, kb, kind, levels, vb, stream)
+                if rc:
+                    _lib.check(rc)
+
+    r_new = timed(new, restore)
+    got = keys.clone()
+    r_loop = timed(loop, restore)
+    assert torch.equal(got.view(it), keys.view(it)), "the segmented entry and the loop disagree"
+    batched = counts[0] + counts[1]
+    row = {"shape": name, "keys": str(kdtype).replace("torch.", ""), "values": str(vdtype).replace("torch.", "") if vdtype is not None else None,
+           "segments": int(len(lengths)), "n": n, "class_counts": list(counts), "segmented": r_new, "loop": r_loop,
+           "speedup_median": r_loop["median_ms"] / r_new["median_ms"]}
+    if counts[2] == len(lengths):      # all long: the same launches as the loop
+        row["within_loop_spread"] = bool(r_loop["min_ms"] <= r_new["median_ms"] <= r_loop["max_ms"])
+    if batched >= 1024:
+        row["faster_than_loop"] = bool(r_new["median_ms"] < r_loop["median_ms"])
+    print(f"{name:30s} {row['keys']:7s} {str(row['values']):7s} n={n:.2e} classes={counts}: segmented {r_new['median_ms']:9.3f} ms "
+          f"[{r_new['min_ms']:.3f}, {r_new['max_ms']:.3f}]  loop {r_loop['median_ms']:9.3f} ms [{r_loop['min_ms']:.3f}, {r_loop['max_ms']:.3f}]  "
+          f"x{row['speedup_median']:.1f}", flush=True)
+    return row
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--quick", action="store_true", help="a 64th of every shape's segments (a check of the tool itself)")
+    ap.add_argument("--out", default=os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "segments_bench.json"))
+    args = ap.parse_args()
+    rows = []
+    for name, lengths in shapes(args.quick):
+        for kdtype, vdtype in ((torch.uint32, None), (torch.uint64, None), (torch.uint32, torch.uint32)):
+            rows.append(run(name, lengths, kdtype, vdtype))
+            torch.cuda.empty_cache()
+    result = {"tool": "tools/segments_bench.py", "repeats": REPEATS, "quick": args.quick, "device": torch.cuda.get_device_name(0), "rows": rows,
+              "all_long_within_loop_spread": all(r["within_loop_spread"] for r in rows if "within_loop_spread" in r),
+              "batched_faster_than_loop": all(r["faster_than_loop"] for r in rows if "faster_than_loop" in r)}
+    with open(args.out, "w") as f:
+        json.dump(result, f, indent=1)
+        f.write("\n")
+    print(f"all-long within the loop's spread: {result['all_long_within_loop_spread']}; batched shapes faster than the loop: "
+          f"{result['batched_faster_than_loop']}")
+
+
+if __name__ == "__main__":
+    main()
