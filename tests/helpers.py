@@ -793,3 +793,262 @@ def chain_split_cases(n, dtype, seed=77, short=40_000, tiny=700):
         "short": full[:short],
         "tiny": full[:tiny],
     }
+
+
+# ---- the wide [u8; N] route's refinement rounds: rows with a known order, and §2d's loop restated --------------------------
+# The library's constants, quoted from rdst_amd/csrc/rdst_bytes.hip (tests/test_bytes_rounds_inputs.py reads the constexpr
+# lines and compares):
+BYTES_SMALL = 256                # longest run the comparison kernel takes
+CMP_WORDS = 3840                 # its staging budget per wave, in u32 words
+CMP_WAVES = 4                    # runs per workgroup of short_runs_kernel
+BYTES_GRID_CAP = 256 * 16        # GRID_CAP: workgroups (of 256 threads) of the grid-stride kernels
+BYTES_SCAN_TILE = 256 * 16       # SCAN_TILE: items per tile of the scans
+SHORT_RUNS_BLOCKS = 1 << 20      # bytes_order: `if (blocks > (1u << 20)) blocks = 1u << 20;`
+GRID_ROWS = BYTES_GRID_CAP * 256             # rows one trip of a grid-stride kernel covers
+SHORT_RUNS_PER_TRIP = SHORT_RUNS_BLOCKS * CMP_WAVES
+
+ROUND_KINDS = ("word0", "later", "last", "straddle", "dup")   # where a run's deciding bytes fall; "+dups": a third repeats
+ROUND_ID_BITS = 16               # ids stay below 2^16: the int64 (run, id) key is run << 16 | id
+
+
+def run_is_long(length, words):
+    """run_is_long of rdst_bytes.hip: too many rows for four per lane, or too many words to stage"""
+    return length > BYTES_SMALL or length * words > CMP_WORDS
+
+
+def long_round_bits(long_runs):
+    """(b, k) of a long round: b = ceil(log2(long runs)) bits of run ordinal, k = (64 - b) / 8 whole key bytes"""
+    b = 0 if long_runs <= 1 else (long_runs - 1).bit_length()
+    return b, (64 - b) // 8
+
+
+def _trips(items, per_trip):
+    return -(-items // per_trip)
+
+
+def bytes_first_round(lengths, N):
+    """The first refinement round of rows whose 8-byte prefixes differ from run to run, from the runs' lengths alone (what
+    bytes_round_census reports as its round 0): the form the full-size device cases are held to."""
+    lengths = np.asarray(lengths, dtype=np.int64)
+    words = (N - 8 + 3) // 4
+    tied = lengths[lengths >= 2]
+    is_long = (tied > BYTES_SMALL) | (tied * words > CMP_WORDS)
+    long, short = tied[is_long], tied[~is_long]
+    b, k = long_round_bits(len(long))
+    m = int(lengths.sum())
+    return dict(depth=8, words=words, m=m, tied=int(tied.sum()), runs=len(tied), long_rows=int(long.sum()), long_runs=len(long),
+                b=b, k=k, short_max=int(short.max()) if len(short) else 0, scan_trips=_trips(m, GRID_ROWS),
+                short_trips=_trips(len(short), SHORT_RUNS_PER_TRIP), long_trips=_trips(int(long.sum()), GRID_ROWS))
+
+
+def bytes_round_census(rows_sorted, N):
+    """DESIGN.md §2d's loop restated in numpy over the SORTED rows (n, N): one dict per refinement round with what the host
+    reads (tied rows, runs, long rows, long runs), the round's depth, words, b and k, the longest short run, and the trips the
+    grid-stride loops make: `scan_trips` long_rows_kernel over the round's m rows, `short_trips` short_runs_kernel over its
+    runs (0: not launched), `long_trips` bytes_keys_kernel and both slot kernels over the long rows."""
+    rows = np.asarray(rows_sorted)
+    n = rows.shape[0]
+    assert rows.shape == (n, N) and rows.dtype == np.uint8 and N > 8
+    # group[i]: the rows i - 1 and i are still tied; active: the rows the round looks at (positions in sorted order)
+    same = np.ones(n, dtype=bool)
+    same[1:] = (rows[1:, :8] == rows[:-1, :8]).all(axis=1)
+    same[0] = False
+    active = np.arange(n)
+    depth, out = 8, []
+    while depth < N:
+        words = (N - depth + 3) // 4
+        m = len(active)
+        heads = np.flatnonzero(~same[active]) if m else np.arange(0)      # run heads among the active rows
+        lens = np.diff(np.append(heads, m))
+        tied_mask = lens >= 2
+        tlen, thead = lens[tied_mask], heads[tied_mask]
+        long_mask = (tlen > BYTES_SMALL) | (tlen * words > CMP_WORDS)
+        long_runs, long_rows = int(long_mask.sum()), int(tlen[long_mask].sum())
+        b, k = long_round_bits(long_runs)
+        short = tlen[~long_mask]
+        out.append(dict(depth=depth, words=words, m=m, tied=int(tlen.sum()), runs=len(tlen), long_rows=long_rows, long_runs=long_runs,
+                        b=b, k=k, short_max=int(short.max()) if len(short) else 0, scan_trips=_trips(m, GRID_ROWS),
+                        short_trips=_trips(len(short), SHORT_RUNS_PER_TRIP), long_trips=_trips(long_rows, GRID_ROWS)))
+        if len(tlen) == 0 or long_runs == 0:
+            break
+        keep = np.concatenate([np.arange(h, h + l) for h, l in zip(thead[long_mask], tlen[long_mask])])
+        nxt = active[keep]
+        first = np.zeros(len(nxt), dtype=bool)
+        first[np.cumsum(tlen[long_mask])[:-1]] = True
+        first[0] = True
+        chunk = rows[nxt, depth:min(depth + k, N)]                         # (bytes past N are zero for every row)
+        differs = np.ones(len(nxt), dtype=bool)
+        differs[1:] = (chunk[1:] != chunk[:-1]).any(axis=1)
+        same = same.copy()
+        same[nxt] = ~(first | differs)
+        active, depth = nxt, depth + k
+    return out
+
+
+def spread_runs(runs, singles):
+    """`runs` spread evenly among `singles` unrelated rows (runs of one row): the list bytes_round_rows takes"""
+    out, gap = [], singles // (len(runs) + 1)
+    for r in runs:
+        out += [(1, "word0")] * gap + [r]
+    return out + [(1, "word0")] * (singles - gap * len(runs))
+
+
+def _mix(x):
+    """a byte from an int64 (wrapping multiply, a middle byte of the product)"""
+    return ((x * 0x2545F4914F6CDD1D) >> 29) & 0xFF
+
+
+def bytes_round_rows(torch, lengths, kinds, N, k=8, seed=0, device="cpu", dups=None):
+    """Rows of [u8; N], N > 8, whose sorted order is known without sorting.  Run r (lengths[r] rows) has the big-endian prefix
+    r * scale + (an offset below scale): strictly increasing.  The N - 8 bytes behind it come from a per-row integer id, in
+    the field its kind names, big-endian — before the field every byte is the run's own, behind it a function of (run, id) —
+    so id order is the lexicographic order and equal ids are equal rows:
+      word0      ids in suffix bytes [0, 2): decided in the comparison kernel's first word
+      later      ids in the first two bytes of suffix word 1 + run % (whole words - 1): word 0 never decides
+      last       ids in the last byte alone (0x00 and 0x01 among them); more than 256 rows repeat
+      straddle   id = hi << 8 | lo, hi at row byte 8 + k - 1, lo at 8 + k, sixteen rows to a hi: the round that takes k bytes
+                 leaves them tied in sixteens, the next byte separates them
+      dup        every row the same
+    `kinds`: indices into ROUND_KINDS; `dups`: runs in which every third row repeats the row before it.  `lengths`, `kinds`,
+    `dups`: sequences or tensors, one entry per run.  Returns a dict: `sorted` (n, N) uint8, `rows` = sorted[perm] with a
+    seeded `perm`, `key` (the int64 run << 16 | id of the sorted rows) and `key_shuffled` = key[perm]."""
+    i64 = torch.int64
+    lengths = torch.as_tensor(lengths, dtype=i64, device=device)
+    kinds = torch.as_tensor(kinds, dtype=i64, device=device)
+    dups = torch.zeros_like(lengths, dtype=torch.bool) if dups is None else torch.as_tensor(dups, dtype=torch.bool, device=device)
+    R, S = lengths.numel(), N - 8
+    assert N > 8 and 1 <= k <= 8 and int(lengths.min()) >= 1 and int(lengths.max()) <= 4096
+    n = int(lengths.sum())
+    run = torch.repeat_interleave(torch.arange(R, device=device, dtype=i64), lengths)
+    start = torch.cumsum(lengths, 0) - lengths
+    i = torch.arange(n, device=device, dtype=i64) - start[run]
+    ln, kd = lengths[run], kinds[run]
+    j = i - (dups[run] & (i % 3 == 2)).to(i64)
+    W0, LATER, LAST, STRADDLE, DUP = range(5)
+    if bool((kinds == LATER).any()):
+        assert S >= 6, "no word behind word 0 to decide in"
+    if bool((kinds == STRADDLE).any()):
+        assert k + 1 <= S, "the straddled byte pair lies past N"
+    width = torch.where(kd == LAST, 1, 2)
+    cap = torch.where(kd == LAST, 256, 65536)
+    stride = torch.clamp((cap - 1) // torch.clamp(ln - 1, min=1), min=1)
+    ident = torch.where(ln <= cap, torch.where(j == 1, 1, j * stride), j * cap // ln)
+    ident = torch.where(kd == STRADDLE, (j // 16) * 256 + (j % 16) * 17, ident)
+    ident = torch.where(kd == DUP, 0, ident)
+    assert int(ident.max()) < (1 << ROUND_ID_BITS)
+    later_words = max(1, (S - 2) // 4)                       # the words 1 .. later_words hold two whole bytes
+    f0 = torch.where(kd == W0, 0, torch.where(kd == LATER, 4 * (1 + run % later_words), torch.where(kd == LAST, S - 1, k - 1)))
+    f0 = torch.where(kd == DUP, S, f0)
+    width = torch.where(kd == DUP, 0, width)
+    # the prefix
+    scale = ((1 << 63) - 1) // R
+    v = run * scale + ((run * 2654435761) & 0x7FFFFFFF) % scale
+    shifts = torch.arange(56, -8, -8, device=device, dtype=i64)
+    prefix = (v[:, None] >> shifts[None, :]) & 0xFF
+    # the suffix
+    P = torch.arange(S, device=device, dtype=i64)[None, :]
+    f0c, wc = f0[:, None], width[:, None]
+    own = _mix(run[:, None] * 0x9E3779B1 + P * 0x85EBCA6B + 1)
+    behind = _mix(run[:, None] * 0x9E3779B1 + P * 0x85EBCA6B + (ident[:, None] + 1) * 0xC2B2AE35)
+    field = (ident[:, None] >> (8 * torch.clamp(f0c + wc - 1 - P, min=0, max=7))) & 0xFF
+    suffix = torch.where(P < f0c, own, torch.where(P < f0c + wc, field, behind))
+    rows = torch.cat([prefix, suffix], dim=1).to(torch.uint8)
+    key = (run << ROUND_ID_BITS) | ident
+    gen = torch.Generator(device=device)
+    gen.manual_seed(int(seed))
+    perm = torch.randperm(n, generator=gen, device=device)
+    return {"sorted": rows, "rows": rows[perm], "perm": perm, "key": key, "key_shuffled": key[perm], "N": N, "n": n}
+
+
+def bytes_round_case(torch, runs, N, k=8, seed=0, device="cpu"):
+    """bytes_round_rows for a list of runs (length, kind), kind a name of ROUND_KINDS, "+dups" appended for a run in which a
+    third of the rows repeat"""
+    lengths = [r[0] for r in runs]
+    kinds = [ROUND_KINDS.index(r[1].split("+")[0]) for r in runs]
+    dups = [r[1].endswith("+dups") for r in runs]
+    return bytes_round_rows(torch, lengths, kinds, N, k, seed, device, dups)
+
+
+RECORD_JUNK = 3                  # random bytes directly behind the key: a read past N changes the order
+
+
+def bytes_round_records(case, seed):
+    """The records form of a (host) case: rows `tag(u1) | key(N) | junk(3) | seq(<u4)`, R = N + 8, the key at the odd offset
+    1, random junk directly behind it, seq = arange(n) in shuffled (input) order, tag one of three values.  Returns the raw
+    (n, R) uint8 input, its structured view's dtype, and the two expected outputs: `by_key` — the stable order on the int64
+    (run, id) key — and `by_key_tag_desc` — the stable order on (key ascending, tag descending)."""
+    N, n = case["N"], case["n"]
+    rng = np.random.default_rng(seed)
+    dt = np.dtype({"names": ["tag", "k", "junk", "seq"], "formats": ["u1", ("u1", (N,)), ("u1", (RECORD_JUNK,)), "<u4"],
+                   "offsets": [0, 1, 1 + N, 1 + N + RECORD_JUNK], "itemsize": N + 8})
+    raw = np.zeros((n, dt.itemsize), dtype=np.uint8)
+    raw[:, 0] = rng.integers(0, 3, size=n, dtype=np.uint8)
+    raw[:, 1:1 + N] = case["rows"].cpu().numpy()
+    raw[:, 1 + N:1 + N + RECORD_JUNK] = rng.integers(0, 256, size=(n, RECORD_JUNK), dtype=np.uint8)
+    raw[:, 1 + N + RECORD_JUNK:] = np.arange(n, dtype="<u4").view(np.uint8).reshape(n, 4)
+    key = case["key_shuffled"].cpu().numpy()
+    by_key = raw[np.argsort(key, kind="stable")]
+    by_key_tag = raw[np.argsort(key * 4 + (3 - raw[:, 0].astype(np.int64)), kind="stable")]
+    return {"raw": raw, "dtype": dt, "by_key": by_key, "by_key_tag_desc": by_key_tag}
+
+
+# The cases of tests/test_gpu_bytes_rounds.py, as (name, runs, N, k): built here so that the CPU test of the inputs and the
+# GPU test use the same lists.
+RANK_WIDTHS = (20, 41, 68)       # 3 words; 9 words, the last one byte and three of padding; 15 words
+RANK_LENGTHS = (2, 3, 63, 64, 65, 127, 128, 129, 191, 192, 193, 255, 256)
+RANK_KINDS = ("later", "last+dups", "straddle", "word0+dups", "dup", "later+dups", "last", "straddle+dups", "word0")
+BUDGET_PAIRS = ((68, 256, 257), (72, 240, 241), (1000, 15, 16), (3848, 4, 5), (3849, 3, 4), (4096, 3, 4))   # N, short, long
+LAYOUT_LONG_RUNS = {1: (0, 8), 2: (1, 7), 3: (2, 7), 256: (8, 7), 257: (9, 6), 65536: (16, 6), 65537: (17, 5)}   # -> (b, k)
+LAYOUT_KINDS = ("straddle", "last", "straddle+dups", "last+dups", "dup", "word0")
+STRIDE_PAIRS, STRIDE_MID = 4_200_000, 2_000     # the runs of the short-run grid-stride case
+
+
+def ranking_runs(N):
+    """three runs of every length of RANK_LENGTHS, the kinds dealt round (9 kinds, 39 runs: every length meets three kinds,
+    every kind at least four lengths), among 5 000 unrelated rows; the straddled pair is suffix bytes 3 and 4: the border
+    of the comparison kernel's words 0 and 1"""
+    runs = [(length, RANK_KINDS[(3 * a + rep) % len(RANK_KINDS)]) for a, length in enumerate(RANK_LENGTHS) for rep in range(3)]
+    return spread_runs(runs, 5000), 4
+
+
+def budget_runs(N, short, long):
+    """one run on each side of len * words = CMP_WORDS, distinct rows decided in the last byte, among 40 unrelated rows"""
+    return spread_runs([(short, "last"), (long, "last")], 40), 8
+
+
+def layout_runs(long_runs, scale=1):
+    """`long_runs` runs of 257 rows (the shortest long run), the kinds of LAYOUT_KINDS dealt round, a few short runs and
+    unrelated rows between them; k is the first long round's"""
+    k = long_round_bits(long_runs)[1]
+    runs = [(BYTES_SMALL + 1, LAYOUT_KINDS[r % len(LAYOUT_KINDS)]) for r in range(long_runs)]
+    extra = [(2, "last"), (64, "straddle"), (200, "later+dups"), (256, "last")]
+    step = max(1, long_runs // 4)
+    out = []
+    for r, item in enumerate(runs):
+        if r % step == 0 and r // step < len(extra):
+            out += [(1, "word0")] * 5 + [extra[r // step]]
+        out.append(item)
+    return out + [(1, "word0")] * 5, k
+
+
+def layout_tensors(torch, long_runs, device):
+    """layout_runs(long_runs) without the extras, as tensors: every run 257 rows, kinds and "+dups" as LAYOUT_KINDS deals
+    them (the two largest cases are built on the device)"""
+    r = torch.arange(long_runs, device=device, dtype=torch.int64)
+    names = [ROUND_KINDS.index(kname.split("+")[0]) for kname in LAYOUT_KINDS]
+    kinds = torch.tensor(names, device=device, dtype=torch.int64)[r % len(LAYOUT_KINDS)]
+    dups = torch.tensor([kname.endswith("+dups") for kname in LAYOUT_KINDS], device=device)[r % len(LAYOUT_KINDS)]
+    return torch.full_like(r, BYTES_SMALL + 1), kinds, dups
+
+
+def stride_tensors(torch, device, pairs=STRIDE_PAIRS, mid=STRIDE_MID):
+    """`pairs` runs of 2 rows with `mid` runs of 65 ... 256 rows spread evenly through them, all decided in the last byte
+    (alternately with a third of the rows repeating)"""
+    total = pairs + mid
+    r = torch.arange(total, device=device, dtype=torch.int64)
+    every = total // mid
+    is_mid = (r % every == every // 2) & (r // every < mid)
+    lengths = torch.where(is_mid, 65 + (r // every) * 37 % 192, 2)
+    kinds = torch.full_like(r, ROUND_KINDS.index("last"))
+    dups = is_mid & ((r // every) % 2 == 1)
+    return lengths, kinds, dups
