@@ -208,5 +208,36 @@ void sort_segments(T* dev_keys, std::size_t len, const std::uint64_t* offsets, s
     if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
 }
 
+// The same with the table of borders in DEVICE memory (rdst_hip_sort_segments_device_offsets): dev_offsets holds
+// n_segments + 1 entries of the unsigned type Off (std::uint32_t or std::uint64_t), read in stream order.  dev_scratch:
+// at least segments_device_offsets_scratch_bytes(n_segments) bytes, 256-byte aligned.  tmp_elems == 0: fully asynchronous —
+// an invalid table or a segment beyond the block class leaves the keys untouched and surfaces in rdst_hip_device_status;
+// tmp_elems > 0: longer segments are sorted too, and the call waits once for `stream` to read the plan's counts.
+inline std::size_t segments_device_offsets_scratch_bytes(std::size_t n_segments) {
+    return static_cast<std::size_t>(rdst_hip_sort_segments_device_offsets_scratch_bytes(n_segments));
+}
+template <typename T, typename Off>
+void sort_segments_device_offsets(T* dev_keys, std::size_t len, const Off* dev_offsets, std::size_t n_segments, void* dev_scratch,
+                                  std::size_t scratch_bytes, T* dev_tmp = nullptr, std::size_t tmp_elems = 0, void* stream = nullptr) {
+    static_assert(std::is_unsigned<Off>::value && (sizeof(Off) == 4 || sizeof(Off) == 8), "offsets are 4- or 8-byte unsigned integers");
+    const int rc = rdst_hip_sort_segments_device_offsets(dev_keys, dev_tmp, tmp_elems, len, dev_offsets, sizeof(Off), n_segments, sizeof(T),
+                                                         RadixKey<T>::kind, static_cast<std::uint32_t>(RadixKey<T>::LEVELS), dev_scratch,
+                                                         scratch_bytes, stream);
+    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+}
+// Key-value form (rdst_hip_sort_segments_pairs_device_offsets): 4- or 8-byte keys and values; equal keys keep their order.
+template <typename T, typename V, typename Off>
+void sort_segments_pairs_device_offsets(T* dev_keys, V* dev_vals, std::size_t len, const Off* dev_offsets, std::size_t n_segments,
+                                        void* dev_scratch, std::size_t scratch_bytes, T* dev_tmp_keys = nullptr, V* dev_tmp_vals = nullptr,
+                                        std::size_t tmp_elems = 0, void* stream = nullptr) {
+    static_assert(std::is_unsigned<Off>::value && (sizeof(Off) == 4 || sizeof(Off) == 8), "offsets are 4- or 8-byte unsigned integers");
+    static_assert(std::is_trivially_copyable<V>::value, "values are moved as bytes");
+    const int rc = rdst_hip_sort_segments_pairs_device_offsets(dev_keys, dev_vals, dev_tmp_keys, dev_tmp_vals, tmp_elems, len, dev_offsets,
+                                                               sizeof(Off), n_segments, sizeof(T), RadixKey<T>::kind,
+                                                               static_cast<std::uint32_t>(RadixKey<T>::LEVELS), sizeof(V), dev_scratch,
+                                                               scratch_bytes, stream);
+    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+}
+
 }  // namespace rdst
 #endif  // RDST_HPP

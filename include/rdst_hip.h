@@ -99,7 +99,7 @@ typedef enum {
     RDST_STAGE_MSD_A = 10,   /* atomic route: scatter by the top byte into over-provisioned areas (claims instead of counts) */
     RDST_STAGE_MSD_B = 11,   /* atomic route: scatter of every area by the second byte into the bucket slots (low halves) */
     RDST_STAGE_SAMPLE = 12,  /* the 8 192-key sample (and, if it flags the keys, K1h + the route decision) before the MSD passes */
-    RDST_STAGE_SEGMENTS = 13 /* segmented sort: the item table's copy and the batched wave-class and block-class launches */
+    RDST_STAGE_SEGMENTS = 13 /* segmented sort: the item table's copy (host offsets) and the batched wave-class and block-class launches */
 } rdst_stage;
 
 /* Device routes (rdst_hip_last_route). */
@@ -218,6 +218,60 @@ typedef struct { uint64_t start; uint32_t len; uint32_t seg; } rdst_segment_item
 int rdst_segments_plan(const uint64_t* offsets, uint64_t n_segments, uint64_t len, uint32_t elem_bytes, uint32_t val_bytes,
                        rdst_segment_item* items_out, uint64_t capacity, uint64_t class_counts_out[3],
                        uint64_t* tmp_elems_out);
+
+/* The same two sorts with the table of borders in DEVICE memory (src/sorter.rs:131-138, as above): a CSR row pointer, the
+ * cumulative sum of a ragged batch's lengths, the bucket borders rdst_hip_split_top_level_device leaves behind — no copy of
+ * the table to the host, no host plan.  dev_offsets: n_segments + 1 unsigned integers of offset_bytes (4 or 8) bytes,
+ * aligned to that size, read only, and read in stream order (the kernel that writes the table may still be running when
+ * the call returns).  4-byte offsets need len < 2^32; n_segments <= 2^30 (RDST_ERR_UNSUPPORTED beyond: the plan's own
+ * sort stays below the lengths rdst_hip_sort_device splits).  Segment semantics, key widths, kinds, `levels`, the classes
+ * and their limits, and the error codes for them are those of the host-offsets entries; every segment ends bit for bit as
+ * rdst_hip_sort_segments_device leaves it, pairs with equal keys keep their input order, nothing outside
+ * [offsets[0], offsets[n_segments]) is written.
+ *
+ * dev_scratch: caller-provided like rdst_hip_sort_bytes_device's, 256-byte aligned, at least
+ * rdst_hip_sort_segments_device_offsets_scratch_bytes(n_segments) bytes.  The plan lives there: a class key and the segment
+ * index per segment, one stable (u32, u32) pair sort of them by the library's own pair route (so rdst_hip_last_route, the
+ * profile runs and rdst_hip_debug_last_sample see that sort too), and the work list — rdst_segments_plan's, item for item.
+ * Stream order makes the scratch reusable by the next call on the same stream.
+ *
+ * tmp_elems chooses between two modes:
+ *   tmp_elems == 0 (tmp pointers may be NULL): FULLY ASYNCHRONOUS.  The call enqueues the plan and the two batched
+ *       launches (grids bounded by what the host knows — n_segments and len —, counts read from the scratch) and returns:
+ *       no copy to or from the host, no wait on an event or on the stream, no staging buffer.  The one exception is the one
+ *       every entry shares: a library workspace that has to grow.  A table the device finds invalid (decreasing, last
+ *       offset past len) or a segment longer than block_max cannot be answered by the return code: NO key or value is
+ *       modified, the bit of value 16 (0x10) of the sticky device error word is set, and rdst_hip_device_status returns RDST_ERR_DEVICE once.
+ *   tmp_elems > 0: for tables that may hold segments beyond block_max, which the host has to enqueue one after another
+ *       (dev_tmp — pairs: dev_tmp_keys, dev_tmp_vals — as their scratch, as above).  One exception to "asynchronous", of
+ *       the kind rdst_hip_sort_device documents for its split: the call WAITS once for `stream` after the plan and reads
+ *       the three counts, the longest long segment and the flags; with long segments it reads their items too (one further
+ *       wait), and long segments beyond the window wait as rdst_hip_sort_device does.  Because the host sees the flags, an
+ *       invalid table, tmp_elems below the longest long segment, or a NULL tmp is RDST_ERR_ARG with nothing sorted and
+ *       nothing left in the error word.
+ * Before any device work — RDST_ERR_ARG: NULL dev_offsets with n_segments > 0, offset_bytes not 4 or 8, 4-byte offsets with
+ * len >= 2^32, tmp_elems > 0 with a NULL tmp, NULL scratch, scratch_bytes too small; RDST_ERR_ALIGN: a misaligned offsets
+ * pointer or scratch; RDST_ERR_UNSUPPORTED: n_segments > 2^30, pair widths other than 4/8 x 4/8.  n_segments == 0 is
+ * RDST_OK and needs no pointers. */
+int rdst_hip_sort_segments_device_offsets(void* dev_keys, void* dev_tmp, uint64_t tmp_elems, uint64_t len,
+                                          const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments,
+                                          uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels,
+                                          void* dev_scratch, uint64_t scratch_bytes, void* stream);
+int rdst_hip_sort_segments_pairs_device_offsets(void* dev_keys, void* dev_vals, void* dev_tmp_keys, void* dev_tmp_vals,
+                                                uint64_t tmp_elems, uint64_t len, const void* dev_offsets, uint32_t offset_bytes,
+                                                uint64_t n_segments, uint32_t key_bytes, rdst_key_kind kind, uint32_t levels,
+                                                uint32_t val_bytes, void* dev_scratch, uint64_t scratch_bytes, void* stream);
+/* The scratch of the two entries above (src/sorter.rs:131-138).  Pure: 32 bytes per segment, rounded up array by array, and a
+ * 256-byte header; 0 for n_segments == 0 or > 2^30. */
+uint64_t rdst_hip_sort_segments_device_offsets_scratch_bytes(uint64_t n_segments);
+/* Test hook (src/sorter.rs:131-138), BLOCKING: runs the device plan and copies out the work list it produced, in
+ * rdst_segments_plan's output form.  *flags_out: 1 = offsets decrease somewhere, 2 = the last offset lies past len (then
+ * RDST_OK with the flags as the answer; counts and items mean nothing); the error word is left alone.  A `capacity` below
+ * the three counts' sum: RDST_ERR_ARG with the counts, *tmp_elems_out and *flags_out written. */
+int rdst_hip_debug_segments_plan_device(const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments, uint64_t len,
+                                        uint32_t elem_bytes, uint32_t val_bytes, void* dev_scratch, uint64_t scratch_bytes,
+                                        rdst_segment_item* items_out, uint64_t capacity, uint64_t class_counts_out[3],
+                                        uint64_t* tmp_elems_out, uint32_t* flags_out, void* stream);
 
 /* [u8; N] rows (N = n_bytes in 1..RDST_BYTES_MAX_N), device-resident, sorted IN PLACE in lexicographic order
  * (src/radix_key_impl.rs:78-85).  No alignment requirement on dev_rows.  dev_scratch: at least

@@ -31,6 +31,10 @@ SYMBOLS = (
     "rdst_hip_sort_segments_pairs_device",
     "rdst_hip_sort_segments_limits",
     "rdst_segments_plan",
+    "rdst_hip_sort_segments_device_offsets",
+    "rdst_hip_sort_segments_pairs_device_offsets",
+    "rdst_hip_sort_segments_device_offsets_scratch_bytes",
+    "rdst_hip_debug_segments_plan_device",
     "rdst_hip_sort_records",
     "rdst_hip_sort_bytes_device",
     "rdst_hip_sort_bytes_scratch_bytes",
@@ -126,6 +130,12 @@ def load():
     lib.rdst_hip_sort_segments_pairs_device.argtypes = [vp, vp, vp, vp, u64, u64, u64p, u64, u32, ci, u32, u32, vp]
     lib.rdst_hip_sort_segments_limits.argtypes = [u32, u32, ctypes.POINTER(u32)]
     lib.rdst_segments_plan.argtypes = [u64p, u64, u64, u32, u32, ctypes.POINTER(SegmentItemC), u64, u64p, u64p]
+    lib.rdst_hip_sort_segments_device_offsets.argtypes = [vp, vp, u64, u64, vp, u32, u64, u32, ci, u32, vp, u64, vp]
+    lib.rdst_hip_sort_segments_pairs_device_offsets.argtypes = [vp, vp, vp, vp, u64, u64, vp, u32, u64, u32, ci, u32, u32, vp, u64, vp]
+    lib.rdst_hip_sort_segments_device_offsets_scratch_bytes.argtypes = [u64]
+    lib.rdst_hip_sort_segments_device_offsets_scratch_bytes.restype = u64
+    lib.rdst_hip_debug_segments_plan_device.argtypes = [vp, u32, u64, u64, u32, u32, vp, u64, ctypes.POINTER(SegmentItemC), u64, u64p, u64p,
+                                                        ctypes.POINTER(u32), vp]
     lib.rdst_hip_sort_records.argtypes = [vp, u64, u32, u32, u32, ci, ctypes.POINTER(HipOptsC)]
     lib.rdst_hip_sort_bytes_device.argtypes = [vp, u64, u32, vp, u64, vp]
     lib.rdst_hip_sort_bytes_scratch_bytes.argtypes = [u64, u32]
@@ -163,7 +173,7 @@ def load():
     lib.rdst_hip_last_error.restype = ctypes.c_char_p
     for name in SYMBOLS:
         if name not in ("rdst_hip_workspace_bytes", "rdst_hip_sort_bytes_scratch_bytes", "rdst_hip_sort_records_by_fields_scratch_bytes",
-                        "rdst_hip_last_error"):
+                        "rdst_hip_sort_segments_device_offsets_scratch_bytes", "rdst_hip_last_error"):
             getattr(lib, name).restype = ctypes.c_int
     _lib = lib
     return lib

@@ -5523,8 +5523,8 @@ int read_device_error(DeviceState& D, hipStream_t s) {
         const uint32_t word = *D.host_err;
         HIP_TRY(hipMemsetAsync(D.err_dev, 0, sizeof(uint32_t), s));  // reported once: the next check starts clean
         HIP_TRY(hipStreamSynchronize(s));
-        char b[256];
-        snprintf(b, sizeof b, "device error word = 0x%x (1 = look-back spin bound expired, 2 = scatter destination out of range, 4 = hybrid-route bucket larger than a tile, 8 = [u8; N] route: a row index or run out of range)", word);
+        char b[448];
+        snprintf(b, sizeof b, "device error word = 0x%x (1 = look-back spin bound expired, 2 = scatter destination out of range, 4 = hybrid-route bucket larger than a tile, 8 = [u8; N] route: a row index or run out of range, 16 = segmented sort: offsets table decreasing, past len, or a segment beyond block_max without tmp)", word);
         return fail(RDST_ERR_DEVICE, b);
     }
     return RDST_OK;

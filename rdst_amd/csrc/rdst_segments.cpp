@@ -49,6 +49,16 @@ extern "C" int rdst_hip_sort_segments_limits(uint32_t elem_bytes, uint32_t val_b
     return RDST_OK;
 }
 
+// Device-resident offsets: what the plan keeps in the caller's scratch.  A 256-byte header; four u32 arrays of n_segments
+// (the class keys and segment indices of the plan's pair sort, and that sort's two tmps), each rounded up to 256 bytes; the
+// item table (16 bytes per segment), rounded up likewise: 32 bytes per segment and at most 1 536 bytes besides.
+extern "C" uint64_t rdst_hip_sort_segments_device_offsets_scratch_bytes(uint64_t n_segments) {
+    if (n_segments == 0 || n_segments > (1ull << 30)) return 0;
+    const uint64_t arr = (n_segments * sizeof(uint32_t) + 255) / 256 * 256;
+    const uint64_t table = (n_segments * sizeof(rdst_segment_item) + 255) / 256 * 256;
+    return 256 + 4 * arr + table;
+}
+
 extern "C" int rdst_segments_plan(const uint64_t* offsets, uint64_t n_segments, uint64_t len, uint32_t elem_bytes, uint32_t val_bytes,
                                   rdst_segment_item* items_out, uint64_t capacity, uint64_t class_counts_out[3],
                                   uint64_t* tmp_elems_out) {

@@ -70,8 +70,8 @@ __device__ __forceinline__ void wave_sync() {
 }
 
 template <typename K, typename V, int LEVELS, bool MAPPED>
-__global__ __launch_bounds__(SEG_WAVES * 64) void segment_wave_kernel(K* __restrict__ keys, V* __restrict__ vals,
-                                                                       const rdst_segment_item* __restrict__ items, uint32_t n_items, K neg, K pos) {
+__device__ __forceinline__ void segment_wave_body(K* __restrict__ keys, V* __restrict__ vals, const rdst_segment_item* __restrict__ items,
+                                                  uint32_t n_items, K neg, K pos) {
     constexpr bool HAS_V = ValBytes<V>::value != 0;
     constexpr int KPT = wave_kpt(sizeof(K));
     constexpr int CAP = 64 * KPT;
@@ -169,8 +169,13 @@ __global__ __launch_bounds__(SEG_WAVES * 64) void segment_wave_kernel(K* __restr
 }
 
 template <typename K, typename V, int LEVELS, bool MAPPED>
-__global__ __launch_bounds__(BLOCK_THREADS) void segment_block_kernel(K* __restrict__ keys, V* __restrict__ vals,
-                                                                      const rdst_segment_item* __restrict__ items, K neg, K pos) {
+__global__ __launch_bounds__(SEG_WAVES * 64) void segment_wave_kernel(K* __restrict__ keys, V* __restrict__ vals,
+                                                                       const rdst_segment_item* __restrict__ items, uint32_t n_items, K neg, K pos) {
+    segment_wave_body<K, V, LEVELS, MAPPED>(keys, vals, items, n_items, neg, pos);
+}
+
+template <typename K, typename V, int LEVELS, bool MAPPED>
+__device__ __forceinline__ void segment_block_body(K* __restrict__ keys, V* __restrict__ vals, const rdst_segment_item it, K neg, K pos) {
     constexpr bool HAS_V = ValBytes<V>::value != 0;
     constexpr int KPT = block_kpt(sizeof(K), ValBytes<V>::value);
     constexpr int TILE = BLOCK_THREADS * KPT;
@@ -180,7 +185,6 @@ __global__ __launch_bounds__(BLOCK_THREADS) void segment_block_kernel(K* __restr
     K* stage = reinterpret_cast<K*>(smem + BLOCK_WAVES * 1024 + 16);                      // [TILE]
     V* vstage = reinterpret_cast<V*>(smem + BLOCK_WAVES * 1024 + 16 + sizeof(K) * TILE);  // [TILE]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const rdst_segment_item it = items[blockIdx.x];  // the grid is exactly this class's items
     const uint32_t n = it.len < (uint32_t)TILE ? it.len : (uint32_t)TILE;  // (the plan never hands this class a longer one)
     K* seg = keys + it.start;
     V* vseg = HAS_V ? vals + it.start : vals;
@@ -261,6 +265,124 @@ __global__ __launch_bounds__(BLOCK_THREADS) void segment_block_kernel(K* __restr
             seg[idx] = MAPPED ? unmap_key<K>(mk[i], neg, pos) : mk[i];
             if constexpr (HAS_V) vseg[idx] = mv[i];
         }
+    }
+}
+
+template <typename K, typename V, int LEVELS, bool MAPPED>
+__global__ __launch_bounds__(BLOCK_THREADS) void segment_block_kernel(K* __restrict__ keys, V* __restrict__ vals,
+                                                                      const rdst_segment_item* __restrict__ items, K neg, K pos) {
+    segment_block_body<K, V, LEVELS, MAPPED>(keys, vals, items[blockIdx.x], neg, pos);  // the grid is exactly this class's items
+}
+
+// ---- the same two bodies with their item range read from a plan header in device memory (device-resident offsets) -------
+//
+// The header is the first 256 bytes of the caller's scratch (rdst_hip_sort_segments_device_offsets_scratch_bytes):
+enum PlanHeader : int {
+    HDR_N_WAVE = 0,      // items of the wave class
+    HDR_N_BLOCK = 1,     // items of the block class (they follow the wave class in the item table)
+    HDR_N_LONG = 2,      // items of the long class
+    HDR_FLAGS = 3,       // PLAN_* bits: what the plan found wrong
+    HDR_LONGEST = 4,     // u64 in the words 4 and 5: the longest long segment
+    HDR_RUN_WAVE = 6,    // the counts the batched kernels run: HDR_N_WAVE and HDR_N_BLOCK, or 0 and 0 when nothing may be sorted
+    HDR_RUN_BLOCK = 7,
+    HDR_WORDS = 64,
+};
+constexpr uint32_t PLAN_DECREASING = 1;  // offsets[s + 1] < offsets[s] somewhere
+constexpr uint32_t PLAN_PAST_LEN = 2;    // offsets[n_segments] > len
+constexpr uint32_t PLAN_LONG_NO_TMP = 4; // asynchronous mode only: a segment beyond block_max, and no tmp to sort it with
+constexpr uint32_t ERR_SEGMENTS_TABLE = 16;  // the device error word's bit for all three (1, 2, 4, 8 and the bits from 8 up are taken)
+
+// The grids are bounds the host can state without the counts; workgroups (waves) past the count return before any barrier.
+template <typename K, typename V, int LEVELS, bool MAPPED>
+__global__ __launch_bounds__(SEG_WAVES * 64) void segment_wave_counted_kernel(K* __restrict__ keys, V* __restrict__ vals,
+                                                                               const rdst_segment_item* __restrict__ items,
+                                                                               const uint32_t* __restrict__ hdr, K neg, K pos) {
+    segment_wave_body<K, V, LEVELS, MAPPED>(keys, vals, items, hdr[HDR_RUN_WAVE], neg, pos);
+}
+
+template <typename K, typename V, int LEVELS, bool MAPPED>
+__global__ __launch_bounds__(BLOCK_THREADS) void segment_block_counted_kernel(K* __restrict__ keys, V* __restrict__ vals,
+                                                                              const rdst_segment_item* __restrict__ items,
+                                                                              const uint32_t* __restrict__ hdr, K neg, K pos) {
+    if (blockIdx.x >= hdr[HDR_RUN_BLOCK]) return;  // block-uniform
+    segment_block_body<K, V, LEVELS, MAPPED>(keys, vals, items[hdr[HDR_N_WAVE] + blockIdx.x], neg, pos);
+}
+
+// ---- the plan on the device ------------------------------------------------------------------------------------------------
+//
+// rdst_segments_plan's work list, item for item, from a table of borders in device memory: a class key per segment, one
+// stable (u32 key, u32 segment) pair sort by the library's own route, and the items written from the sorted pairs.
+//   key 0                        wave class: stays in segment order
+//   key 1 + (block_max - n)      block class: longest first, ties in segment order
+//   key block_max + 2            long class: in segment order
+//   key block_max + 3            fewer than two keys: no item
+// block_max is at most 16 384, so every key lies below 2^16 and the sort's two upper levels hold one digit.
+constexpr int PLAN_THREADS = 256;
+
+template <typename Off>
+__global__ __launch_bounds__(PLAN_THREADS) void segments_keygen_kernel(const Off* __restrict__ offsets, uint32_t n_segments, uint64_t len,
+                                                                       uint32_t wave_max, uint32_t block_max, uint32_t* __restrict__ keys,
+                                                                       uint32_t* __restrict__ segs, uint32_t* __restrict__ hdr) {
+    __shared__ uint32_t s_count[4];  // wave, block, long, flags
+    __shared__ unsigned long long s_longest;
+    const int tid = threadIdx.x, lane = tid & 63;
+    if (tid < 4) s_count[tid] = 0;
+    if (tid == 0) s_longest = 0;
+    __syncthreads();
+    const uint32_t s = blockIdx.x * PLAN_THREADS + (uint32_t)tid;  // n_segments <= 2^30
+    uint32_t cls = 3, flags = 0;
+    uint64_t n = 0;
+    if (s < n_segments) {
+        const uint64_t lo = offsets[s], hi = offsets[s + 1];
+        if (hi < lo) flags |= PLAN_DECREASING;
+        else n = hi - lo;
+        if (s == n_segments - 1 && hi > len) flags |= PLAN_PAST_LEN;
+        cls = n < 2 ? 3u : (n <= wave_max ? 0u : (n <= block_max ? 1u : 2u));
+        keys[s] = cls == 0 ? 0u : (cls == 1 ? 1u + (block_max - (uint32_t)n) : block_max + cls);
+        segs[s] = s;
+    }
+    // per wave one LDS atomic per count, per workgroup one global atomic per count
+#pragma unroll
+    for (uint32_t c = 0; c < 3; ++c) {
+        const uint32_t hits = (uint32_t)__builtin_popcountll(__builtin_amdgcn_ballot_w64(cls == c));
+        if (lane == 0 && hits) atomicAdd(&s_count[c], hits);
+    }
+    if (flags) atomicOr(&s_count[3], flags);             // (an invalid table: nothing is sorted, time does not matter)
+    if (cls == 2) atomicMax(&s_longest, (unsigned long long)n);  // (long segments are few)
+    __syncthreads();
+    if (tid < 3 && s_count[tid]) atomicAdd(&hdr[tid], s_count[tid]);
+    if (tid == 3 && s_count[3]) atomicOr(&hdr[HDR_FLAGS], s_count[3]);
+    if (tid == 4 && s_longest) atomicMax(reinterpret_cast<unsigned long long*>(hdr + HDR_LONGEST), s_longest);
+}
+
+// One thread per sorted pair: position i of the sorted pairs is position i of the work list.  `long_lens`: the unsaturated
+// lengths of the long items, in their order (for the host, which enqueues them).  Thread 0 closes the header: with a flag
+// up — or, with `no_long`, a long segment — the batched kernels get zero counts and `err` (if given) the table bit.
+template <typename Off>
+__global__ __launch_bounds__(PLAN_THREADS) void segments_items_kernel(const Off* __restrict__ offsets, uint32_t n_segments, uint32_t block_max,
+                                                                      const uint32_t* __restrict__ keys, const uint32_t* __restrict__ segs,
+                                                                      rdst_segment_item* __restrict__ items, uint64_t* __restrict__ long_lens,
+                                                                      uint32_t* hdr, uint32_t no_long, uint32_t* err) {
+    const uint32_t i = blockIdx.x * PLAN_THREADS + threadIdx.x;
+    const uint32_t n_wave = hdr[HDR_N_WAVE], n_block = hdr[HDR_N_BLOCK];
+    if (i == 0) {
+        uint32_t flags = hdr[HDR_FLAGS];
+        if (no_long && hdr[HDR_N_LONG] != 0) {
+            flags |= PLAN_LONG_NO_TMP;
+            hdr[HDR_FLAGS] = flags;
+        }
+        hdr[HDR_RUN_WAVE] = flags ? 0u : n_wave;
+        hdr[HDR_RUN_BLOCK] = flags ? 0u : n_block;
+        if (flags && err) atomicOr(err, ERR_SEGMENTS_TABLE);
+    }
+    if (i >= n_segments) return;
+    const uint32_t key = keys[i], seg = segs[i];
+    if (key > block_max + 2 || seg >= n_segments) return;  // no item (and a segment index is never trusted beyond the table)
+    const uint64_t lo = offsets[seg], n = (uint64_t)offsets[seg + 1] - lo;  // (an item's class says offsets[seg + 1] >= lo)
+    items[i] = {lo, (uint32_t)(n < 0xFFFFFFFFull ? n : 0xFFFFFFFFull), seg};
+    if (key == block_max + 2) {
+        const uint32_t j = i - n_wave - n_block;
+        if (j < n_segments) long_lens[j] = n;
     }
 }
 
@@ -420,7 +542,256 @@ int sort_segments(void* keys, void* vals, void* tmp_keys, void* tmp_vals, uint64
     return RDST_OK;
 }
 
+
+// ---- device-resident offsets -------------------------------------------------------------------------------------------------
+
+// The caller's scratch: header, the plan's pair arrays and their tmps, the item table.  The size has one statement,
+// rdst_hip_sort_segments_device_offsets_scratch_bytes (rdst_segments.cpp); plan_scratch() checks this layout against it.
+struct PlanScratch {
+    uint32_t* hdr;
+    uint32_t *keys, *segs, *tmp_keys, *tmp_segs;
+    rdst_segment_item* items;
+    uint64_t* long_lens;  // over the two tmps, which are dead once the pairs are sorted
+};
+
+int plan_scratch(void* scratch, uint64_t n_segments, PlanScratch* out) {
+    const size_t arr = ((size_t)n_segments * sizeof(uint32_t) + 255) / 256 * 256;
+    const size_t table = ((size_t)n_segments * sizeof(rdst_segment_item) + 255) / 256 * 256;
+    char* base = static_cast<char*>(scratch);
+    char* at = base + HDR_WORDS * sizeof(uint32_t);
+    out->hdr = reinterpret_cast<uint32_t*>(base);
+    out->keys = reinterpret_cast<uint32_t*>(at);
+    out->segs = reinterpret_cast<uint32_t*>(at + arr);
+    out->tmp_keys = reinterpret_cast<uint32_t*>(at + 2 * arr);
+    out->tmp_segs = reinterpret_cast<uint32_t*>(at + 3 * arr);
+    out->items = reinterpret_cast<rdst_segment_item*>(at + 4 * arr);
+    out->long_lens = reinterpret_cast<uint64_t*>(at + 2 * arr);
+    static_assert(sizeof(uint64_t) == 2 * sizeof(uint32_t), "the long lengths fit the two tmps");
+    if ((uint64_t)(at + 4 * arr + table - base) != rdst_hip_sort_segments_device_offsets_scratch_bytes(n_segments))
+        return set_error(RDST_ERR_ARG, "segments: the scratch layout and rdst_hip_sort_segments_device_offsets_scratch_bytes disagree");
+    return RDST_OK;
+}
+
+// What the device-offsets entries and the plan hook check alike, before any device work.
+int check_offsets_args(const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments, uint64_t len, const void* scratch, uint64_t scratch_bytes) {
+    if (n_segments > (1ull << 30)) return set_error(RDST_ERR_UNSUPPORTED, "segments: device-resident offsets take at most 2^30 segments");
+    if (offset_bytes != 4 && offset_bytes != 8) return set_error(RDST_ERR_ARG, "segments: offset_bytes must be 4 or 8");
+    if (dev_offsets == nullptr) return set_error(RDST_ERR_ARG, "segments: null offsets");
+    if (reinterpret_cast<uintptr_t>(dev_offsets) % offset_bytes) return set_error(RDST_ERR_ALIGN, "segments: offsets pointer not aligned to offset_bytes");
+    if (offset_bytes == 4 && len >= (1ull << 32)) return set_error(RDST_ERR_ARG, "segments: 4-byte offsets need len below 2^32");
+    if (scratch == nullptr) return set_error(RDST_ERR_ARG, "segments: null scratch");
+    if (reinterpret_cast<uintptr_t>(scratch) % 256) return set_error(RDST_ERR_ALIGN, "segments: scratch not aligned to 256 bytes");
+    if (scratch_bytes < rdst_hip_sort_segments_device_offsets_scratch_bytes(n_segments))
+        return set_error(RDST_ERR_ARG, "segments: scratch_bytes is below rdst_hip_sort_segments_device_offsets_scratch_bytes(n_segments)");
+    return RDST_OK;
+}
+
+// Enqueues the plan: header cleared, class keys, the pair sort (it takes and hands back the workspace itself), items.
+// Callers hold the library's mutex.  Nothing here waits for the device.
+template <typename Off>
+int enqueue_plan_t(const void* dev_offsets, uint64_t n_segments, uint64_t len, const uint32_t lim[2], const PlanScratch& P, bool no_long,
+                   uint32_t* err, hipStream_t s) {
+    const Off* off = static_cast<const Off*>(dev_offsets);
+    const uint32_t nseg = (uint32_t)n_segments;
+    const dim3 grid((uint32_t)((n_segments + PLAN_THREADS - 1) / PLAN_THREADS));
+    SEG_HIP_TRY(hipMemsetAsync(P.hdr, 0, HDR_WORDS * sizeof(uint32_t), s));
+    int rc = launch("segments_keygen_kernel", segments_keygen_kernel<Off>, grid, dim3(PLAN_THREADS), 0, s, off, nseg, len, lim[0], lim[1], P.keys, P.segs, P.hdr);
+    if (rc) return rc;
+    if (n_segments > 1 && (rc = rdst_internal::sort_pairs_slice_locked(P.keys, P.segs, P.tmp_keys, P.tmp_segs, n_segments, 4, RDST_KEY_UNSIGNED, 4, s))) return rc;
+    return launch("segments_items_kernel", segments_items_kernel<Off>, grid, dim3(PLAN_THREADS), 0, s, off, nseg, lim[1],
+                  static_cast<const uint32_t*>(P.keys), static_cast<const uint32_t*>(P.segs), P.items, P.long_lens, P.hdr, no_long ? 1u : 0u, err);
+}
+
+int enqueue_plan(const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments, uint64_t len, uint32_t key_bytes, uint32_t val_bytes,
+                 const PlanScratch& P, bool no_long, uint32_t* err, hipStream_t s) {
+    uint32_t lim[2];
+    if (int rc = rdst_hip_sort_segments_limits(key_bytes, val_bytes, lim)) return rc;
+    if (lim[1] + 3 >= (1u << 16)) return set_error(RDST_ERR_ARG, "segments: the class keys no longer fit 16 bits");
+    return offset_bytes == 4 ? enqueue_plan_t<uint32_t>(dev_offsets, n_segments, len, lim, P, no_long, err, s)
+                             : enqueue_plan_t<uint64_t>(dev_offsets, n_segments, len, lim, P, no_long, err, s);
+}
+
+// The batched launches of the asynchronous mode: grids from what the host knows, counts from the header.
+template <typename K, typename V>
+int launch_counted(K* keys, V* vals, const PlanScratch& P, uint64_t n_segments, uint64_t len, rdst_key_kind kind, hipStream_t s) {
+    constexpr int LEVELS = (int)sizeof(K);
+    constexpr size_t VB = ValBytes<V>::value;
+    if (!limits_match<K, V>()) return set_error(RDST_ERR_ARG, "segments: the kernels' shapes and rdst_hip_sort_segments_limits disagree");
+    unsigned __int128 neg128, pos128;
+    rdst_internal::key_xor_masks(kind, (uint32_t)sizeof(K), &neg128, &pos128);
+    const K neg = (K)neg128, pos = (K)pos128;
+    const bool mapped = neg128 != 0 || pos128 != 0;
+    const rdst_segment_item* items = P.items;
+    const uint32_t* hdr = P.hdr;
+    // a wave-class segment holds at least two keys, a block-class one more than wave_max
+    const uint64_t wave_bound = std::min<uint64_t>(n_segments, len / 2);
+    const uint64_t block_bound = std::min<uint64_t>(n_segments, len / (64u * wave_kpt(sizeof(K)) + 1));
+    int rc = RDST_OK;
+    if (wave_bound) {
+        const dim3 grid((uint32_t)((wave_bound + SEG_WAVES - 1) / SEG_WAVES));
+        rc = mapped ? launch("segment_wave_counted_kernel", segment_wave_counted_kernel<K, V, LEVELS, true>, grid, dim3(SEG_WAVES * 64),
+                             wave_lds_bytes(sizeof(K), VB), s, keys, vals, items, hdr, neg, pos)
+                    : launch("segment_wave_counted_kernel", segment_wave_counted_kernel<K, V, LEVELS, false>, grid, dim3(SEG_WAVES * 64),
+                             wave_lds_bytes(sizeof(K), VB), s, keys, vals, items, hdr, neg, pos);
+        if (rc) return rc;
+    }
+    if (block_bound) {
+        const dim3 grid((uint32_t)block_bound);
+        rc = mapped ? launch("segment_block_counted_kernel", segment_block_counted_kernel<K, V, LEVELS, true>, grid, dim3(BLOCK_THREADS),
+                             block_lds_bytes(sizeof(K), VB), s, keys, vals, items, hdr, neg, pos)
+                    : launch("segment_block_counted_kernel", segment_block_counted_kernel<K, V, LEVELS, false>, grid, dim3(BLOCK_THREADS),
+                             block_lds_bytes(sizeof(K), VB), s, keys, vals, items, hdr, neg, pos);
+    }
+    return rc;
+}
+
+int dispatch_counted(void* keys, void* vals, uint32_t key_bytes, uint32_t val_bytes, const PlanScratch& P, uint64_t n_segments, uint64_t len,
+                     rdst_key_kind kind, hipStream_t s) {
+    NoVal* const none = nullptr;
+    if (val_bytes == 0) {
+        switch (key_bytes) {
+            case 1: return launch_counted(static_cast<uint8_t*>(keys), none, P, n_segments, len, kind, s);
+            case 2: return launch_counted(static_cast<uint16_t*>(keys), none, P, n_segments, len, kind, s);
+            case 4: return launch_counted(static_cast<uint32_t*>(keys), none, P, n_segments, len, kind, s);
+            case 8: return launch_counted(static_cast<uint64_t*>(keys), none, P, n_segments, len, kind, s);
+            default: return launch_counted(static_cast<u128*>(keys), none, P, n_segments, len, kind, s);
+        }
+    }
+    if (key_bytes == 4)
+        return val_bytes == 4 ? launch_counted(static_cast<uint32_t*>(keys), static_cast<uint32_t*>(vals), P, n_segments, len, kind, s)
+                              : launch_counted(static_cast<uint32_t*>(keys), static_cast<uint64_t*>(vals), P, n_segments, len, kind, s);
+    return val_bytes == 4 ? launch_counted(static_cast<uint64_t*>(keys), static_cast<uint32_t*>(vals), P, n_segments, len, kind, s)
+                          : launch_counted(static_cast<uint64_t*>(keys), static_cast<uint64_t*>(vals), P, n_segments, len, kind, s);
+}
+
+// The header as the host reads it (tmp mode and the plan hook): one copy and one wait for `s`.
+struct PlanResult {
+    uint64_t counts[3], longest;
+    uint32_t flags;
+};
+int read_plan(const PlanScratch& P, PlanResult* r, hipStream_t s) {
+    uint32_t h[8] = {};
+    SEG_HIP_TRY(hipMemcpyAsync(h, P.hdr, sizeof h, hipMemcpyDeviceToHost, s));
+    SEG_HIP_TRY(hipStreamSynchronize(s));
+    r->counts[0] = h[HDR_N_WAVE];
+    r->counts[1] = h[HDR_N_BLOCK];
+    r->counts[2] = h[HDR_N_LONG];
+    r->flags = h[HDR_FLAGS];
+    r->longest = (uint64_t)h[HDR_LONGEST] | ((uint64_t)h[HDR_LONGEST + 1] << 32);
+    return RDST_OK;
+}
+
+int flags_error(uint32_t flags) {
+    if (flags & PLAN_DECREASING) return set_error(RDST_ERR_ARG, "segments: offsets must be non-decreasing");
+    return set_error(RDST_ERR_ARG, "segments: the last offset lies past len");
+}
+
+// Both device-offsets entries.  val_bytes == 0: keys only.
+int sort_segments_offsets(void* keys, void* vals, void* tmp_keys, void* tmp_vals, uint64_t tmp_elems, uint64_t len, const void* dev_offsets,
+                          uint32_t offset_bytes, uint64_t n_segments, uint32_t key_bytes, rdst_key_kind kind, uint32_t levels, uint32_t val_bytes,
+                          void* scratch, uint64_t scratch_bytes, void* stream) {
+    const bool pairs = val_bytes != 0;
+    int rc = rdst_internal::check_key_args(keys, n_segments ? len : 0, key_bytes, kind, levels);
+    if (rc) return rc;
+    if (n_segments == 0) return RDST_OK;
+    if ((rc = check_offsets_args(dev_offsets, offset_bytes, n_segments, len, scratch, scratch_bytes))) return rc;
+    if (pairs && vals == nullptr && len != 0) return set_error(RDST_ERR_ARG, "null value pointer");
+    if (pairs && reinterpret_cast<uintptr_t>(vals) % val_bytes) return set_error(RDST_ERR_ALIGN, "value pointer not aligned to the value size");
+    if (tmp_elems != 0 && (tmp_keys == nullptr || (pairs && tmp_vals == nullptr))) return set_error(RDST_ERR_ARG, "segments: tmp_elems > 0 needs a tmp array");
+    if (reinterpret_cast<uintptr_t>(tmp_keys) % key_bytes) return set_error(RDST_ERR_ALIGN, "tmp pointer not aligned to the element size");
+    if (pairs && reinterpret_cast<uintptr_t>(tmp_vals) % val_bytes) return set_error(RDST_ERR_ALIGN, "tmp value pointer not aligned to the value size");
+    PlanScratch P;
+    if ((rc = plan_scratch(scratch, n_segments, &P))) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    const bool async = tmp_elems == 0;
+    uint32_t* err = nullptr;
+    if (async && (rc = rdst_internal::device_error_word(&err))) return rc;  // (takes the mutex itself)
+    std::lock_guard<std::mutex> lock(rdst_internal::library_mutex());
+    if ((rc = enqueue_plan(dev_offsets, offset_bytes, n_segments, len, key_bytes, val_bytes, P, async, err, s))) return rc;
+    if (async) {  // the counts stay on the device
+        if ((rc = rdst_internal::profile_open_run(s))) return rc;
+        if ((rc = dispatch_counted(keys, vals, key_bytes, val_bytes, P, n_segments, len, kind, s))) return rc;
+        return rdst_internal::profile_stage_end(s, RDST_STAGE_SEGMENTS);
+    }
+    PlanResult r;
+    if ((rc = read_plan(P, &r, s))) return rc;  // the one wait of this mode (and one more below, if there are long segments)
+    if (r.flags) return flags_error(r.flags);
+    if (r.counts[2] != 0 && tmp_elems < r.longest) return set_error(RDST_ERR_ARG, "segments: tmp_elems is below the longest segment beyond block_max");
+    const uint64_t batched = r.counts[0] + r.counts[1];
+    if (batched) {
+        if ((rc = rdst_internal::profile_open_run(s))) return rc;
+        if ((rc = dispatch_batched(keys, vals, key_bytes, val_bytes, P.items, r.counts[0], r.counts[1], kind, s))) return rc;
+        if ((rc = rdst_internal::profile_stage_end(s, RDST_STAGE_SEGMENTS))) return rc;
+    }
+    if (r.counts[2] == 0) return RDST_OK;
+    std::vector<rdst_segment_item> long_items((size_t)r.counts[2]);
+    std::vector<uint64_t> long_lens((size_t)r.counts[2]);
+    SEG_HIP_TRY(hipMemcpyAsync(long_items.data(), P.items + batched, long_items.size() * sizeof(rdst_segment_item), hipMemcpyDeviceToHost, s));
+    SEG_HIP_TRY(hipMemcpyAsync(long_lens.data(), P.long_lens, long_lens.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
+    SEG_HIP_TRY(hipStreamSynchronize(s));
+    for (size_t i = 0; i < long_items.size(); ++i) {
+        const uint64_t start = long_items[i].start, n = long_lens[i];
+        if (n > tmp_elems || start > len || n > len - start) return set_error(RDST_ERR_DEVICE, "segments: a long item of the device plan lies outside the array");
+        char* k = static_cast<char*>(keys) + start * key_bytes;
+        rc = pairs ? rdst_internal::sort_pairs_slice_locked(k, static_cast<char*>(vals) + start * val_bytes, tmp_keys, tmp_vals, n, key_bytes, kind, val_bytes, s)
+                   : rdst_internal::sort_slice_locked(k, tmp_keys, n, key_bytes, kind, s);
+        if (rc) return rc;
+    }
+    return RDST_OK;
+}
+
 }  // namespace
+
+extern "C" int rdst_hip_sort_segments_device_offsets(void* dev_keys, void* dev_tmp, uint64_t tmp_elems, uint64_t len, const void* dev_offsets,
+                                                     uint32_t offset_bytes, uint64_t n_segments, uint32_t elem_bytes, rdst_key_kind kind,
+                                                     uint32_t levels, void* dev_scratch, uint64_t scratch_bytes, void* stream) {
+    return sort_segments_offsets(dev_keys, nullptr, dev_tmp, nullptr, tmp_elems, len, dev_offsets, offset_bytes, n_segments, elem_bytes, kind, levels, 0,
+                                 dev_scratch, scratch_bytes, stream);
+}
+
+extern "C" int rdst_hip_sort_segments_pairs_device_offsets(void* dev_keys, void* dev_vals, void* dev_tmp_keys, void* dev_tmp_vals, uint64_t tmp_elems,
+                                                           uint64_t len, const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments,
+                                                           uint32_t key_bytes, rdst_key_kind kind, uint32_t levels, uint32_t val_bytes,
+                                                           void* dev_scratch, uint64_t scratch_bytes, void* stream) {
+    int rc = rdst_internal::check_key_args(dev_keys, n_segments ? len : 0, key_bytes, kind, levels);
+    if (rc) return rc;
+    if (key_bytes != 4 && key_bytes != 8) return set_error(RDST_ERR_UNSUPPORTED, "key-value sorts take 4- or 8-byte keys");
+    if (val_bytes != 4 && val_bytes != 8) return set_error(RDST_ERR_UNSUPPORTED, "key-value sorts carry 4- or 8-byte values");
+    return sort_segments_offsets(dev_keys, dev_vals, dev_tmp_keys, dev_tmp_vals, tmp_elems, len, dev_offsets, offset_bytes, n_segments, key_bytes, kind,
+                                 levels, val_bytes, dev_scratch, scratch_bytes, stream);
+}
+
+extern "C" int rdst_hip_debug_segments_plan_device(const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments, uint64_t len,
+                                                   uint32_t elem_bytes, uint32_t val_bytes, void* dev_scratch, uint64_t scratch_bytes,
+                                                   rdst_segment_item* items_out, uint64_t capacity, uint64_t class_counts_out[3],
+                                                   uint64_t* tmp_elems_out, uint32_t* flags_out, void* stream) {
+    uint32_t lim[2];
+    int rc = rdst_hip_sort_segments_limits(elem_bytes, val_bytes, lim);
+    if (rc) return rc;
+    if (!class_counts_out || !tmp_elems_out || !flags_out) return set_error(RDST_ERR_ARG, "segments_plan_device: null output");
+    class_counts_out[0] = class_counts_out[1] = class_counts_out[2] = 0;
+    *tmp_elems_out = 0;
+    *flags_out = 0;
+    if (n_segments == 0) return RDST_OK;
+    if ((rc = check_offsets_args(dev_offsets, offset_bytes, n_segments, len, dev_scratch, scratch_bytes))) return rc;
+    PlanScratch P;
+    if ((rc = plan_scratch(dev_scratch, n_segments, &P))) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    std::lock_guard<std::mutex> lock(rdst_internal::library_mutex());
+    if ((rc = enqueue_plan(dev_offsets, offset_bytes, n_segments, len, elem_bytes, val_bytes, P, false, nullptr, s))) return rc;
+    PlanResult r;
+    if ((rc = read_plan(P, &r, s))) return rc;
+    for (int c = 0; c < 3; ++c) class_counts_out[c] = r.counts[c];
+    *tmp_elems_out = r.longest;
+    *flags_out = r.flags;
+    const uint64_t total = r.counts[0] + r.counts[1] + r.counts[2];
+    if (r.flags || total == 0) return RDST_OK;  // (an invalid table: the flags are the answer, the items mean nothing)
+    if (total > capacity) return set_error(RDST_ERR_ARG, "segments_plan_device: capacity too small for the work list");
+    if (!items_out) return set_error(RDST_ERR_ARG, "segments_plan_device: null item table");
+    SEG_HIP_TRY(hipMemcpyAsync(items_out, P.items, (size_t)total * sizeof(rdst_segment_item), hipMemcpyDeviceToHost, s));
+    SEG_HIP_TRY(hipStreamSynchronize(s));
+    return RDST_OK;
+}
 
 extern "C" int rdst_hip_sort_segments_device(void* dev_keys, void* dev_tmp, uint64_t tmp_elems, uint64_t len, const uint64_t* offsets,
                                              uint64_t n_segments, uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels, void* stream) {

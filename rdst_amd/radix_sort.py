@@ -208,7 +208,8 @@ def sort_segments_device_tensor(keys, offsets, tmp=None, values=None, tmp_values
     permuted with their keys; equal keys keep their input order.  ``tmp`` (and ``tmp_values``) are needed only when a segment
     is longer than ``segments_limits(...)[1]``: at least as many elements as the longest such segment; they are allocated
     when omitted and needed, and not at all otherwise.  Runs on the tensor's current stream; with ``check`` the call
-    blocks and raises if a kernel reported failure."""
+    blocks and raises if a kernel reported failure.  Offsets that are computed on the device and should stay there:
+    :func:`sort_segments_device_offsets_tensor`."""
     import torch
     if not keys.is_cuda:
         raise ValueError("sort_segments_device_tensor needs a tensor on a HIP device")
@@ -262,6 +263,122 @@ def sort_segments_device_tensor(keys, offsets, tmp=None, values=None, tmp_values
         else:
             _lib.check(lib.rdst_hip_sort_segments_pairs_device(ptr(keys), ptr(values), ptr(tmp), ptr(tmp_values), tmp_elems, n, offp,
                                                                n_segments, nbytes, kind, levels, vbytes, s))
+        if check:
+            _lib.check(lib.rdst_hip_device_status(s))
+
+
+def segments_device_offsets_scratch_bytes(n_segments):
+    """``rdst_hip_sort_segments_device_offsets_scratch_bytes``: bytes of scratch the device-offsets segmented sort needs for
+    ``n_segments`` segments (0 for none, or for more than 2^30)."""
+    return int(_lib.load().rdst_hip_sort_segments_device_offsets_scratch_bytes(int(n_segments)))
+
+
+def _device_offsets(offsets, keys, n):
+    """(n_segments, offset_bytes) of a device-resident table of borders, checked without looking at its values"""
+    import torch
+    if not _is_torch_tensor(offsets) or not offsets.is_cuda or offsets.device != keys.device:
+        raise ValueError("offsets must be a tensor on the keys' HIP device")
+    if offsets.dim() != 1 or offsets.numel() == 0 or not offsets.is_contiguous():
+        raise ValueError("offsets: a contiguous 1-D tensor of n_segments + 1 element indices")
+    if offsets.dtype not in (torch.int32, torch.int64):
+        raise ValueError("offsets must be int32 or int64 (read as unsigned: a negative value fails the device's check)")
+    if offsets.dtype == torch.int32 and n >= 2**31:
+        raise ValueError("int32 offsets need fewer than 2^31 keys")
+    return offsets.numel() - 1, offsets.element_size()
+
+
+def _offsets_scratch(scratch, n_segments, device):
+    import torch
+    need = segments_device_offsets_scratch_bytes(n_segments)
+    if scratch is None:
+        return torch.empty(max(need, 1), dtype=torch.uint8, device=device), need   # the caching allocator hands out 512-byte aligned blocks
+    if not scratch.is_cuda or scratch.device != device or not scratch.is_contiguous() or scratch.numel() * scratch.element_size() < need:
+        raise ValueError(f"scratch must be a contiguous tensor on the keys' device with at least {need} bytes")
+    return scratch, scratch.numel() * scratch.element_size()
+
+
+def segments_plan_device(offsets, n, dtype, val_bytes=0, scratch=None):
+    """``rdst_hip_debug_segments_plan_device`` (test hook, blocking): the work list the DEVICE plan makes of a device-resident
+    ``offsets`` tensor (int32 / int64) over ``n`` elements — ``(items, counts, tmp_elems, flags)``, the first three as
+    :func:`segments_plan` returns them; ``flags``: 1 = offsets decrease somewhere, 2 = the last offset lies past ``n`` (the
+    other three then mean nothing)."""
+    import torch
+    _kind, nbytes, _levels = key_info(dtype)
+    n_segments, obytes = _device_offsets(offsets, offsets, 0)
+    lib = _lib.load()
+    items = (_lib.SegmentItemC * max(1, n_segments))()
+    counts = (ctypes.c_uint64 * 3)()
+    tmp_elems = ctypes.c_uint64(0)
+    flags = ctypes.c_uint32(0)
+    with torch.cuda.device(offsets.device):
+        scratch, sbytes = _offsets_scratch(scratch, n_segments, offsets.device)
+        _lib.check(lib.rdst_hip_debug_segments_plan_device(ctypes.c_void_p(offsets.data_ptr()), obytes, n_segments, int(n), nbytes, int(val_bytes),
+                                                           ctypes.c_void_p(scratch.data_ptr()), sbytes, items, n_segments, counts,
+                                                           ctypes.byref(tmp_elems), ctypes.byref(flags), _stream_handle(offsets)))
+    total = int(counts[0] + counts[1] + counts[2]) if not flags.value else 0
+    return ([(int(it.start), int(it.len), int(it.seg)) for it in items[:total]], tuple(int(c) for c in counts), int(tmp_elems.value),
+            int(flags.value))
+
+
+def sort_segments_device_offsets_tensor(keys, offsets, tmp=None, values=None, tmp_values=None, scratch=None, check=True, key=None):
+    """``rdst_hip_sort_segments_device_offsets`` (with ``values``: ``rdst_hip_sort_segments_pairs_device_offsets``):
+    :func:`sort_segments_device_tensor` for a table of borders that lives on the device — a CSR row pointer, a ``cumsum`` of
+    lengths — and never visits the host.  ``offsets``: a contiguous 1-D int32 or int64 tensor on the keys' device with
+    n_segments + 1 entries, read as unsigned and in stream order (int32 only below 2^31 keys).  ``scratch``: optional uint8
+    tensor of at least ``segments_device_offsets_scratch_bytes(n_segments)`` bytes, 256-byte aligned (allocated when
+    omitted); calls on one stream may share it.
+
+    ``tmp=None`` is the fully asynchronous mode: nothing is copied to the host and nothing waited for; a table that
+    decreases or ends past the keys, or a segment longer than ``segments_limits(...)[1]``, leaves every key and value as
+    it was and raises from :func:`device_status` (here, with ``check``).  With ``tmp`` (and ``tmp_values`` for pairs; as
+    many elements as the longest segment may have) longer segments are sorted too; the call then waits once for the
+    stream to read the plan's counts, and an invalid table or a ``tmp`` that is too short raises at once."""
+    import torch
+    if not keys.is_cuda:
+        raise ValueError("sort_segments_device_offsets_tensor needs a tensor on a HIP device")
+    if _wide(key):
+        _check_wide_shape(tuple(keys.shape), keys.element_size())
+    elif keys.dim() != 1:
+        raise ValueError("keys must be a contiguous 1-D tensor")
+    if not keys.is_contiguous():
+        raise ValueError("keys must be a contiguous 1-D tensor")
+    kind, nbytes, levels = key_info(key if key else keys.dtype)
+    n = keys.numel() * keys.element_size() // nbytes
+    vbytes = 0
+    if values is not None:
+        if not values.is_cuda or values.device != keys.device or values.dim() != 1 or values.numel() != n or not values.is_contiguous():
+            raise ValueError("values must be a contiguous 1-D tensor of the keys' length on the keys' device")
+        vbytes = values.element_size()
+    n_segments, obytes = _device_offsets(offsets, keys, n)
+    per_key = keys.numel() // n if n else 1      # container elements per key (2 for the 128-bit limbs)
+    tmp_elems = 0
+    if tmp is not None:
+        if tmp.dtype != keys.dtype or not tmp.is_contiguous() or tmp.device != keys.device:
+            raise ValueError("tmp must be a contiguous tensor of the keys' dtype and device")
+        tmp_elems = tmp.numel() // per_key
+        if values is not None:
+            if tmp_values is None:
+                tmp_values = torch.empty(tmp_elems, dtype=values.dtype, device=values.device)
+            elif tmp_values.dtype != values.dtype or not tmp_values.is_contiguous() or tmp_values.device != values.device:
+                raise ValueError("tmp_values must be a contiguous tensor of the values' dtype and device")
+            tmp_elems = min(tmp_elems, tmp_values.numel())
+    elif tmp_values is not None:
+        raise ValueError("tmp_values without tmp")
+
+    def ptr(t):
+        return ctypes.c_void_p(t.data_ptr() if t is not None else None)
+
+    lib = _lib.load()
+    with torch.cuda.device(keys.device):
+        scratch, sbytes = _offsets_scratch(scratch, n_segments, keys.device)
+        s = _stream_handle(keys)
+        if values is None:
+            _lib.check(lib.rdst_hip_sort_segments_device_offsets(ptr(keys), ptr(tmp) if tmp_elems else None, tmp_elems, n, ptr(offsets), obytes,
+                                                                 n_segments, nbytes, kind, levels, ptr(scratch), sbytes, s))
+        else:
+            _lib.check(lib.rdst_hip_sort_segments_pairs_device_offsets(ptr(keys), ptr(values), ptr(tmp) if tmp_elems else None,
+                                                                       ptr(tmp_values) if tmp_elems else None, tmp_elems, n, ptr(offsets), obytes,
+                                                                       n_segments, nbytes, kind, levels, vbytes, ptr(scratch), sbytes, s))
         if check:
             _lib.check(lib.rdst_hip_device_status(s))
 

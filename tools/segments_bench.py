@@ -3,9 +3,12 @@
 segmented entries existed.  Both are timed on the host clock from the first call to the end of the stream (the loop is
 launch-bound: its cost is the host's), five repeats each on fresh copies of the same input; the loop calls the C entry
 through ctypes with precomputed pointers.  Writes profiles/segments_bench.json: median and spread (min, max) per shape
-and type, and the two conditions DESIGN.md §2f reports:
+and type, and the three conditions DESIGN.md §2f reports:
   all-long shape: the segmented entry's median lies within the loop's own run-to-run spread (it runs the same launches);
-  every shape with at least 1 024 batched segments: the segmented entry is faster than the loop.
+  every shape with at least 1 024 batched segments: the segmented entry is faster than the loop;
+  every shape with at least 1 024 batched segments: the device-offsets entry (rdst_hip_sort_segments_device_offsets, the
+  table already in device memory, its scratch allocated once) has its median within the host-offsets entry's run-to-run
+  spread or below it — both measured in the same run.
 usage: python tools/segments_bench.py [--quick] [--out profiles/segments_bench.json]"""
 import argparse
 import ctypes
@@ -87,6 +90,14 @@ def run(name, lengths, kdtype, vdtype):
     def new():
         rdst_amd.sort_segments_device_tensor(keys, off, tmp=tmp, values=vals, tmp_values=tmpv, check=False)
 
+    dev_off = torch.from_numpy(off.astype(np.int64)).cuda()
+    scratch = torch.empty(rdst_amd.segments_device_offsets_scratch_bytes(len(lengths)), dtype=torch.uint8, device="cuda")
+    has_long = counts[2] != 0      # without long segments: the fully asynchronous mode (no tmp)
+
+    def dev():
+        rdst_amd.sort_segments_device_offsets_tensor(keys, dev_off, tmp=tmp if has_long else None, values=vals,
+                                                     tmp_values=tmpv if has_long else None, scratch=scratch, check=False)
+
     if vdtype is None:
         def loop():
             f = lib.rdst_hip_sort_device
@@ -106,18 +117,21 @@ def run(name, lengths, kdtype, vdtype):
 
     r_new = timed(new, restore)
     got = keys.clone()
+    r_dev = timed(dev, restore)
+    assert torch.equal(got.view(it), keys.view(it)), "the host-offsets and the device-offsets entry disagree"
     r_loop = timed(loop, restore)
     assert torch.equal(got.view(it), keys.view(it)), "the segmented entry and the loop disagree"
     batched = counts[0] + counts[1]
     row = {"shape": name, "keys": str(kdtype).replace("torch.", ""), "values": str(vdtype).replace("torch.", "") if vdtype is not None else None,
-           "segments": int(len(lengths)), "n": n, "class_counts": list(counts), "segmented": r_new, "loop": r_loop,
-           "speedup_median": r_loop["median_ms"] / r_new["median_ms"]}
+           "segments": int(len(lengths)), "n": n, "class_counts": list(counts), "segmented": r_new, "device_offsets": r_dev,
+           "device_offsets_mode": "tmp" if has_long else "asynchronous", "loop": r_loop, "speedup_median": r_loop["median_ms"] / r_new["median_ms"]}
     if counts[2] == len(lengths):      # all long: the same launches as the loop
         row["within_loop_spread"] = bool(r_loop["min_ms"] <= r_new["median_ms"] <= r_loop["max_ms"])
     if batched >= 1024:
         row["faster_than_loop"] = bool(r_new["median_ms"] < r_loop["median_ms"])
+        row["device_offsets_within_host_spread_or_below"] = bool(r_dev["median_ms"] <= r_new["max_ms"])
     print(f"{name:30s} {row['keys']:7s} {str(row['values']):7s} n={n:.2e} classes={counts}: segmented {r_new['median_ms']:9.3f} ms "
-          f"[{r_new['min_ms']:.3f}, {r_new['max_ms']:.3f}]  loop {r_loop['median_ms']:9.3f} ms [{r_loop['min_ms']:.3f}, {r_loop['max_ms']:.3f}]  "
+          f"[{r_new['min_ms']:.3f}, {r_new['max_ms']:.3f}]  device offsets {r_dev['median_ms']:9.3f} ms [{r_dev['min_ms']:.3f}, {r_dev['max_ms']:.3f}]  loop {r_loop['median_ms']:9.3f} ms [{r_loop['min_ms']:.3f}, {r_loop['max_ms']:.3f}]  "
           f"x{row['speedup_median']:.1f}", flush=True)
     return row
 
@@ -134,12 +148,15 @@ def main():
             torch.cuda.empty_cache()
     result = {"tool": "tools/segments_bench.py", "repeats": REPEATS, "quick": args.quick, "device": torch.cuda.get_device_name(0), "rows": rows,
               "all_long_within_loop_spread": all(r["within_loop_spread"] for r in rows if "within_loop_spread" in r),
-              "batched_faster_than_loop": all(r["faster_than_loop"] for r in rows if "faster_than_loop" in r)}
+              "batched_faster_than_loop": all(r["faster_than_loop"] for r in rows if "faster_than_loop" in r),
+              "device_offsets_within_host_spread_or_below": all(r["device_offsets_within_host_spread_or_below"] for r in rows
+                                                                if "device_offsets_within_host_spread_or_below" in r)}
     with open(args.out, "w") as f:
         json.dump(result, f, indent=1)
         f.write("\n")
     print(f"all-long within the loop's spread: {result['all_long_within_loop_spread']}; batched shapes faster than the loop: "
-          f"{result['batched_faster_than_loop']}")
+          f"{result['batched_faster_than_loop']}; device offsets within the host-offsets spread or below: "
+          f"{result['device_offsets_within_host_spread_or_below']}")
 
 
 if __name__ == "__main__":
