@@ -239,5 +239,40 @@ void sort_segments_pairs_device_offsets(T* dev_keys, V* dev_vals, std::size_t le
     if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
 }
 
+// Device offsets with no host involvement for segments of ANY length (rdst_hip_sort_segments_device_offsets_nowait): segments
+// beyond the block class are sorted on the device too, tile by tile between the keys and dev_tmp, which holds `len` elements
+// (only the positions of such segments are written).  Nothing is copied to the host and nothing waited for; an invalid table
+// leaves keys, values and tmp untouched and surfaces in rdst_hip_device_status.  dev_scratch: at least
+// segments_nowait_scratch_bytes<T>(n_segments, len) bytes (pairs: <T, V>), 256-byte aligned.  len must be below 2^32.
+template <typename T>
+std::size_t segments_nowait_scratch_bytes(std::size_t n_segments, std::size_t len) {
+    return static_cast<std::size_t>(rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes(n_segments, len, sizeof(T), 0));
+}
+template <typename T, typename V>
+std::size_t segments_nowait_scratch_bytes(std::size_t n_segments, std::size_t len) {
+    return static_cast<std::size_t>(rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes(n_segments, len, sizeof(T), sizeof(V)));
+}
+template <typename T, typename Off>
+void sort_segments_device_offsets_nowait(T* dev_keys, T* dev_tmp, std::size_t len, const Off* dev_offsets, std::size_t n_segments,
+                                         void* dev_scratch, std::size_t scratch_bytes, void* stream = nullptr) {
+    static_assert(std::is_unsigned<Off>::value && (sizeof(Off) == 4 || sizeof(Off) == 8), "offsets are 4- or 8-byte unsigned integers");
+    const int rc = rdst_hip_sort_segments_device_offsets_nowait(dev_keys, dev_tmp, len, dev_offsets, sizeof(Off), n_segments, sizeof(T),
+                                                                RadixKey<T>::kind, static_cast<std::uint32_t>(RadixKey<T>::LEVELS), dev_scratch,
+                                                                scratch_bytes, stream);
+    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+}
+// Key-value form (rdst_hip_sort_segments_pairs_device_offsets_nowait): 4- or 8-byte keys and values; equal keys keep their order.
+template <typename T, typename V, typename Off>
+void sort_segments_device_offsets_nowait(T* dev_keys, V* dev_vals, T* dev_tmp_keys, V* dev_tmp_vals, std::size_t len, const Off* dev_offsets,
+                                         std::size_t n_segments, void* dev_scratch, std::size_t scratch_bytes, void* stream = nullptr) {
+    static_assert(std::is_unsigned<Off>::value && (sizeof(Off) == 4 || sizeof(Off) == 8), "offsets are 4- or 8-byte unsigned integers");
+    static_assert(std::is_trivially_copyable<V>::value, "values are moved as bytes");
+    const int rc = rdst_hip_sort_segments_pairs_device_offsets_nowait(dev_keys, dev_vals, dev_tmp_keys, dev_tmp_vals, len, dev_offsets, sizeof(Off),
+                                                                      n_segments, sizeof(T), RadixKey<T>::kind,
+                                                                      static_cast<std::uint32_t>(RadixKey<T>::LEVELS), sizeof(V), dev_scratch,
+                                                                      scratch_bytes, stream);
+    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+}
+
 }  // namespace rdst
 #endif  // RDST_HPP

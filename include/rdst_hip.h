@@ -99,7 +99,8 @@ typedef enum {
     RDST_STAGE_MSD_A = 10,   /* atomic route: scatter by the top byte into over-provisioned areas (claims instead of counts) */
     RDST_STAGE_MSD_B = 11,   /* atomic route: scatter of every area by the second byte into the bucket slots (low halves) */
     RDST_STAGE_SAMPLE = 12,  /* the 8 192-key sample (and, if it flags the keys, K1h + the route decision) before the MSD passes */
-    RDST_STAGE_SEGMENTS = 13 /* segmented sort: the item table's copy (host offsets) and the batched wave-class and block-class launches */
+    RDST_STAGE_SEGMENTS = 13, /* segmented sort: the item table's copy (host offsets) and the batched wave-class and block-class launches */
+    RDST_STAGE_SEGMENTS_TILED = 14 /* segmented sort, nowait entries: the tiled route's launches for the segments beyond block_max */
 } rdst_stage;
 
 /* Device routes (rdst_hip_last_route). */
@@ -264,6 +265,38 @@ int rdst_hip_sort_segments_pairs_device_offsets(void* dev_keys, void* dev_vals, 
 /* The scratch of the two entries above (src/sorter.rs:131-138).  Pure: 32 bytes per segment, rounded up array by array, and a
  * 256-byte header; 0 for n_segments == 0 or > 2^30. */
 uint64_t rdst_hip_sort_segments_device_offsets_scratch_bytes(uint64_t n_segments);
+/* The device-offsets sorts with NO HOST INVOLVEMENT FOR SEGMENTS OF ANY LENGTH (src/sorter.rs:131-138, as above).  The
+ * arguments are those of the two entries above without tmp_elems: dev_tmp (pairs: dev_tmp_keys, dev_tmp_vals) holds `len`
+ * elements, as for rdst_hip_sort_device.  Segments up to block_max take the two batched launches of the asynchronous mode;
+ * longer ones take a device route of their own ("tiled"): they are cut into tiles of block_max keys and sorted by one
+ * stable counting pass per key byte between the keys and tmp — per level a count launch, a prefix launch and a scatter
+ * launch over all long segments at once, grids bounded by what the host knows (n_segments and len), counts read from the
+ * scratch.  The call enqueues the plan and these launches and returns: no device-to-host copy, no wait on an event or on
+ * the stream, no staging buffer (the one exception is the one every entry shares: a library workspace that has to grow for
+ * the plan's own pair sort).  Every segment ends bit for bit as rdst_hip_sort_segments_device leaves it, pairs with equal
+ * keys keep their input order, nothing outside [offsets[0], offsets[n_segments]) of the keys or values is written, and of
+ * tmp only the positions of segments beyond block_max are written (content afterwards unspecified).
+ * A table the device finds invalid (decreasing, last offset past len): NO key, value or tmp element is modified, bit 0x10
+ * of the device error word is set and rdst_hip_device_status returns RDST_ERR_DEVICE once.  A long segment is no error here.
+ * dev_scratch: 256-byte aligned, at least rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes(n_segments, len,
+ * elem_bytes, val_bytes) bytes.  Before any device work: the errors of the entries above (scratch_bytes against this size
+ * function); len >= 2^32: RDST_ERR_UNSUPPORTED (positions inside an item and tile indices are u32, as on the [u8; N > 16]
+ * route); a NULL tmp with len > 0 and n_segments > 0: RDST_ERR_ARG.  n_segments == 0 is RDST_OK and needs no pointers. */
+int rdst_hip_sort_segments_device_offsets_nowait(void* dev_keys, void* dev_tmp, uint64_t len, const void* dev_offsets,
+                                                 uint32_t offset_bytes, uint64_t n_segments, uint32_t elem_bytes,
+                                                 rdst_key_kind kind, uint32_t levels, void* dev_scratch, uint64_t scratch_bytes,
+                                                 void* stream);
+int rdst_hip_sort_segments_pairs_device_offsets_nowait(void* dev_keys, void* dev_vals, void* dev_tmp_keys, void* dev_tmp_vals,
+                                                       uint64_t len, const void* dev_offsets, uint32_t offset_bytes,
+                                                       uint64_t n_segments, uint32_t key_bytes, rdst_key_kind kind, uint32_t levels,
+                                                       uint32_t val_bytes, void* dev_scratch, uint64_t scratch_bytes, void* stream);
+/* The scratch of the two nowait entries (src/sorter.rs:131-138).  Pure, monotone in n_segments and in len: the plan's layout
+ * (rdst_hip_sort_segments_device_offsets_scratch_bytes) followed by the tiled route's tile_base (n_long_bound + 1 u32),
+ * digit_base (256 u32 per possible long segment) and tile_counts (256 u32 per possible tile), each rounded up to 256 bytes,
+ * with n_long_bound = min(n_segments, len / (block_max + 1)) and len / block_max + n_long_bound tiles at most: 1 KiB per
+ * possible tile, about len / 16 bytes for keys of up to 4 bytes.  0 for n_segments == 0 or > 2^30, len >= 2^32 and unsupported widths. */
+uint64_t rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes(uint64_t n_segments, uint64_t len, uint32_t elem_bytes,
+                                                                    uint32_t val_bytes);
 /* Test hook (src/sorter.rs:131-138), BLOCKING: runs the device plan and copies out the work list it produced, in
  * rdst_segments_plan's output form.  *flags_out: 1 = offsets decrease somewhere, 2 = the last offset lies past len (then
  * RDST_OK with the flags as the answer; counts and items mean nothing); the error word is left alone.  A `capacity` below

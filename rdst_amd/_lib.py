@@ -17,6 +17,7 @@ RDST_BYTES_MAX_N = 4096  # longest [u8; N] key the device route takes (include/r
 RDST_FIELD_DESCENDING = 1  # rdst_key_field.flags: complement the field's mapped bytes
 RDST_KEY_FIELDS_MAX = 16   # fields in one key description
 RDST_STAGE_SEGMENTS = 13   # rdst_stage: the batched launches of the segmented sort
+RDST_STAGE_SEGMENTS_TILED = 14   # rdst_stage: the tiled route of the nowait entries (segments beyond block_max)
 
 # every symbol include/rdst_hip.h declares; tests check that the library exports all of them
 SYMBOLS = (
@@ -34,6 +35,9 @@ SYMBOLS = (
     "rdst_hip_sort_segments_device_offsets",
     "rdst_hip_sort_segments_pairs_device_offsets",
     "rdst_hip_sort_segments_device_offsets_scratch_bytes",
+    "rdst_hip_sort_segments_device_offsets_nowait",
+    "rdst_hip_sort_segments_pairs_device_offsets_nowait",
+    "rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes",
     "rdst_hip_debug_segments_plan_device",
     "rdst_hip_sort_records",
     "rdst_hip_sort_bytes_device",
@@ -134,6 +138,10 @@ def load():
     lib.rdst_hip_sort_segments_pairs_device_offsets.argtypes = [vp, vp, vp, vp, u64, u64, vp, u32, u64, u32, ci, u32, u32, vp, u64, vp]
     lib.rdst_hip_sort_segments_device_offsets_scratch_bytes.argtypes = [u64]
     lib.rdst_hip_sort_segments_device_offsets_scratch_bytes.restype = u64
+    lib.rdst_hip_sort_segments_device_offsets_nowait.argtypes = [vp, vp, u64, vp, u32, u64, u32, ci, u32, vp, u64, vp]
+    lib.rdst_hip_sort_segments_pairs_device_offsets_nowait.argtypes = [vp, vp, vp, vp, u64, vp, u32, u64, u32, ci, u32, u32, vp, u64, vp]
+    lib.rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes.argtypes = [u64, u64, u32, u32]
+    lib.rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes.restype = u64
     lib.rdst_hip_debug_segments_plan_device.argtypes = [vp, u32, u64, u64, u32, u32, vp, u64, ctypes.POINTER(SegmentItemC), u64, u64p, u64p,
                                                         ctypes.POINTER(u32), vp]
     lib.rdst_hip_sort_records.argtypes = [vp, u64, u32, u32, u32, ci, ctypes.POINTER(HipOptsC)]
@@ -173,7 +181,8 @@ def load():
     lib.rdst_hip_last_error.restype = ctypes.c_char_p
     for name in SYMBOLS:
         if name not in ("rdst_hip_workspace_bytes", "rdst_hip_sort_bytes_scratch_bytes", "rdst_hip_sort_records_by_fields_scratch_bytes",
-                        "rdst_hip_sort_segments_device_offsets_scratch_bytes", "rdst_hip_last_error"):
+                        "rdst_hip_sort_segments_device_offsets_scratch_bytes", "rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes",
+                        "rdst_hip_last_error"):
             getattr(lib, name).restype = ctypes.c_int
     _lib = lib
     return lib

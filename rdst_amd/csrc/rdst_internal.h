@@ -53,7 +53,8 @@ struct HostJob {
 };
 
 // The current device's sticky error word (kernels OR bits into it; rdst_hip_device_status reports and clears it).
-int device_error_word(uint32_t** out);
+// `cus_out`, if given: the device's compute-unit count.
+int device_error_word(uint32_t** out, int* cus_out = nullptr);
 
 // [u8; N] rows with N in 1..16, in place on `s`: widened to 4-, 8- or 16-byte integers in `scratch`, sorted by the integer
 // route, narrowed back (the path rdst_hip_sort takes for these widths).  Asynchronous.

@@ -6333,12 +6333,13 @@ int profile_stage_end(hipStream_t s, uint32_t stage) {
     return prof_mark(*D, s, stage);
 }
 
-int device_error_word(uint32_t** out) {
+int device_error_word(uint32_t** out, int* cus_out) {
     std::lock_guard<std::mutex> lock(g_mutex);
     DeviceState* D;
     int rc = current_device_state(&D);
     if (rc) return rc;
     *out = D->err_dev;
+    if (cus_out) *cus_out = D->cus;
     return RDST_OK;
 }
 

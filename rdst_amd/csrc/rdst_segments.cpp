@@ -59,6 +59,27 @@ extern "C" uint64_t rdst_hip_sort_segments_device_offsets_scratch_bytes(uint64_t
     return 256 + 4 * arr + table;
 }
 
+// The nowait entries (rdst_hip_sort_segments_device_offsets_nowait / _pairs_): the plan's layout above, then what the tiled
+// route keeps for the long class.  What the host knows bounds that class: a long segment holds more than block_max keys, so
+// there are at most n_long_bound = min(n_segments, len / (block_max + 1)) of them, and with tiles of T = block_max keys item i
+// has ceil(len_i / T) tiles: at most tiles_bound = len / T + n_long_bound in all.  Behind the plan: tile_base
+// (n_long_bound + 1 u32), digit_base (256 u32 per possible long item), tile_counts (256 u32 per possible tile), each rounded
+// up to 256 bytes.  This is the one statement of the layout (rdst_segments.hip checks its own against it).
+extern "C" uint64_t rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes(uint64_t n_segments, uint64_t len, uint32_t elem_bytes,
+                                                                               uint32_t val_bytes) {
+    const uint64_t plan = rdst_hip_sort_segments_device_offsets_scratch_bytes(n_segments);
+    if (plan == 0 || len >= (1ull << 32)) return 0;
+    if (elem_bytes != 1 && elem_bytes != 2 && elem_bytes != 4 && elem_bytes != 8 && elem_bytes != 16) return 0;
+    if (val_bytes != 0 && ((elem_bytes != 4 && elem_bytes != 8) || (val_bytes != 4 && val_bytes != 8))) return 0;
+    uint32_t block_kpt = elem_bytes <= 4 ? 16u : (elem_bytes == 8 ? 8u : 4u);  // (rdst_hip_sort_segments_limits, without its error notes)
+    if (val_bytes != 0 && elem_bytes + val_bytes > 8) block_kpt = 8u;
+    const uint64_t tile = 1024ull * block_kpt;
+    const uint64_t n_long_bound = std::min<uint64_t>(n_segments, len / (tile + 1));
+    const uint64_t tiles_bound = len / tile + n_long_bound;
+    const auto up = [](uint64_t bytes) { return (bytes + 255) / 256 * 256; };
+    return plan + up((n_long_bound + 1) * sizeof(uint32_t)) + up(n_long_bound * 256 * sizeof(uint32_t)) + up(tiles_bound * 256 * sizeof(uint32_t));
+}
+
 extern "C" int rdst_segments_plan(const uint64_t* offsets, uint64_t n_segments, uint64_t len, uint32_t elem_bytes, uint32_t val_bytes,
                                   rdst_segment_item* items_out, uint64_t capacity, uint64_t class_counts_out[3],
                                   uint64_t* tmp_elems_out) {

@@ -285,6 +285,9 @@ enum PlanHeader : int {
     HDR_LONGEST = 4,     // u64 in the words 4 and 5: the longest long segment
     HDR_RUN_WAVE = 6,    // the counts the batched kernels run: HDR_N_WAVE and HDR_N_BLOCK, or 0 and 0 when nothing may be sorted
     HDR_RUN_BLOCK = 7,
+    HDR_RUN_LONG = 8,    // the tiled route (nowait entries): the long items it serves, or 0 when nothing may be sorted
+    HDR_TILES = 9,       //   their tiles in all
+    HDR_LONG_AT = 10,    //   where they start in the item table: HDR_N_WAVE + HDR_N_BLOCK
     HDR_WORDS = 64,
 };
 constexpr uint32_t PLAN_DECREASING = 1;  // offsets[s + 1] < offsets[s] somewhere
@@ -357,7 +360,8 @@ __global__ __launch_bounds__(PLAN_THREADS) void segments_keygen_kernel(const Off
 
 // One thread per sorted pair: position i of the sorted pairs is position i of the work list.  `long_lens`: the unsaturated
 // lengths of the long items, in their order (for the host, which enqueues them).  Thread 0 closes the header: with a flag
-// up — or, with `no_long`, a long segment — the batched kernels get zero counts and `err` (if given) the table bit.
+// up — or, with `no_long` == 1, a long segment — the batched kernels get zero counts and `err` (if given) the table bit.
+// `no_long` == 2 (the nowait entries): long items are no error, the tiled route sorts them; a flag still zeroes the counts.
 template <typename Off>
 __global__ __launch_bounds__(PLAN_THREADS) void segments_items_kernel(const Off* __restrict__ offsets, uint32_t n_segments, uint32_t block_max,
                                                                       const uint32_t* __restrict__ keys, const uint32_t* __restrict__ segs,
@@ -367,7 +371,7 @@ __global__ __launch_bounds__(PLAN_THREADS) void segments_items_kernel(const Off*
     const uint32_t n_wave = hdr[HDR_N_WAVE], n_block = hdr[HDR_N_BLOCK];
     if (i == 0) {
         uint32_t flags = hdr[HDR_FLAGS];
-        if (no_long && hdr[HDR_N_LONG] != 0) {
+        if (no_long == 1 && hdr[HDR_N_LONG] != 0) {
             flags |= PLAN_LONG_NO_TMP;
             hdr[HDR_FLAGS] = flags;
         }
@@ -573,12 +577,17 @@ int plan_scratch(void* scratch, uint64_t n_segments, PlanScratch* out) {
 }
 
 // What the device-offsets entries and the plan hook check alike, before any device work.
-int check_offsets_args(const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments, uint64_t len, const void* scratch, uint64_t scratch_bytes) {
+int check_offsets_table(const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments, uint64_t len) {
     if (n_segments > (1ull << 30)) return set_error(RDST_ERR_UNSUPPORTED, "segments: device-resident offsets take at most 2^30 segments");
     if (offset_bytes != 4 && offset_bytes != 8) return set_error(RDST_ERR_ARG, "segments: offset_bytes must be 4 or 8");
     if (dev_offsets == nullptr) return set_error(RDST_ERR_ARG, "segments: null offsets");
     if (reinterpret_cast<uintptr_t>(dev_offsets) % offset_bytes) return set_error(RDST_ERR_ALIGN, "segments: offsets pointer not aligned to offset_bytes");
     if (offset_bytes == 4 && len >= (1ull << 32)) return set_error(RDST_ERR_ARG, "segments: 4-byte offsets need len below 2^32");
+    return RDST_OK;
+}
+
+int check_offsets_args(const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments, uint64_t len, const void* scratch, uint64_t scratch_bytes) {
+    if (int rc = check_offsets_table(dev_offsets, offset_bytes, n_segments, len)) return rc;
     if (scratch == nullptr) return set_error(RDST_ERR_ARG, "segments: null scratch");
     if (reinterpret_cast<uintptr_t>(scratch) % 256) return set_error(RDST_ERR_ALIGN, "segments: scratch not aligned to 256 bytes");
     if (scratch_bytes < rdst_hip_sort_segments_device_offsets_scratch_bytes(n_segments))
@@ -589,7 +598,7 @@ int check_offsets_args(const void* dev_offsets, uint32_t offset_bytes, uint64_t 
 // Enqueues the plan: header cleared, class keys, the pair sort (it takes and hands back the workspace itself), items.
 // Callers hold the library's mutex.  Nothing here waits for the device.
 template <typename Off>
-int enqueue_plan_t(const void* dev_offsets, uint64_t n_segments, uint64_t len, const uint32_t lim[2], const PlanScratch& P, bool no_long,
+int enqueue_plan_t(const void* dev_offsets, uint64_t n_segments, uint64_t len, const uint32_t lim[2], const PlanScratch& P, uint32_t no_long,
                    uint32_t* err, hipStream_t s) {
     const Off* off = static_cast<const Off*>(dev_offsets);
     const uint32_t nseg = (uint32_t)n_segments;
@@ -599,11 +608,11 @@ int enqueue_plan_t(const void* dev_offsets, uint64_t n_segments, uint64_t len, c
     if (rc) return rc;
     if (n_segments > 1 && (rc = rdst_internal::sort_pairs_slice_locked(P.keys, P.segs, P.tmp_keys, P.tmp_segs, n_segments, 4, RDST_KEY_UNSIGNED, 4, s))) return rc;
     return launch("segments_items_kernel", segments_items_kernel<Off>, grid, dim3(PLAN_THREADS), 0, s, off, nseg, lim[1],
-                  static_cast<const uint32_t*>(P.keys), static_cast<const uint32_t*>(P.segs), P.items, P.long_lens, P.hdr, no_long ? 1u : 0u, err);
+                  static_cast<const uint32_t*>(P.keys), static_cast<const uint32_t*>(P.segs), P.items, P.long_lens, P.hdr, no_long, err);
 }
 
 int enqueue_plan(const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments, uint64_t len, uint32_t key_bytes, uint32_t val_bytes,
-                 const PlanScratch& P, bool no_long, uint32_t* err, hipStream_t s) {
+                 const PlanScratch& P, uint32_t no_long, uint32_t* err, hipStream_t s) {
     uint32_t lim[2];
     if (int rc = rdst_hip_sort_segments_limits(key_bytes, val_bytes, lim)) return rc;
     if (lim[1] + 3 >= (1u << 16)) return set_error(RDST_ERR_ARG, "segments: the class keys no longer fit 16 bits");
@@ -707,7 +716,7 @@ int sort_segments_offsets(void* keys, void* vals, void* tmp_keys, void* tmp_vals
     uint32_t* err = nullptr;
     if (async && (rc = rdst_internal::device_error_word(&err))) return rc;  // (takes the mutex itself)
     std::lock_guard<std::mutex> lock(rdst_internal::library_mutex());
-    if ((rc = enqueue_plan(dev_offsets, offset_bytes, n_segments, len, key_bytes, val_bytes, P, async, err, s))) return rc;
+    if ((rc = enqueue_plan(dev_offsets, offset_bytes, n_segments, len, key_bytes, val_bytes, P, async ? 1u : 0u, err, s))) return rc;
     if (async) {  // the counts stay on the device
         if ((rc = rdst_internal::profile_open_run(s))) return rc;
         if ((rc = dispatch_counted(keys, vals, key_bytes, val_bytes, P, n_segments, len, kind, s))) return rc;
@@ -740,6 +749,446 @@ int sort_segments_offsets(void* keys, void* vals, void* tmp_keys, void* tmp_vals
     return RDST_OK;
 }
 
+// ---- the tiled route: long segments on the device (the nowait entries) -----------------------------------------------------------
+//
+// The plan leaves the long items behind the batched ones in the item table, in segment order.  A long item is cut into tiles
+// of T = BLOCK_THREADS * block_kpt keys — segment_block_body's tile — and sorted by LEVELS stable counting passes between the
+// keys and tmp (values: vals and tmp_vals), every item over its own range of both arrays:
+//   segments_tiles_kernel        one workgroup: exclusive scan of the items' tile counts into tile_base, the total into the header
+//   per level  segment_tile_count_kernel    a workgroup per tile (grid-stride): 256 digit counts into tile_counts[tile]
+//              segment_tile_offsets_kernel  a workgroup per item: per digit, exclusive prefixes over the item's tiles in place;
+//                                           the 256 totals become the exclusive digit bases digit_base[item]
+//              segment_tile_scatter_kernel  a workgroup per tile: segment_block_body's wave-major layout and ranking, slots
+//                                           starting at digit_base + the tile's prefix + the earlier waves' counts
+//   segment_tile_copy_kernel     one-byte keys only (an odd level count leaves the result in tmp)
+// No kernel waits for another workgroup: every dependency is a kernel boundary.  Every count read from memory is bounded
+// against what the host passed (TileBounds) before it is used, and every store is checked against the item's own length.
+struct TileBounds {
+    uint32_t n_segments;    // the item table's size
+    uint32_t n_long_bound;  // min(n_segments, len / (T + 1))
+    uint32_t tiles_bound;   // len / T + n_long_bound
+    uint32_t tile;          // T
+    uint64_t len;           // below 2^32
+};
+struct TileScratch {
+    uint32_t* tile_base;    // [n_long_bound + 1]
+    uint32_t* digit_base;   // [n_long_bound][256]
+    uint32_t* tile_counts;  // [tiles_bound][256]
+};
+constexpr int TILE_GRID_PER_CU = 4;  // the tile kernels' grids: min(tiles_bound, this * CU count), grid-stride beyond
+
+__global__ __launch_bounds__(BLOCK_THREADS) void segments_tiles_kernel(const rdst_segment_item* __restrict__ items, uint32_t* hdr,
+                                                                       uint32_t* __restrict__ tile_base, TileBounds B, uint32_t* err) {
+    __shared__ uint32_t s_wave[BLOCK_WAVES];
+    __shared__ uint32_t s_bad;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint32_t flags = hdr[HDR_FLAGS], n_long = hdr[HDR_N_LONG];
+    const uint64_t at = (uint64_t)hdr[HDR_N_WAVE] + hdr[HDR_N_BLOCK];
+    const bool off_limits = n_long > B.n_long_bound || at + n_long > B.n_segments;
+    if (flags || off_limits) {  // block-uniform: the header words stay zero (the plan cleared them), nothing later runs
+        if (tid == 0 && !flags && err) atomicOr(err, ERR_SEGMENTS_TABLE);
+        return;
+    }
+    if (tid == 0) s_bad = 0;
+    __syncthreads();
+    uint32_t carry = 0;  // block-uniform: the tiles of the chunks before this one
+    bool bad = false;
+    for (uint32_t base = 0; base < n_long && carry <= B.tiles_bound; base += BLOCK_THREADS) {  // n_long <= n_long_bound
+        const uint32_t i = base + (uint32_t)tid;
+        uint32_t mine = 0;
+        if (i < n_long) {
+            const rdst_segment_item it = items[at + i];
+            if (it.len == 0 || it.start > B.len || it.len > B.len - it.start) bad = true;
+            else mine = (it.len - 1) / B.tile + 1;
+        }
+        uint32_t incl = mine;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const uint32_t y = __shfl_up(incl, o);
+            if (lane >= o) incl += y;
+        }
+        if (lane == 63) s_wave[wave] = incl;
+        __syncthreads();
+        uint32_t before = 0, total = 0;  // a chunk holds at most 1024 * (2^32 / 4096 + 1) tiles: below 2^31
+#pragma unroll
+        for (int w = 0; w < BLOCK_WAVES; ++w) {
+            const uint32_t c = s_wave[w];
+            before += w < wave ? c : 0u;
+            total += c;
+        }
+        if (i < n_long) tile_base[i] = carry + before + incl - mine;
+        carry += total;
+        __syncthreads();
+    }
+    if (bad) s_bad = 1;
+    __syncthreads();
+    if (tid == 0) {
+        const bool ok = s_bad == 0 && carry <= B.tiles_bound;
+        tile_base[n_long] = ok ? carry : 0u;
+        hdr[HDR_LONG_AT] = (uint32_t)at;
+        hdr[HDR_TILES] = ok ? carry : 0u;
+        hdr[HDR_RUN_LONG] = ok ? n_long : 0u;
+        if (!ok && err) atomicOr(err, ERR_SEGMENTS_TABLE);
+    }
+}
+
+// What the tile kernels read from the header, bounded.
+struct TileRun {
+    uint32_t n_long, tiles, at;
+};
+__device__ __forceinline__ TileRun tile_run(const uint32_t* __restrict__ hdr, const TileBounds& B) {
+    TileRun r;
+    r.n_long = hdr[HDR_RUN_LONG];
+    r.tiles = hdr[HDR_TILES];
+    r.at = hdr[HDR_LONG_AT];
+    if (r.n_long == 0 || r.n_long > B.n_long_bound || r.tiles > B.tiles_bound || (uint64_t)r.at + r.n_long > B.n_segments) r.n_long = r.tiles = 0;
+    return r;
+}
+
+// Tile t of the route: its item (a bounded binary search in tile_base: the last i with tile_base[i] <= t), the item's range
+// and the tile's range inside it.  `n` == 0: the tables do not agree with each other, the tile is left alone.
+struct TileRef {
+    uint64_t start;  // the item's first element
+    uint32_t ilen;   // the item's length
+    uint32_t first;  // the tile's first position inside the item
+    uint32_t n;      // the tile's keys: T, or fewer in an item's last tile
+    uint32_t item;
+};
+__device__ __forceinline__ TileRef tile_ref(const rdst_segment_item* __restrict__ items, const uint32_t* __restrict__ tile_base, const TileRun& R,
+                                            const TileBounds& B, uint32_t t) {
+    uint32_t lo = 0, hi = R.n_long;
+    for (int step = 0; step < 32 && hi - lo > 1; ++step) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (tile_base[mid] <= t) lo = mid;
+        else hi = mid;
+    }
+    const rdst_segment_item it = items[R.at + lo];
+    TileRef r;
+    r.item = lo;
+    r.start = it.start;
+    r.ilen = it.len;
+    const uint32_t tb = tile_base[lo];
+    const uint64_t first = (uint64_t)(t - tb) * B.tile;
+    const bool ok = tb <= t && first < it.len && it.start <= B.len && it.len <= B.len - it.start;
+    r.first = ok ? (uint32_t)first : 0u;
+    r.n = ok ? (it.len - r.first < B.tile ? it.len - r.first : B.tile) : 0u;
+    return r;
+}
+
+template <typename K, typename V, bool MAPPED>
+__global__ __launch_bounds__(BLOCK_THREADS) void segment_tile_count_kernel(const K* __restrict__ src, const rdst_segment_item* __restrict__ items,
+                                                                           const uint32_t* __restrict__ hdr, const uint32_t* __restrict__ tile_base,
+                                                                           uint32_t* __restrict__ tile_counts, TileBounds B, int shift, K neg, K pos) {
+    constexpr int KPT = block_kpt(sizeof(K), ValBytes<V>::value);
+    __shared__ uint32_t wave_hist[BLOCK_WAVES * RADIX];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    uint32_t* wh = wave_hist + wave * RADIX;
+    const TileRun R = tile_run(hdr, B);
+    for (uint32_t t = blockIdx.x; t < R.tiles; t += gridDim.x) {  // block-uniform; tiles <= tiles_bound
+        const TileRef T = tile_ref(items, tile_base, R, B, t);
+        const K* seg = src + T.start + T.first;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) wh[lane + 64 * j] = 0;
+#pragma unroll
+        for (int i = 0; i < KPT; ++i) {
+            const uint32_t idx = (uint32_t)tid + (uint32_t)i * BLOCK_THREADS;
+            if (idx < T.n) {
+                K v = seg[idx];
+                if constexpr (MAPPED) v = map_key<K>(v, neg, pos);
+                atomicAdd(&wh[digit_of(v, shift)], 1u);
+            }
+        }
+        __syncthreads();
+        if (tid < RADIX) {
+            uint32_t count_d = 0;
+#pragma unroll
+            for (int w = 0; w < BLOCK_WAVES; ++w) count_d += wave_hist[w * RADIX + tid];
+            tile_counts[(size_t)t * RADIX + tid] = count_d;
+        }
+        __syncthreads();  // the tables are zeroed again at the top
+    }
+}
+
+// One workgroup per long item, four groups of 256 threads: thread d of group g walks the g-th quarter of the item's tiles.
+// First the quarters' sums, then every quarter's exclusive prefixes from the sum of the quarters before it: a single walk of
+// an item of 2^32 - 1 four-byte keys (2^18 tiles) is split in four, and the loads of a walk do not depend on each other.
+constexpr int OFFSET_GROUPS = BLOCK_THREADS / RADIX;
+__global__ __launch_bounds__(BLOCK_THREADS) void segment_tile_offsets_kernel(const uint32_t* __restrict__ hdr, const uint32_t* __restrict__ tile_base,
+                                                                             uint32_t* __restrict__ tile_counts, uint32_t* __restrict__ digit_base,
+                                                                             TileBounds B) {
+    __shared__ uint32_t s_part[OFFSET_GROUPS][RADIX];
+    __shared__ uint32_t s_sum[RADIX / 64];
+    const TileRun R = tile_run(hdr, B);
+    const uint32_t item = blockIdx.x;
+    if (item >= R.n_long) return;  // block-uniform
+    const uint32_t t0 = tile_base[item], t1 = tile_base[item + 1];
+    if (t0 > t1 || t1 > R.tiles) return;  // block-uniform
+    const int tid = threadIdx.x, lane = tid & 63, g = tid >> 8, d = tid & (RADIX - 1);
+    const uint32_t nt = t1 - t0, per = (nt + OFFSET_GROUPS - 1) / OFFSET_GROUPS;
+    const uint32_t a = (uint32_t)g * per < nt ? (uint32_t)g * per : nt, b = nt - a < per ? nt : a + per;
+    uint32_t* col = tile_counts + (size_t)t0 * RADIX + d;
+    uint32_t sum = 0;
+    for (uint32_t j = a; j < b; ++j) sum += col[(size_t)j * RADIX];  // nt <= tiles_bound
+    s_part[g][d] = sum;
+    __syncthreads();
+    uint32_t run = 0, total = 0;
+#pragma unroll
+    for (int q = 0; q < OFFSET_GROUPS; ++q) {
+        const uint32_t c = s_part[q][d];
+        run += q < g ? c : 0u;
+        total += c;
+    }
+    for (uint32_t j = a; j < b; ++j) {
+        const uint32_t c = col[(size_t)j * RADIX];
+        col[(size_t)j * RADIX] = run;
+        run += c;
+    }
+    // group 0 (the waves 0 .. 3): the exclusive scan of the 256 totals
+    uint32_t incl = total;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(incl, o);
+        if (lane >= o) incl += y;
+    }
+    if (g == 0 && lane == 63) s_sum[tid >> 6] = incl;
+    __syncthreads();
+    if (g == 0) {
+        uint32_t base = incl - total;
+        for (int w = 0; w < (tid >> 6); ++w) base += s_sum[w];
+        digit_base[(size_t)item * RADIX + d] = base;
+    }
+}
+
+template <typename K, typename V, bool MAPPED>
+__global__ __launch_bounds__(BLOCK_THREADS) void segment_tile_scatter_kernel(const K* __restrict__ src, K* __restrict__ dst, const V* __restrict__ vsrc,
+                                                                             V* __restrict__ vdst, const rdst_segment_item* __restrict__ items,
+                                                                             const uint32_t* __restrict__ hdr, const uint32_t* __restrict__ tile_base,
+                                                                             const uint32_t* __restrict__ tile_counts,
+                                                                             const uint32_t* __restrict__ digit_base, TileBounds B, int shift, K neg,
+                                                                             K pos) {
+    constexpr bool HAS_V = ValBytes<V>::value != 0;
+    constexpr int KPT = block_kpt(sizeof(K), ValBytes<V>::value);
+    __shared__ uint32_t wave_hist[BLOCK_WAVES * RADIX];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int bit0 = shift & 31;
+    uint32_t* wh = wave_hist + wave * RADIX;
+    const TileRun R = tile_run(hdr, B);
+    for (uint32_t t = blockIdx.x; t < R.tiles; t += gridDim.x) {  // block-uniform; tiles <= tiles_bound
+        const TileRef T = tile_ref(items, tile_base, R, B, t);
+        const K* seg = src + T.start + T.first;
+        const V* vseg = HAS_V ? vsrc + T.start + T.first : vsrc;
+        K* out = dst + T.start;
+        V* vout = HAS_V ? vdst + T.start : vdst;
+        // segment_block_body's layout: key index = wave * 64 * rounds + round * 64 + lane, only as many rounds as the tile needs
+        const int rounds = (int)((T.n + BLOCK_THREADS - 1) / BLOCK_THREADS);
+        const uint32_t wbase = (uint32_t)wave * 64u * (uint32_t)rounds + (uint32_t)lane;
+        K mk[KPT];
+        V mv[KPT];
+#pragma unroll
+        for (int i = 0; i < KPT; ++i) {
+            const uint32_t idx = wbase + i * 64;
+            K v = (K) ~(K)0;
+            if (i < rounds && idx < T.n) {
+                v = seg[idx];
+                if constexpr (MAPPED) v = map_key<K>(v, neg, pos);
+                if constexpr (HAS_V) mv[i] = vseg[idx];
+            }
+            mk[i] = v;
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) wh[lane + 64 * j] = 0;
+#pragma unroll
+        for (int i = 0; i < KPT; ++i)
+            if (i < rounds && wbase + i * 64 < T.n) atomicAdd(&wh[digit_of(mk[i], shift)], 1u);  // slots past the tile's end are not counted
+        __syncthreads();
+        if (tid < RADIX) {
+            uint32_t run = digit_base[(size_t)T.item * RADIX + tid] + tile_counts[(size_t)t * RADIX + tid];
+#pragma unroll
+            for (int w = 0; w < BLOCK_WAVES; ++w) {
+                const uint32_t c = wave_hist[w * RADIX + tid];
+                wave_hist[w * RADIX + tid] = run;
+                run += c;
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int i = 0; i < KPT; ++i) {
+            if (i < rounds) {  // block-uniform: all 64 lanes rank (peers_below needs them)
+                uint32_t* slot = &wh[digit_of(mk[i], shift)];
+                const uint32_t b = *slot;
+                // the slots past the tile's end sit in the lanes above every real key of their round: they change no real key's rank
+                const uint32_t below = peers_below(digit_word<K>(mk[i], shift), bit0);
+                __builtin_amdgcn_wave_barrier();
+                const uint32_t to = b + below;
+                if (wbase + i * 64 < T.n) {
+                    atomicAdd(slot, 1u);
+                    if (to < T.ilen) {  // (always, when the counts are those of these keys)
+                        out[to] = MAPPED ? unmap_key<K>(mk[i], neg, pos) : mk[i];
+                        if constexpr (HAS_V) vout[to] = mv[i];
+                    }
+                }
+            }
+        }
+        __syncthreads();  // the tables are zeroed again at the top
+    }
+}
+
+// One-byte keys: their one level leaves the sorted items in tmp.
+template <typename K, typename V>
+__global__ __launch_bounds__(BLOCK_THREADS) void segment_tile_copy_kernel(const K* __restrict__ src, K* __restrict__ dst, const V* __restrict__ vsrc,
+                                                                          V* __restrict__ vdst, const rdst_segment_item* __restrict__ items,
+                                                                          const uint32_t* __restrict__ hdr, const uint32_t* __restrict__ tile_base,
+                                                                          TileBounds B) {
+    constexpr bool HAS_V = ValBytes<V>::value != 0;
+    constexpr int KPT = block_kpt(sizeof(K), ValBytes<V>::value);
+    const TileRun R = tile_run(hdr, B);
+    for (uint32_t t = blockIdx.x; t < R.tiles; t += gridDim.x) {
+        const TileRef T = tile_ref(items, tile_base, R, B, t);
+        const uint64_t at = T.start + T.first;
+#pragma unroll
+        for (int i = 0; i < KPT; ++i) {
+            const uint32_t idx = (uint32_t)threadIdx.x + (uint32_t)i * BLOCK_THREADS;
+            if (idx < T.n) {
+                dst[at + idx] = src[at + idx];
+                if constexpr (HAS_V) vdst[at + idx] = vsrc[at + idx];
+            }
+        }
+    }
+}
+
+// The tiled layout behind the plan's; checked against the one statement of it.
+int tile_scratch(void* scratch, uint64_t n_segments, uint64_t len, uint32_t key_bytes, uint32_t val_bytes, uint32_t tile, TileBounds* B, TileScratch* out) {
+    B->n_segments = (uint32_t)n_segments;
+    B->n_long_bound = (uint32_t)std::min<uint64_t>(n_segments, len / ((uint64_t)tile + 1));
+    B->tiles_bound = (uint32_t)(len / tile) + B->n_long_bound;
+    B->tile = tile;
+    B->len = len;
+    const auto up = [](size_t bytes) { return (bytes + 255) / 256 * 256; };
+    char* base = static_cast<char*>(scratch);
+    char* at = base + rdst_hip_sort_segments_device_offsets_scratch_bytes(n_segments);
+    out->tile_base = reinterpret_cast<uint32_t*>(at);
+    at += up(((size_t)B->n_long_bound + 1) * sizeof(uint32_t));
+    out->digit_base = reinterpret_cast<uint32_t*>(at);
+    at += up((size_t)B->n_long_bound * RADIX * sizeof(uint32_t));
+    out->tile_counts = reinterpret_cast<uint32_t*>(at);
+    at += up((size_t)B->tiles_bound * RADIX * sizeof(uint32_t));
+    if ((uint64_t)(at - base) != rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes(n_segments, len, key_bytes, val_bytes))
+        return set_error(RDST_ERR_ARG, "segments: the tiled scratch layout and rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes disagree");
+    return RDST_OK;
+}
+
+template <typename K, typename V>
+int launch_tiled(K* keys, V* vals, K* tmp_keys, V* tmp_vals, const PlanScratch& P, const TileScratch& S, const TileBounds& B, int cus, uint32_t* err,
+                 rdst_key_kind kind, hipStream_t s) {
+    constexpr int LEVELS = (int)sizeof(K);
+    static_assert(BLOCK_WAVES * RADIX * sizeof(uint32_t) <= LDS_LIMIT, "a workgroup's LDS stays within 160 KiB");  // the per-wave count tables: 16 KiB
+    if (!limits_match<K, V>() || B.tile != (uint32_t)BLOCK_THREADS * block_kpt(sizeof(K), ValBytes<V>::value))
+        return set_error(RDST_ERR_ARG, "segments: the kernels' shapes and rdst_hip_sort_segments_limits disagree");
+    unsigned __int128 neg128, pos128;
+    rdst_internal::key_xor_masks(kind, (uint32_t)sizeof(K), &neg128, &pos128);
+    const K neg = (K)neg128, pos = (K)pos128;
+    const bool mapped = neg128 != 0 || pos128 != 0;
+    const rdst_segment_item* items = P.items;
+    const uint32_t* hdr = P.hdr;
+    const uint32_t* tile_base = S.tile_base;
+    const dim3 block(BLOCK_THREADS);
+    const dim3 tile_grid(std::min<uint32_t>(B.tiles_bound, (uint32_t)(TILE_GRID_PER_CU * cus)));
+    const dim3 item_grid(B.n_long_bound);
+    int rc = launch("segments_tiles_kernel", segments_tiles_kernel, dim3(1), block, 0, s, items, P.hdr, S.tile_base, B, err);
+    if (rc) return rc;
+    for (int level = 0; level < LEVELS; ++level) {
+        const int shift = level * 8;
+        const K* src = level & 1 ? tmp_keys : keys;
+        K* dst = level & 1 ? keys : tmp_keys;
+        const V* vsrc = level & 1 ? tmp_vals : vals;
+        V* vdst = level & 1 ? vals : tmp_vals;
+        rc = mapped ? launch("segment_tile_count_kernel", segment_tile_count_kernel<K, V, true>, tile_grid, block, 0, s, src, items, hdr, tile_base,
+                             S.tile_counts, B, shift, neg, pos)
+                    : launch("segment_tile_count_kernel", segment_tile_count_kernel<K, V, false>, tile_grid, block, 0, s, src, items, hdr, tile_base,
+                             S.tile_counts, B, shift, neg, pos);
+        if (rc) return rc;
+        if ((rc = launch("segment_tile_offsets_kernel", segment_tile_offsets_kernel, item_grid, block, 0, s, hdr, tile_base, S.tile_counts, S.digit_base, B)))
+            return rc;
+        const uint32_t* counts = S.tile_counts;
+        const uint32_t* bases = S.digit_base;
+        rc = mapped ? launch("segment_tile_scatter_kernel", segment_tile_scatter_kernel<K, V, true>, tile_grid, block, 0, s, src, dst, vsrc, vdst, items, hdr,
+                             tile_base, counts, bases, B, shift, neg, pos)
+                    : launch("segment_tile_scatter_kernel", segment_tile_scatter_kernel<K, V, false>, tile_grid, block, 0, s, src, dst, vsrc, vdst, items, hdr,
+                             tile_base, counts, bases, B, shift, neg, pos);
+        if (rc) return rc;
+    }
+    if constexpr (LEVELS & 1) {
+        const K* src = tmp_keys;
+        const V* vsrc = tmp_vals;
+        rc = launch("segment_tile_copy_kernel", segment_tile_copy_kernel<K, V>, tile_grid, block, 0, s, src, keys, vsrc, vals, items, hdr, tile_base, B);
+    }
+    return rc;
+}
+
+int dispatch_tiled(void* keys, void* vals, void* tmp_keys, void* tmp_vals, uint32_t key_bytes, uint32_t val_bytes, const PlanScratch& P,
+                   const TileScratch& S, const TileBounds& B, int cus, uint32_t* err, rdst_key_kind kind, hipStream_t s) {
+    NoVal* const none = nullptr;
+    if (val_bytes == 0) {
+        switch (key_bytes) {
+            case 1: return launch_tiled(static_cast<uint8_t*>(keys), none, static_cast<uint8_t*>(tmp_keys), none, P, S, B, cus, err, kind, s);
+            case 2: return launch_tiled(static_cast<uint16_t*>(keys), none, static_cast<uint16_t*>(tmp_keys), none, P, S, B, cus, err, kind, s);
+            case 4: return launch_tiled(static_cast<uint32_t*>(keys), none, static_cast<uint32_t*>(tmp_keys), none, P, S, B, cus, err, kind, s);
+            case 8: return launch_tiled(static_cast<uint64_t*>(keys), none, static_cast<uint64_t*>(tmp_keys), none, P, S, B, cus, err, kind, s);
+            default: return launch_tiled(static_cast<u128*>(keys), none, static_cast<u128*>(tmp_keys), none, P, S, B, cus, err, kind, s);
+        }
+    }
+    if (key_bytes == 4)
+        return val_bytes == 4 ? launch_tiled(static_cast<uint32_t*>(keys), static_cast<uint32_t*>(vals), static_cast<uint32_t*>(tmp_keys),
+                                             static_cast<uint32_t*>(tmp_vals), P, S, B, cus, err, kind, s)
+                              : launch_tiled(static_cast<uint32_t*>(keys), static_cast<uint64_t*>(vals), static_cast<uint32_t*>(tmp_keys),
+                                             static_cast<uint64_t*>(tmp_vals), P, S, B, cus, err, kind, s);
+    return val_bytes == 4 ? launch_tiled(static_cast<uint64_t*>(keys), static_cast<uint32_t*>(vals), static_cast<uint64_t*>(tmp_keys),
+                                         static_cast<uint32_t*>(tmp_vals), P, S, B, cus, err, kind, s)
+                          : launch_tiled(static_cast<uint64_t*>(keys), static_cast<uint64_t*>(vals), static_cast<uint64_t*>(tmp_keys),
+                                         static_cast<uint64_t*>(tmp_vals), P, S, B, cus, err, kind, s);
+}
+
+// Both nowait entries.  val_bytes == 0: keys only.  Nothing between here and the return waits for the device or copies to
+// the host: the plan, the two counted launches and the tiled launches are enqueued and the call returns.
+int sort_segments_nowait(void* keys, void* vals, void* tmp_keys, void* tmp_vals, uint64_t len, const void* dev_offsets, uint32_t offset_bytes,
+                         uint64_t n_segments, uint32_t key_bytes, rdst_key_kind kind, uint32_t levels, uint32_t val_bytes, void* scratch,
+                         uint64_t scratch_bytes, void* stream) {
+    const bool pairs = val_bytes != 0;
+    int rc = rdst_internal::check_key_args(keys, n_segments ? len : 0, key_bytes, kind, levels);
+    if (rc) return rc;
+    if (n_segments == 0) return RDST_OK;
+    if ((rc = check_offsets_table(dev_offsets, offset_bytes, n_segments, len))) return rc;
+    if (len >= (1ull << 32)) return set_error(RDST_ERR_UNSUPPORTED, "segments: the nowait entries take len below 2^32 (tile indices and positions inside an item are u32)");
+    if (scratch == nullptr) return set_error(RDST_ERR_ARG, "segments: null scratch");
+    if (reinterpret_cast<uintptr_t>(scratch) % 256) return set_error(RDST_ERR_ALIGN, "segments: scratch not aligned to 256 bytes");
+    if (scratch_bytes < rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes(n_segments, len, key_bytes, val_bytes))
+        return set_error(RDST_ERR_ARG, "segments: scratch_bytes is below rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes(n_segments, len, ...)");
+    if (pairs && vals == nullptr && len != 0) return set_error(RDST_ERR_ARG, "null value pointer");
+    if (pairs && reinterpret_cast<uintptr_t>(vals) % val_bytes) return set_error(RDST_ERR_ALIGN, "value pointer not aligned to the value size");
+    if (len != 0 && (tmp_keys == nullptr || (pairs && tmp_vals == nullptr))) return set_error(RDST_ERR_ARG, "segments: the nowait entries need a tmp array of len elements");
+    if (reinterpret_cast<uintptr_t>(tmp_keys) % key_bytes) return set_error(RDST_ERR_ALIGN, "tmp pointer not aligned to the element size");
+    if (pairs && reinterpret_cast<uintptr_t>(tmp_vals) % val_bytes) return set_error(RDST_ERR_ALIGN, "tmp value pointer not aligned to the value size");
+    uint32_t lim[2];
+    if ((rc = rdst_hip_sort_segments_limits(key_bytes, val_bytes, lim))) return rc;
+    PlanScratch P;
+    if ((rc = plan_scratch(scratch, n_segments, &P))) return rc;
+    TileBounds B;
+    TileScratch S;
+    if ((rc = tile_scratch(scratch, n_segments, len, key_bytes, val_bytes, lim[1], &B, &S))) return rc;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint32_t* err = nullptr;
+    int cus = 0;
+    if ((rc = rdst_internal::device_error_word(&err, &cus))) return rc;  // (takes the mutex itself)
+    std::lock_guard<std::mutex> lock(rdst_internal::library_mutex());
+    if ((rc = enqueue_plan(dev_offsets, offset_bytes, n_segments, len, key_bytes, val_bytes, P, 2u, err, s))) return rc;
+    if ((rc = rdst_internal::profile_open_run(s))) return rc;
+    if ((rc = dispatch_counted(keys, vals, key_bytes, val_bytes, P, n_segments, len, kind, s))) return rc;
+    if ((rc = rdst_internal::profile_stage_end(s, RDST_STAGE_SEGMENTS))) return rc;
+    if (B.n_long_bound == 0) return RDST_OK;  // no segment of this table can be longer than block_max
+    if ((rc = dispatch_tiled(keys, vals, tmp_keys, tmp_vals, key_bytes, val_bytes, P, S, B, cus, err, kind, s))) return rc;
+    return rdst_internal::profile_stage_end(s, RDST_STAGE_SEGMENTS_TILED);
+}
+
 }  // namespace
 
 extern "C" int rdst_hip_sort_segments_device_offsets(void* dev_keys, void* dev_tmp, uint64_t tmp_elems, uint64_t len, const void* dev_offsets,
@@ -761,6 +1210,25 @@ extern "C" int rdst_hip_sort_segments_pairs_device_offsets(void* dev_keys, void*
                                  levels, val_bytes, dev_scratch, scratch_bytes, stream);
 }
 
+extern "C" int rdst_hip_sort_segments_device_offsets_nowait(void* dev_keys, void* dev_tmp, uint64_t len, const void* dev_offsets, uint32_t offset_bytes,
+                                                            uint64_t n_segments, uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels,
+                                                            void* dev_scratch, uint64_t scratch_bytes, void* stream) {
+    return sort_segments_nowait(dev_keys, nullptr, dev_tmp, nullptr, len, dev_offsets, offset_bytes, n_segments, elem_bytes, kind, levels, 0, dev_scratch,
+                                scratch_bytes, stream);
+}
+
+extern "C" int rdst_hip_sort_segments_pairs_device_offsets_nowait(void* dev_keys, void* dev_vals, void* dev_tmp_keys, void* dev_tmp_vals, uint64_t len,
+                                                                  const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments,
+                                                                  uint32_t key_bytes, rdst_key_kind kind, uint32_t levels, uint32_t val_bytes,
+                                                                  void* dev_scratch, uint64_t scratch_bytes, void* stream) {
+    int rc = rdst_internal::check_key_args(dev_keys, n_segments ? len : 0, key_bytes, kind, levels);
+    if (rc) return rc;
+    if (key_bytes != 4 && key_bytes != 8) return set_error(RDST_ERR_UNSUPPORTED, "key-value sorts take 4- or 8-byte keys");
+    if (val_bytes != 4 && val_bytes != 8) return set_error(RDST_ERR_UNSUPPORTED, "key-value sorts carry 4- or 8-byte values");
+    return sort_segments_nowait(dev_keys, dev_vals, dev_tmp_keys, dev_tmp_vals, len, dev_offsets, offset_bytes, n_segments, key_bytes, kind, levels,
+                                val_bytes, dev_scratch, scratch_bytes, stream);
+}
+
 extern "C" int rdst_hip_debug_segments_plan_device(const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments, uint64_t len,
                                                    uint32_t elem_bytes, uint32_t val_bytes, void* dev_scratch, uint64_t scratch_bytes,
                                                    rdst_segment_item* items_out, uint64_t capacity, uint64_t class_counts_out[3],
@@ -778,7 +1246,7 @@ extern "C" int rdst_hip_debug_segments_plan_device(const void* dev_offsets, uint
     if ((rc = plan_scratch(dev_scratch, n_segments, &P))) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
     std::lock_guard<std::mutex> lock(rdst_internal::library_mutex());
-    if ((rc = enqueue_plan(dev_offsets, offset_bytes, n_segments, len, elem_bytes, val_bytes, P, false, nullptr, s))) return rc;
+    if ((rc = enqueue_plan(dev_offsets, offset_bytes, n_segments, len, elem_bytes, val_bytes, P, 0u, nullptr, s))) return rc;
     PlanResult r;
     if ((rc = read_plan(P, &r, s))) return rc;
     for (int c = 0; c < 3; ++c) class_counts_out[c] = r.counts[c];

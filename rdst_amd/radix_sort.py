@@ -383,6 +383,79 @@ def sort_segments_device_offsets_tensor(keys, offsets, tmp=None, values=None, tm
             _lib.check(lib.rdst_hip_device_status(s))
 
 
+def segments_nowait_scratch_bytes(n_segments, n, dtype, val_bytes=0):
+    """``rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes``: bytes of scratch the nowait segmented sort needs for
+    ``n_segments`` segments of an array of ``n`` keys of ``dtype`` (a dtype or a key name, as for :func:`segments_limits`)
+    with ``val_bytes``-byte values (0: keys only).  0 for no segment, more than 2^30 segments, 2^32 keys or more, and widths
+    the sort does not take."""
+    _kind, nbytes, _levels = key_info(dtype)
+    return int(_lib.load().rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes(int(n_segments), int(n), nbytes, int(val_bytes)))
+
+
+def sort_segments_device_offsets_nowait_tensor(keys, offsets, tmp=None, values=None, tmp_values=None, scratch=None, check=True, key=None):
+    """``rdst_hip_sort_segments_device_offsets_nowait`` (with ``values``: ``rdst_hip_sort_segments_pairs_device_offsets_nowait``):
+    :func:`sort_segments_device_offsets_tensor` without a visit to the host for segments of ANY length.  Segments beyond
+    ``segments_limits(...)[1]`` are sorted on the device too, tile by tile between the keys and ``tmp``; nothing is copied to
+    the host and nothing waited for.  ``tmp`` (and ``tmp_values`` for pairs): as many elements as the keys, allocated on the
+    keys' device when omitted; only the positions of long segments are written.  ``scratch``: optional uint8 tensor of at
+    least ``segments_nowait_scratch_bytes(n_segments, n, dtype, val_bytes)`` bytes, 256-byte aligned (allocated when
+    omitted); calls on one stream may share it.  A table that decreases or ends past the keys leaves every key, value and
+    tmp element as it was and raises from :func:`device_status` (here, with ``check``)."""
+    import torch
+    if not keys.is_cuda:
+        raise ValueError("sort_segments_device_offsets_nowait_tensor needs a tensor on a HIP device")
+    if _wide(key):
+        _check_wide_shape(tuple(keys.shape), keys.element_size())
+    elif keys.dim() != 1:
+        raise ValueError("keys must be a contiguous 1-D tensor")
+    if not keys.is_contiguous():
+        raise ValueError("keys must be a contiguous 1-D tensor")
+    kind, nbytes, levels = key_info(key if key else keys.dtype)
+    n = keys.numel() * keys.element_size() // nbytes
+    if n >= 2**32:
+        raise ValueError("the nowait segmented sort takes fewer than 2^32 keys")
+    vbytes = 0
+    if values is not None:
+        if not values.is_cuda or values.device != keys.device or values.dim() != 1 or values.numel() != n or not values.is_contiguous():
+            raise ValueError("values must be a contiguous 1-D tensor of the keys' length on the keys' device")
+        vbytes = values.element_size()
+    elif tmp_values is not None:
+        raise ValueError("tmp_values without values")
+    n_segments, obytes = _device_offsets(offsets, keys, n)
+    if tmp is None:
+        tmp = torch.empty_like(keys)
+    elif tmp.dtype != keys.dtype or not tmp.is_contiguous() or tmp.device != keys.device or tmp.numel() < keys.numel():
+        raise ValueError("tmp must be a contiguous tensor of the keys' dtype and device with at least as many elements")
+    if values is not None:
+        if tmp_values is None:
+            tmp_values = torch.empty_like(values)
+        elif tmp_values.dtype != values.dtype or not tmp_values.is_contiguous() or tmp_values.device != values.device or tmp_values.numel() < n:
+            raise ValueError("tmp_values must be a contiguous tensor of the values' dtype and device with at least as many elements")
+
+    def ptr(t):
+        return ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
+
+    lib = _lib.load()
+    with torch.cuda.device(keys.device):
+        need = int(lib.rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes(n_segments, n, nbytes, vbytes))
+        if scratch is None:
+            scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=keys.device)   # the caching allocator hands out 512-byte aligned blocks
+            sbytes = need
+        elif not scratch.is_cuda or scratch.device != keys.device or not scratch.is_contiguous() or scratch.numel() * scratch.element_size() < need:
+            raise ValueError(f"scratch must be a contiguous tensor on the keys' device with at least {need} bytes")
+        else:
+            sbytes = scratch.numel() * scratch.element_size()
+        s = _stream_handle(keys)
+        if values is None:
+            _lib.check(lib.rdst_hip_sort_segments_device_offsets_nowait(ptr(keys), ptr(tmp), n, ptr(offsets), obytes, n_segments, nbytes, kind, levels,
+                                                                        ptr(scratch), sbytes, s))
+        else:
+            _lib.check(lib.rdst_hip_sort_segments_pairs_device_offsets_nowait(ptr(keys), ptr(values), ptr(tmp), ptr(tmp_values), n, ptr(offsets), obytes,
+                                                                              n_segments, nbytes, kind, levels, vbytes, ptr(scratch), sbytes, s))
+        if check:
+            _lib.check(lib.rdst_hip_device_status(s))
+
+
 def sort_records_by_key(records, key_field):
     """Device route for a slice of structs whose ``RadixKey`` is one built-in field
     (benches/struct_sort.rs:11-27, examples/impl_radix_key.rs:32-56): ``records`` is a 2-D
@@ -807,7 +880,7 @@ def profile_runs() -> int:
     return int(_lib.load().rdst_hip_profile_runs())
 
 
-STAGE_NAMES = {1: "clear", 2: "histogram", 3: "scan", 4: "pass", 5: "copy_back", 6: "histogram16", 7: "route", 8: "local_sort", 10: "msd_pass_a", 11: "msd_pass_b", 12: "sample", 13: "segments"}
+STAGE_NAMES = {1: "clear", 2: "histogram", 3: "scan", 4: "pass", 5: "copy_back", 6: "histogram16", 7: "route", 8: "local_sort", 10: "msd_pass_a", 11: "msd_pass_b", 12: "sample", 13: "segments", 14: "segments_tiled"}
 
 
 def profile_run(run: int, levels: int):
