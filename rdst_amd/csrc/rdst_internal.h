@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include <mutex>
+#include <type_traits>
 
 #include "rdst_hip.h"
 
@@ -28,6 +29,21 @@ int launch(const char* name, void (*kernel)(P...), dim3 grid, dim3 block, size_t
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? RDST_OK : set_error(RDST_ERR_HIP, name, e);
 }
+
+// Run-time booleans to compile-time ones: with_bools(f, a, b) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}), so a
+// kernel's argument list is written once for all its variants.  Every combination of the booleans is instantiated: a variant
+// that is built for some key widths only stays behind an `if constexpr` at the call site.
+template <typename F>
+int with_bools(F&& f) { return f(); }
+template <typename F, typename... B>
+int with_bools(F&& f, bool b, B... rest) {
+    return b ? with_bools([&](auto... c) { return f(std::true_type{}, c...); }, rest...)
+             : with_bools([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
+}
+
+// f(uint32_t{}) or f(uint64_t{}): a 4- or 8-byte key, value or index type picked at run time
+template <typename F>
+int by_uint(uint32_t bytes, F&& f) { return bytes == 4 ? f(uint32_t{}) : f(uint64_t{}); }
 
 // What a blocking host entry point owns: its stream, its device buffers and the device it switched away from.  All of it is
 // given back when the entry point returns, on whatever path, after the work still queued on the stream has finished.

@@ -4605,16 +4605,7 @@ bool hybrid_eligible(uint64_t n, size_t key_bytes) {
 
 using rdst_internal::launch;  // every kernel launch: LDS attribute, launch, launch error -> fail() naming the kernel
 
-// Run-time booleans to compile-time ones: with_bools(f, a, b) calls f(std::bool_constant<a>{}, std::bool_constant<b>{}), so a
-// kernel's argument list is written once for all its variants.  Every combination of the booleans is instantiated: a variant
-// that is built for some key widths only stays behind an `if constexpr` at the call site.
-template <typename F>
-int with_bools(F&& f) { return f(); }
-template <typename F, typename... B>
-int with_bools(F&& f, bool b, B... rest) {
-    return b ? with_bools([&](auto... c) { return f(std::true_type{}, c...); }, rest...)
-             : with_bools([&](auto... c) { return f(std::false_type{}, c...); }, rest...);
-}
+using rdst_internal::with_bools;  // run-time booleans to compile-time ones: a kernel's argument list written once for all its variants
 template <typename K>
 constexpr int vec_for(bool aligned) { return aligned ? 16 / (int)sizeof(K) : 1; }  // keys per 16-byte load, if the pointer allows one
 bool aligned16(const void* a, const void* b = nullptr) { return ((reinterpret_cast<uintptr_t>(a) | reinterpret_cast<uintptr_t>(b)) & 15u) == 0; }
@@ -5543,9 +5534,7 @@ int stream_run(void* dev_dst, const void* dev_src, uint64_t bytes, void* stream)
                   static_cast<u32x4_t*>(dev_dst), static_cast<const u32x4_t*>(dev_src), bytes / 16, D->err_dev + 8);
 }
 
-// f(uint32_t{}) or f(uint64_t{}): a 4- or 8-byte key, value or index type picked at run time
-template <typename F>
-int by_uint(uint32_t bytes, F&& f) { return bytes == 4 ? f(uint32_t{}) : f(uint64_t{}); }
+using rdst_internal::by_uint;  // f(uint32_t{}) or f(uint64_t{})
 
 // [u8; N] rows with N <= 16 are sorted as W-byte integers: widened (expand) before the sort, narrowed (!expand) after it
 uint32_t widened_bytes(uint32_t nb) { return nb <= 4 ? 4 : (nb <= 8 ? 8 : 16); }

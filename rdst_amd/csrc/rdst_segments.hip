@@ -35,26 +35,27 @@
 #include "rdst_hip.h"
 #include "rdst_internal.h"
 #include "rdst_device.h"
+#include "rdst_segments_layout.h"
 
 namespace {
 
+namespace L = rdst_segments_layout;
+using rdst_internal::by_uint;
 using rdst_internal::launch;
 using rdst_internal::set_error;
+using rdst_internal::with_bools;
 
 constexpr int RADIX = 256;
 struct NoVal {};  // keys only
 template <typename V> struct ValBytes { static constexpr int value = (int)sizeof(V); };
 template <> struct ValBytes<NoVal> { static constexpr int value = 0; };
 
-// Shapes.  rdst_hip_sort_segments_limits (rdst_segments.cpp) states the same numbers; limits_match() below checks them
-// against each other before the first launch.
+// Shapes: rdst_segments_layout.h states them for this file and for rdst_hip_sort_segments_limits (rdst_segments.cpp).
+using L::BLOCK_THREADS;
+using L::block_kpt;
+using L::wave_kpt;
 constexpr int SEG_WAVES = 4;  // segments per workgroup of the wave class
-constexpr int wave_kpt(size_t key_bytes) { return key_bytes == 16 ? 4 : 8; }
-constexpr int BLOCK_WAVES = 16;
-constexpr int BLOCK_THREADS = BLOCK_WAVES * 64;
-constexpr int block_kpt(size_t key_bytes, size_t val_bytes) {
-    return val_bytes != 0 && key_bytes + val_bytes > 8 ? 8 : (key_bytes <= 4 ? 16 : (key_bytes == 8 ? 8 : 4));
-}
+constexpr int BLOCK_WAVES = BLOCK_THREADS / 64;
 constexpr size_t wave_lds_bytes(size_t key_bytes, size_t val_bytes) {  // per workgroup: tables, then key stages, then value stages
     return (size_t)SEG_WAVES * (RADIX * sizeof(uint32_t) + 64 * wave_kpt(key_bytes) * (key_bytes + val_bytes));
 }
@@ -430,88 +431,143 @@ int stage_items(Staging& st, const rdst_segment_item* items, size_t count, void*
     return RDST_OK;
 }
 
-template <typename K, typename V>
-bool limits_match() {
-    uint32_t lim[2] = {0, 0};
-    return rdst_hip_sort_segments_limits((uint32_t)sizeof(K), (uint32_t)ValBytes<V>::value, lim) == RDST_OK &&
-           lim[0] == 64u * wave_kpt(sizeof(K)) && lim[1] == (uint32_t)BLOCK_THREADS * block_kpt(sizeof(K), ValBytes<V>::value);
-}
-
-template <typename K, typename V>
-int launch_batched(K* keys, V* vals, const rdst_segment_item* dev_items, uint64_t n_wave, uint64_t n_block, rdst_key_kind kind, hipStream_t s) {
-    constexpr int LEVELS = (int)sizeof(K);
-    constexpr size_t VB = ValBytes<V>::value;
-    static_assert(wave_lds_bytes(sizeof(K), VB) <= LDS_LIMIT && block_lds_bytes(sizeof(K), VB) <= LDS_LIMIT, "a workgroup's LDS stays within 160 KiB");
-    if (!limits_match<K, V>()) return set_error(RDST_ERR_ARG, "segments: the kernels' shapes and rdst_hip_sort_segments_limits disagree");
-    unsigned __int128 neg128, pos128;
-    rdst_internal::key_xor_masks(kind, (uint32_t)sizeof(K), &neg128, &pos128);
-    const K neg = (K)neg128, pos = (K)pos128;
-    const bool mapped = neg128 != 0 || pos128 != 0;
-    int rc = RDST_OK;
-    if (n_wave) {
-        const dim3 grid((uint32_t)((n_wave + SEG_WAVES - 1) / SEG_WAVES));
-        rc = mapped ? launch("segment_wave_kernel", segment_wave_kernel<K, V, LEVELS, true>, grid, dim3(SEG_WAVES * 64), wave_lds_bytes(sizeof(K), VB), s, keys,
-                             vals, dev_items, (uint32_t)n_wave, neg, pos)
-                    : launch("segment_wave_kernel", segment_wave_kernel<K, V, LEVELS, false>, grid, dim3(SEG_WAVES * 64), wave_lds_bytes(sizeof(K), VB), s, keys,
-                             vals, dev_items, (uint32_t)n_wave, neg, pos);
-        if (rc) return rc;
-    }
-    if (n_block) {
-        const dim3 grid((uint32_t)n_block);
-        const rdst_segment_item* block_items = dev_items + n_wave;
-        rc = mapped ? launch("segment_block_kernel", segment_block_kernel<K, V, LEVELS, true>, grid, dim3(BLOCK_THREADS), block_lds_bytes(sizeof(K), VB), s, keys,
-                             vals, block_items, neg, pos)
-                    : launch("segment_block_kernel", segment_block_kernel<K, V, LEVELS, false>, grid, dim3(BLOCK_THREADS), block_lds_bytes(sizeof(K), VB), s, keys,
-                             vals, block_items, neg, pos);
-    }
-    return rc;
-}
-
-int dispatch_batched(void* keys, void* vals, uint32_t key_bytes, uint32_t val_bytes, const rdst_segment_item* dev_items, uint64_t n_wave,
-                     uint64_t n_block, rdst_key_kind kind, hipStream_t s) {
-    NoVal* const none = nullptr;
+// f(K{}, V{}) for the nine (key, value) widths the entries take — NoVal{}: keys only.  The widths were checked (check_call).
+template <typename F>
+int with_key_value_types(uint32_t key_bytes, uint32_t val_bytes, F&& f) {
     if (val_bytes == 0) {
         switch (key_bytes) {
-            case 1: return launch_batched(static_cast<uint8_t*>(keys), none, dev_items, n_wave, n_block, kind, s);
-            case 2: return launch_batched(static_cast<uint16_t*>(keys), none, dev_items, n_wave, n_block, kind, s);
-            case 4: return launch_batched(static_cast<uint32_t*>(keys), none, dev_items, n_wave, n_block, kind, s);
-            case 8: return launch_batched(static_cast<uint64_t*>(keys), none, dev_items, n_wave, n_block, kind, s);
-            default: return launch_batched(static_cast<u128*>(keys), none, dev_items, n_wave, n_block, kind, s);
+            case 1: return f(uint8_t{}, NoVal{});
+            case 2: return f(uint16_t{}, NoVal{});
+            case 4: return f(uint32_t{}, NoVal{});
+            case 8: return f(uint64_t{}, NoVal{});
+            default: return f(u128{}, NoVal{});
         }
     }
-    if (key_bytes == 4)
-        return val_bytes == 4 ? launch_batched(static_cast<uint32_t*>(keys), static_cast<uint32_t*>(vals), dev_items, n_wave, n_block, kind, s)
-                              : launch_batched(static_cast<uint32_t*>(keys), static_cast<uint64_t*>(vals), dev_items, n_wave, n_block, kind, s);
-    return val_bytes == 4 ? launch_batched(static_cast<uint64_t*>(keys), static_cast<uint32_t*>(vals), dev_items, n_wave, n_block, kind, s)
-                          : launch_batched(static_cast<uint64_t*>(keys), static_cast<uint64_t*>(vals), dev_items, n_wave, n_block, kind, s);
+    return by_uint(key_bytes, [&](auto k) { return by_uint(val_bytes, [&](auto v) { return f(k, v); }); });
 }
 
-// Both entries.  val_bytes == 0: keys only (vals, tmp_vals unused).
-int sort_segments(void* keys, void* vals, void* tmp_keys, void* tmp_vals, uint64_t tmp_elems, uint64_t len, const uint64_t* offsets,
-                  uint64_t n_segments, uint32_t key_bytes, rdst_key_kind kind, uint32_t levels, uint32_t val_bytes, void* stream) {
-    const bool pairs = val_bytes != 0;
+// The order-preserving key map as the kernels take it: the two xor masks, and whether either does anything (MAPPED).
+template <typename K>
+struct KeyXor {
+    K neg, pos;
+    bool mapped;
+};
+template <typename K>
+KeyXor<K> key_xor(rdst_key_kind kind) {
+    unsigned __int128 neg, pos;
+    rdst_internal::key_xor_masks(kind, (uint32_t)sizeof(K), &neg, &pos);
+    return {(K)neg, (K)pos, neg != 0 || pos != 0};
+}
+
+// One call of any entry, as its worker and the launches see it.  val_bytes == 0: keys only (vals, tmp_vals unused).
+struct SegCall {
+    void *keys, *vals, *tmp_keys, *tmp_vals;
+    uint64_t len;
+    uint32_t key_bytes, val_bytes;
+    rdst_key_kind kind;
+    uint32_t levels;
+    hipStream_t s;
+    bool pairs() const { return val_bytes != 0; }
+};
+
+bool misaligned(const void* p, uint32_t to) { return reinterpret_cast<uintptr_t>(p) % to != 0; }
+
+// What every entry checks first: the key arguments, then (the pair entries) the widths.
+int check_call(const SegCall& c, bool pair_entry, uint64_t n_segments) {
     // with no segment there is nothing the pointers could be used for
-    int rc = rdst_internal::check_key_args(keys, n_segments ? len : 0, key_bytes, kind, levels);
-    if (rc) return rc;
-    if (n_segments == 0) return RDST_OK;
+    if (int rc = rdst_internal::check_key_args(c.keys, n_segments ? c.len : 0, c.key_bytes, c.kind, c.levels)) return rc;
+    if (pair_entry && !L::pair_width_ok(c.key_bytes)) return set_error(RDST_ERR_UNSUPPORTED, "key-value sorts take 4- or 8-byte keys");
+    if (pair_entry && !L::pair_width_ok(c.val_bytes)) return set_error(RDST_ERR_UNSUPPORTED, "key-value sorts carry 4- or 8-byte values");
+    return RDST_OK;
+}
+
+// The value and tmp pointers.  `no_tmp`: the text of an entry that cannot do without a tmp array (nullptr: it can).
+int check_pointers(const SegCall& c, const char* no_tmp) {
+    if (c.pairs() && c.vals == nullptr && c.len != 0) return set_error(RDST_ERR_ARG, "null value pointer");
+    if (c.pairs() && misaligned(c.vals, c.val_bytes)) return set_error(RDST_ERR_ALIGN, "value pointer not aligned to the value size");
+    if (no_tmp && (c.tmp_keys == nullptr || (c.pairs() && c.tmp_vals == nullptr))) return set_error(RDST_ERR_ARG, no_tmp);
+    if (misaligned(c.tmp_keys, c.key_bytes)) return set_error(RDST_ERR_ALIGN, "tmp pointer not aligned to the element size");
+    if (c.pairs() && misaligned(c.tmp_vals, c.val_bytes)) return set_error(RDST_ERR_ALIGN, "tmp value pointer not aligned to the value size");
+    return RDST_OK;
+}
+
+// The two batched launches: a wave per item of the wave class, a workgroup per item of the block class.  COUNTED == false:
+// the host knows the counts, `n_wave` and `n_block`, and the block class follows the wave class in `items`.  COUNTED == true:
+// the counts stand in the plan header `hdr`, and `n_wave` and `n_block` are the host's bounds on them, for the grids alone.
+template <bool COUNTED, typename K, typename V>
+int launch_classes_t(K* keys, V* vals, const rdst_segment_item* items, const uint32_t* hdr, uint64_t n_wave, uint64_t n_block, rdst_key_kind kind,
+                     hipStream_t s) {
+    constexpr int LEVELS = (int)sizeof(K);
+    constexpr size_t VB = ValBytes<V>::value;
+    constexpr size_t wave_lds = wave_lds_bytes(sizeof(K), VB), block_lds = block_lds_bytes(sizeof(K), VB);
+    static_assert(wave_lds <= LDS_LIMIT && block_lds <= LDS_LIMIT, "a workgroup's LDS stays within 160 KiB");
+    const KeyXor<K> x = key_xor<K>(kind);
+    const dim3 wave_grid((uint32_t)((n_wave + SEG_WAVES - 1) / SEG_WAVES)), wave_block(SEG_WAVES * 64);
+    const dim3 block_grid((uint32_t)n_block), block_block(BLOCK_THREADS);
+    int rc = RDST_OK;
+    if (n_wave)
+        rc = with_bools([&](auto mapped) {
+            constexpr bool M = decltype(mapped)::value;
+            if constexpr (COUNTED)
+                return launch("segment_wave_counted_kernel", segment_wave_counted_kernel<K, V, LEVELS, M>, wave_grid, wave_block, wave_lds, s, keys, vals,
+                              items, hdr, x.neg, x.pos);
+            else
+                return launch("segment_wave_kernel", segment_wave_kernel<K, V, LEVELS, M>, wave_grid, wave_block, wave_lds, s, keys, vals, items,
+                              (uint32_t)n_wave, x.neg, x.pos);
+        }, x.mapped);
+    if (rc || !n_block) return rc;
+    return with_bools([&](auto mapped) {
+        constexpr bool M = decltype(mapped)::value;
+        if constexpr (COUNTED)
+            return launch("segment_block_counted_kernel", segment_block_counted_kernel<K, V, LEVELS, M>, block_grid, block_block, block_lds, s, keys, vals,
+                          items, hdr, x.neg, x.pos);
+        else
+            return launch("segment_block_kernel", segment_block_kernel<K, V, LEVELS, M>, block_grid, block_block, block_lds, s, keys, vals,
+                          items + n_wave, x.neg, x.pos);
+    }, x.mapped);
+}
+
+template <bool COUNTED>
+int launch_classes(const SegCall& c, const rdst_segment_item* items, const uint32_t* hdr, uint64_t n_wave, uint64_t n_block) {
+    return with_key_value_types(c.key_bytes, c.val_bytes, [&](auto k, auto v) {
+        return launch_classes_t<COUNTED>(static_cast<decltype(k)*>(c.keys), static_cast<decltype(v)*>(c.vals), items, hdr, n_wave, n_block, c.kind, c.s);
+    });
+}
+
+// A batched stage between its profiling calls: a run of its own, `enqueue`, the end of RDST_STAGE_SEGMENTS.
+template <typename F>
+int batched_stage(hipStream_t s, F&& enqueue) {
+    if (int rc = rdst_internal::profile_open_run(s)) return rc;
+    if (int rc = enqueue()) return rc;
+    return rdst_internal::profile_stage_end(s, RDST_STAGE_SEGMENTS);
+}
+
+// One long segment, [start, start + n) of the keys (and values), by the whole-slice route.  Callers hold the library's mutex.
+int sort_long_slice(const SegCall& c, uint64_t start, uint64_t n) {
+    char* k = static_cast<char*>(c.keys) + start * c.key_bytes;
+    return c.pairs() ? rdst_internal::sort_pairs_slice_locked(k, static_cast<char*>(c.vals) + start * c.val_bytes, c.tmp_keys, c.tmp_vals, n, c.key_bytes,
+                                                              c.kind, c.val_bytes, c.s)
+                     : rdst_internal::sort_slice_locked(k, c.tmp_keys, n, c.key_bytes, c.kind, c.s);
+}
+
+// Both host-borders entries.
+int sort_segments(const SegCall& c, bool pair_entry, uint64_t tmp_elems, const uint64_t* offsets, uint64_t n_segments) {
+    int rc = check_call(c, pair_entry, n_segments);
+    if (rc || n_segments == 0) return rc;
     std::vector<rdst_segment_item> items;
     uint64_t counts[3] = {0, 0, 0}, longest = 0;
-    rc = rdst_segments_plan(offsets, n_segments, len, key_bytes, val_bytes, nullptr, 0, counts, &longest);
+    rc = rdst_segments_plan(offsets, n_segments, c.len, c.key_bytes, c.val_bytes, nullptr, 0, counts, &longest);
     const uint64_t total = counts[0] + counts[1] + counts[2];
     if (rc != RDST_OK && !(rc == RDST_ERR_ARG && total > 0)) return rc;  // (a work list that does not fit capacity 0 is the expected answer)
     if (total == 0) return RDST_OK;
     items.resize(total);
-    if ((rc = rdst_segments_plan(offsets, n_segments, len, key_bytes, val_bytes, items.data(), total, counts, &longest))) return rc;
-    if (pairs && vals == nullptr) return set_error(RDST_ERR_ARG, "null value pointer");
-    if (pairs && reinterpret_cast<uintptr_t>(vals) % val_bytes) return set_error(RDST_ERR_ALIGN, "value pointer not aligned to the value size");
-    if (reinterpret_cast<uintptr_t>(tmp_keys) % key_bytes) return set_error(RDST_ERR_ALIGN, "tmp pointer not aligned to the element size");
-    if (pairs && reinterpret_cast<uintptr_t>(tmp_vals) % val_bytes) return set_error(RDST_ERR_ALIGN, "tmp value pointer not aligned to the value size");
+    if ((rc = rdst_segments_plan(offsets, n_segments, c.len, c.key_bytes, c.val_bytes, items.data(), total, counts, &longest))) return rc;
+    if ((rc = check_pointers(c, nullptr))) return rc;  // (a work list: len != 0)
     if (counts[2] != 0) {
-        if (tmp_keys == nullptr || (pairs && tmp_vals == nullptr)) return set_error(RDST_ERR_ARG, "segments: a segment beyond block_max needs a tmp array");
+        if (c.tmp_keys == nullptr || (c.pairs() && c.tmp_vals == nullptr)) return set_error(RDST_ERR_ARG, "segments: a segment beyond block_max needs a tmp array");
         if (tmp_elems < longest) return set_error(RDST_ERR_ARG, "segments: tmp_elems is below the longest segment beyond block_max");
     }
     std::lock_guard<std::mutex> lock(rdst_internal::library_mutex());
-    hipStream_t s = static_cast<hipStream_t>(stream);
     const uint64_t batched = counts[0] + counts[1];
     if (counts[1] >= (1ull << 31)) return set_error(RDST_ERR_ARG, "segments: too many block-class segments for one launch");
     // the workspace is sized ONCE, for the work list and for every long segment: a growth between the launches would free
@@ -520,37 +576,32 @@ int sort_segments(void* keys, void* vals, void* tmp_keys, void* tmp_vals, uint64
     size_t ws_bytes = table_bytes;
     for (uint64_t i = batched; i < total; ++i) {
         const uint32_t sg = items[i].seg;
-        ws_bytes = std::max(ws_bytes, rdst_internal::slice_workspace_bytes(offsets[sg + 1] - offsets[sg], key_bytes, kind, val_bytes));
+        ws_bytes = std::max(ws_bytes, rdst_internal::slice_workspace_bytes(offsets[sg + 1] - offsets[sg], c.key_bytes, c.kind, c.val_bytes));
     }
     void* ws = nullptr;
     int dev = 0;
-    rc = rdst_internal::workspace_take(ws_bytes, s, &ws, &dev);
-    if (rc && ws_bytes > table_bytes) rc = rdst_internal::workspace_take(std::max<size_t>(table_bytes, 256), s, &ws, &dev);  // no room: a long segment then picks its lean layout itself
+    rc = rdst_internal::workspace_take(ws_bytes, c.s, &ws, &dev);
+    if (rc && ws_bytes > table_bytes) rc = rdst_internal::workspace_take(std::max<size_t>(table_bytes, 256), c.s, &ws, &dev);  // no room: a long segment then picks its lean layout itself
     if (rc) return rc;
     if (batched) {
-        if ((rc = rdst_internal::profile_open_run(s))) return rc;
-        if ((rc = stage_items(g_staging[dev], items.data(), (size_t)batched, ws, s))) return rc;
-        if ((rc = dispatch_batched(keys, vals, key_bytes, val_bytes, static_cast<const rdst_segment_item*>(ws), counts[0], counts[1], kind, s))) return rc;
-        if ((rc = rdst_internal::profile_stage_end(s, RDST_STAGE_SEGMENTS))) return rc;
-        if ((rc = rdst_internal::workspace_handback(s))) return rc;
+        rc = batched_stage(c.s, [&] {
+            if (int e = stage_items(g_staging[dev], items.data(), (size_t)batched, ws, c.s)) return e;
+            return launch_classes<false>(c, static_cast<const rdst_segment_item*>(ws), nullptr, counts[0], counts[1]);
+        });
+        if (rc) return rc;
+        if ((rc = rdst_internal::workspace_handback(c.s))) return rc;
     }
     // long segments one after another; each uses the workspace (the work list is dead by then, in stream order)
     for (uint64_t i = batched; i < total; ++i) {
         const uint32_t sg = items[i].seg;
-        const uint64_t start = offsets[sg], n = offsets[sg + 1] - offsets[sg];
-        char* k = static_cast<char*>(keys) + start * key_bytes;
-        rc = pairs ? rdst_internal::sort_pairs_slice_locked(k, static_cast<char*>(vals) + start * val_bytes, tmp_keys, tmp_vals, n, key_bytes, kind, val_bytes, s)
-                   : rdst_internal::sort_slice_locked(k, tmp_keys, n, key_bytes, kind, s);
-        if (rc) return rc;
+        if ((rc = sort_long_slice(c, offsets[sg], offsets[sg + 1] - offsets[sg]))) return rc;
     }
     return RDST_OK;
 }
 
-
 // ---- device-resident offsets -------------------------------------------------------------------------------------------------
 
-// The caller's scratch: header, the plan's pair arrays and their tmps, the item table.  The size has one statement,
-// rdst_hip_sort_segments_device_offsets_scratch_bytes (rdst_segments.cpp); plan_scratch() checks this layout against it.
+// The caller's scratch: header, the plan's pair arrays and their tmps, the item table, where rdst_segments_layout.h puts them.
 struct PlanScratch {
     uint32_t* hdr;
     uint32_t *keys, *segs, *tmp_keys, *tmp_segs;
@@ -558,119 +609,77 @@ struct PlanScratch {
     uint64_t* long_lens;  // over the two tmps, which are dead once the pairs are sorted
 };
 
-int plan_scratch(void* scratch, uint64_t n_segments, PlanScratch* out) {
-    const size_t arr = ((size_t)n_segments * sizeof(uint32_t) + 255) / 256 * 256;
-    const size_t table = ((size_t)n_segments * sizeof(rdst_segment_item) + 255) / 256 * 256;
-    char* base = static_cast<char*>(scratch);
-    char* at = base + HDR_WORDS * sizeof(uint32_t);
-    out->hdr = reinterpret_cast<uint32_t*>(base);
-    out->keys = reinterpret_cast<uint32_t*>(at);
-    out->segs = reinterpret_cast<uint32_t*>(at + arr);
-    out->tmp_keys = reinterpret_cast<uint32_t*>(at + 2 * arr);
-    out->tmp_segs = reinterpret_cast<uint32_t*>(at + 3 * arr);
-    out->items = reinterpret_cast<rdst_segment_item*>(at + 4 * arr);
-    out->long_lens = reinterpret_cast<uint64_t*>(at + 2 * arr);
+PlanScratch plan_scratch(void* scratch, uint64_t n_segments) {
+    static_assert(HDR_WORDS * sizeof(uint32_t) == L::PLAN_HEADER_BYTES, "the header the kernels index is the header of the layout");
     static_assert(sizeof(uint64_t) == 2 * sizeof(uint32_t), "the long lengths fit the two tmps");
-    if ((uint64_t)(at + 4 * arr + table - base) != rdst_hip_sort_segments_device_offsets_scratch_bytes(n_segments))
-        return set_error(RDST_ERR_ARG, "segments: the scratch layout and rdst_hip_sort_segments_device_offsets_scratch_bytes disagree");
-    return RDST_OK;
+    const L::PlanLayout at = L::plan_layout(n_segments);
+    char* base = static_cast<char*>(scratch);
+    const auto u32 = [base](uint64_t offset) { return reinterpret_cast<uint32_t*>(base + offset); };
+    return {u32(0), u32(at.keys), u32(at.segs), u32(at.tmp_keys), u32(at.tmp_segs), reinterpret_cast<rdst_segment_item*>(base + at.items),
+            reinterpret_cast<uint64_t*>(base + at.tmp_keys)};
 }
 
 // What the device-offsets entries and the plan hook check alike, before any device work.
 int check_offsets_table(const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments, uint64_t len) {
-    if (n_segments > (1ull << 30)) return set_error(RDST_ERR_UNSUPPORTED, "segments: device-resident offsets take at most 2^30 segments");
+    if (n_segments > L::MAX_SEGMENTS) return set_error(RDST_ERR_UNSUPPORTED, "segments: device-resident offsets take at most 2^30 segments");
     if (offset_bytes != 4 && offset_bytes != 8) return set_error(RDST_ERR_ARG, "segments: offset_bytes must be 4 or 8");
     if (dev_offsets == nullptr) return set_error(RDST_ERR_ARG, "segments: null offsets");
-    if (reinterpret_cast<uintptr_t>(dev_offsets) % offset_bytes) return set_error(RDST_ERR_ALIGN, "segments: offsets pointer not aligned to offset_bytes");
+    if (misaligned(dev_offsets, offset_bytes)) return set_error(RDST_ERR_ALIGN, "segments: offsets pointer not aligned to offset_bytes");
     if (offset_bytes == 4 && len >= (1ull << 32)) return set_error(RDST_ERR_ARG, "segments: 4-byte offsets need len below 2^32");
+    return RDST_OK;
+}
+
+// `need`: the bytes this entry's ..._scratch_bytes function asks for; `below_need`: the text that names the function.
+int check_scratch(const void* scratch, uint64_t scratch_bytes, uint64_t need, const char* below_need) {
+    if (scratch == nullptr) return set_error(RDST_ERR_ARG, "segments: null scratch");
+    if (misaligned(scratch, 256)) return set_error(RDST_ERR_ALIGN, "segments: scratch not aligned to 256 bytes");
+    if (scratch_bytes < need) return set_error(RDST_ERR_ARG, below_need);
     return RDST_OK;
 }
 
 int check_offsets_args(const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments, uint64_t len, const void* scratch, uint64_t scratch_bytes) {
     if (int rc = check_offsets_table(dev_offsets, offset_bytes, n_segments, len)) return rc;
-    if (scratch == nullptr) return set_error(RDST_ERR_ARG, "segments: null scratch");
-    if (reinterpret_cast<uintptr_t>(scratch) % 256) return set_error(RDST_ERR_ALIGN, "segments: scratch not aligned to 256 bytes");
-    if (scratch_bytes < rdst_hip_sort_segments_device_offsets_scratch_bytes(n_segments))
-        return set_error(RDST_ERR_ARG, "segments: scratch_bytes is below rdst_hip_sort_segments_device_offsets_scratch_bytes(n_segments)");
-    return RDST_OK;
+    return check_scratch(scratch, scratch_bytes, L::plan_layout(n_segments).total,
+                         "segments: scratch_bytes is below rdst_hip_sort_segments_device_offsets_scratch_bytes(n_segments)");
+}
+
+// The class keys of the plan (segments_keygen_kernel) reach block_max + 3.
+constexpr bool class_keys_fit_16_bits() {
+    for (uint32_t kb : {1u, 2u, 4u, 8u, 16u})
+        for (uint32_t vb : {0u, 4u, 8u})
+            if (L::block_max(kb, vb) + 3 >= (1u << 16)) return false;
+    return true;
 }
 
 // Enqueues the plan: header cleared, class keys, the pair sort (it takes and hands back the workspace itself), items.
 // Callers hold the library's mutex.  Nothing here waits for the device.
 template <typename Off>
-int enqueue_plan_t(const void* dev_offsets, uint64_t n_segments, uint64_t len, const uint32_t lim[2], const PlanScratch& P, uint32_t no_long,
-                   uint32_t* err, hipStream_t s) {
+int enqueue_plan_t(const void* dev_offsets, uint64_t n_segments, uint64_t len, uint32_t wave_max, uint32_t block_max, const PlanScratch& P,
+                   uint32_t no_long, uint32_t* err, hipStream_t s) {
     const Off* off = static_cast<const Off*>(dev_offsets);
     const uint32_t nseg = (uint32_t)n_segments;
     const dim3 grid((uint32_t)((n_segments + PLAN_THREADS - 1) / PLAN_THREADS));
     SEG_HIP_TRY(hipMemsetAsync(P.hdr, 0, HDR_WORDS * sizeof(uint32_t), s));
-    int rc = launch("segments_keygen_kernel", segments_keygen_kernel<Off>, grid, dim3(PLAN_THREADS), 0, s, off, nseg, len, lim[0], lim[1], P.keys, P.segs, P.hdr);
+    int rc = launch("segments_keygen_kernel", segments_keygen_kernel<Off>, grid, dim3(PLAN_THREADS), 0, s, off, nseg, len, wave_max, block_max, P.keys, P.segs, P.hdr);
     if (rc) return rc;
     if (n_segments > 1 && (rc = rdst_internal::sort_pairs_slice_locked(P.keys, P.segs, P.tmp_keys, P.tmp_segs, n_segments, 4, RDST_KEY_UNSIGNED, 4, s))) return rc;
-    return launch("segments_items_kernel", segments_items_kernel<Off>, grid, dim3(PLAN_THREADS), 0, s, off, nseg, lim[1],
+    return launch("segments_items_kernel", segments_items_kernel<Off>, grid, dim3(PLAN_THREADS), 0, s, off, nseg, block_max,
                   static_cast<const uint32_t*>(P.keys), static_cast<const uint32_t*>(P.segs), P.items, P.long_lens, P.hdr, no_long, err);
 }
 
 int enqueue_plan(const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments, uint64_t len, uint32_t key_bytes, uint32_t val_bytes,
                  const PlanScratch& P, uint32_t no_long, uint32_t* err, hipStream_t s) {
-    uint32_t lim[2];
-    if (int rc = rdst_hip_sort_segments_limits(key_bytes, val_bytes, lim)) return rc;
-    if (lim[1] + 3 >= (1u << 16)) return set_error(RDST_ERR_ARG, "segments: the class keys no longer fit 16 bits");
-    return offset_bytes == 4 ? enqueue_plan_t<uint32_t>(dev_offsets, n_segments, len, lim, P, no_long, err, s)
-                             : enqueue_plan_t<uint64_t>(dev_offsets, n_segments, len, lim, P, no_long, err, s);
+    static_assert(class_keys_fit_16_bits(), "the plan's pair sort relies on class keys below 2^16");
+    const uint32_t wave_max = L::wave_max(key_bytes), block_max = L::block_max(key_bytes, val_bytes);
+    return offset_bytes == 4 ? enqueue_plan_t<uint32_t>(dev_offsets, n_segments, len, wave_max, block_max, P, no_long, err, s)
+                             : enqueue_plan_t<uint64_t>(dev_offsets, n_segments, len, wave_max, block_max, P, no_long, err, s);
 }
 
-// The batched launches of the asynchronous mode: grids from what the host knows, counts from the header.
-template <typename K, typename V>
-int launch_counted(K* keys, V* vals, const PlanScratch& P, uint64_t n_segments, uint64_t len, rdst_key_kind kind, hipStream_t s) {
-    constexpr int LEVELS = (int)sizeof(K);
-    constexpr size_t VB = ValBytes<V>::value;
-    if (!limits_match<K, V>()) return set_error(RDST_ERR_ARG, "segments: the kernels' shapes and rdst_hip_sort_segments_limits disagree");
-    unsigned __int128 neg128, pos128;
-    rdst_internal::key_xor_masks(kind, (uint32_t)sizeof(K), &neg128, &pos128);
-    const K neg = (K)neg128, pos = (K)pos128;
-    const bool mapped = neg128 != 0 || pos128 != 0;
-    const rdst_segment_item* items = P.items;
-    const uint32_t* hdr = P.hdr;
-    // a wave-class segment holds at least two keys, a block-class one more than wave_max
-    const uint64_t wave_bound = std::min<uint64_t>(n_segments, len / 2);
-    const uint64_t block_bound = std::min<uint64_t>(n_segments, len / (64u * wave_kpt(sizeof(K)) + 1));
-    int rc = RDST_OK;
-    if (wave_bound) {
-        const dim3 grid((uint32_t)((wave_bound + SEG_WAVES - 1) / SEG_WAVES));
-        rc = mapped ? launch("segment_wave_counted_kernel", segment_wave_counted_kernel<K, V, LEVELS, true>, grid, dim3(SEG_WAVES * 64),
-                             wave_lds_bytes(sizeof(K), VB), s, keys, vals, items, hdr, neg, pos)
-                    : launch("segment_wave_counted_kernel", segment_wave_counted_kernel<K, V, LEVELS, false>, grid, dim3(SEG_WAVES * 64),
-                             wave_lds_bytes(sizeof(K), VB), s, keys, vals, items, hdr, neg, pos);
-        if (rc) return rc;
-    }
-    if (block_bound) {
-        const dim3 grid((uint32_t)block_bound);
-        rc = mapped ? launch("segment_block_counted_kernel", segment_block_counted_kernel<K, V, LEVELS, true>, grid, dim3(BLOCK_THREADS),
-                             block_lds_bytes(sizeof(K), VB), s, keys, vals, items, hdr, neg, pos)
-                    : launch("segment_block_counted_kernel", segment_block_counted_kernel<K, V, LEVELS, false>, grid, dim3(BLOCK_THREADS),
-                             block_lds_bytes(sizeof(K), VB), s, keys, vals, items, hdr, neg, pos);
-    }
-    return rc;
-}
-
-int dispatch_counted(void* keys, void* vals, uint32_t key_bytes, uint32_t val_bytes, const PlanScratch& P, uint64_t n_segments, uint64_t len,
-                     rdst_key_kind kind, hipStream_t s) {
-    NoVal* const none = nullptr;
-    if (val_bytes == 0) {
-        switch (key_bytes) {
-            case 1: return launch_counted(static_cast<uint8_t*>(keys), none, P, n_segments, len, kind, s);
-            case 2: return launch_counted(static_cast<uint16_t*>(keys), none, P, n_segments, len, kind, s);
-            case 4: return launch_counted(static_cast<uint32_t*>(keys), none, P, n_segments, len, kind, s);
-            case 8: return launch_counted(static_cast<uint64_t*>(keys), none, P, n_segments, len, kind, s);
-            default: return launch_counted(static_cast<u128*>(keys), none, P, n_segments, len, kind, s);
-        }
-    }
-    if (key_bytes == 4)
-        return val_bytes == 4 ? launch_counted(static_cast<uint32_t*>(keys), static_cast<uint32_t*>(vals), P, n_segments, len, kind, s)
-                              : launch_counted(static_cast<uint32_t*>(keys), static_cast<uint64_t*>(vals), P, n_segments, len, kind, s);
-    return val_bytes == 4 ? launch_counted(static_cast<uint64_t*>(keys), static_cast<uint32_t*>(vals), P, n_segments, len, kind, s)
-                          : launch_counted(static_cast<uint64_t*>(keys), static_cast<uint64_t*>(vals), P, n_segments, len, kind, s);
+// The batched launches of the asynchronous mode: grids from what the host knows, counts from the header.  A wave-class
+// segment holds at least two keys, a block-class one more than wave_max.
+int launch_counted(const SegCall& c, const PlanScratch& P, uint64_t n_segments) {
+    return launch_classes<true>(c, P.items, P.hdr, std::min<uint64_t>(n_segments, c.len / 2),
+                                std::min<uint64_t>(n_segments, c.len / (L::wave_max(c.key_bytes) + 1)));
 }
 
 // The header as the host reads it (tmp mode and the plan hook): one copy and one wait for `s`.
@@ -695,56 +704,36 @@ int flags_error(uint32_t flags) {
     return set_error(RDST_ERR_ARG, "segments: the last offset lies past len");
 }
 
-// Both device-offsets entries.  val_bytes == 0: keys only.
-int sort_segments_offsets(void* keys, void* vals, void* tmp_keys, void* tmp_vals, uint64_t tmp_elems, uint64_t len, const void* dev_offsets,
-                          uint32_t offset_bytes, uint64_t n_segments, uint32_t key_bytes, rdst_key_kind kind, uint32_t levels, uint32_t val_bytes,
-                          void* scratch, uint64_t scratch_bytes, void* stream) {
-    const bool pairs = val_bytes != 0;
-    int rc = rdst_internal::check_key_args(keys, n_segments ? len : 0, key_bytes, kind, levels);
-    if (rc) return rc;
-    if (n_segments == 0) return RDST_OK;
-    if ((rc = check_offsets_args(dev_offsets, offset_bytes, n_segments, len, scratch, scratch_bytes))) return rc;
-    if (pairs && vals == nullptr && len != 0) return set_error(RDST_ERR_ARG, "null value pointer");
-    if (pairs && reinterpret_cast<uintptr_t>(vals) % val_bytes) return set_error(RDST_ERR_ALIGN, "value pointer not aligned to the value size");
-    if (tmp_elems != 0 && (tmp_keys == nullptr || (pairs && tmp_vals == nullptr))) return set_error(RDST_ERR_ARG, "segments: tmp_elems > 0 needs a tmp array");
-    if (reinterpret_cast<uintptr_t>(tmp_keys) % key_bytes) return set_error(RDST_ERR_ALIGN, "tmp pointer not aligned to the element size");
-    if (pairs && reinterpret_cast<uintptr_t>(tmp_vals) % val_bytes) return set_error(RDST_ERR_ALIGN, "tmp value pointer not aligned to the value size");
-    PlanScratch P;
-    if ((rc = plan_scratch(scratch, n_segments, &P))) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
+// Both device-offsets entries.
+int sort_segments_offsets(const SegCall& c, bool pair_entry, uint64_t tmp_elems, const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments,
+                          void* scratch, uint64_t scratch_bytes) {
+    int rc = check_call(c, pair_entry, n_segments);
+    if (rc || n_segments == 0) return rc;
+    if ((rc = check_offsets_args(dev_offsets, offset_bytes, n_segments, c.len, scratch, scratch_bytes))) return rc;
+    if ((rc = check_pointers(c, tmp_elems != 0 ? "segments: tmp_elems > 0 needs a tmp array" : nullptr))) return rc;
+    const PlanScratch P = plan_scratch(scratch, n_segments);
     const bool async = tmp_elems == 0;
     uint32_t* err = nullptr;
     if (async && (rc = rdst_internal::device_error_word(&err))) return rc;  // (takes the mutex itself)
     std::lock_guard<std::mutex> lock(rdst_internal::library_mutex());
-    if ((rc = enqueue_plan(dev_offsets, offset_bytes, n_segments, len, key_bytes, val_bytes, P, async ? 1u : 0u, err, s))) return rc;
-    if (async) {  // the counts stay on the device
-        if ((rc = rdst_internal::profile_open_run(s))) return rc;
-        if ((rc = dispatch_counted(keys, vals, key_bytes, val_bytes, P, n_segments, len, kind, s))) return rc;
-        return rdst_internal::profile_stage_end(s, RDST_STAGE_SEGMENTS);
-    }
+    if ((rc = enqueue_plan(dev_offsets, offset_bytes, n_segments, c.len, c.key_bytes, c.val_bytes, P, async ? 1u : 0u, err, c.s))) return rc;
+    if (async) return batched_stage(c.s, [&] { return launch_counted(c, P, n_segments); });  // the counts stay on the device
     PlanResult r;
-    if ((rc = read_plan(P, &r, s))) return rc;  // the one wait of this mode (and one more below, if there are long segments)
+    if ((rc = read_plan(P, &r, c.s))) return rc;  // the one wait of this mode (and one more below, if there are long segments)
     if (r.flags) return flags_error(r.flags);
     if (r.counts[2] != 0 && tmp_elems < r.longest) return set_error(RDST_ERR_ARG, "segments: tmp_elems is below the longest segment beyond block_max");
     const uint64_t batched = r.counts[0] + r.counts[1];
-    if (batched) {
-        if ((rc = rdst_internal::profile_open_run(s))) return rc;
-        if ((rc = dispatch_batched(keys, vals, key_bytes, val_bytes, P.items, r.counts[0], r.counts[1], kind, s))) return rc;
-        if ((rc = rdst_internal::profile_stage_end(s, RDST_STAGE_SEGMENTS))) return rc;
-    }
+    if (batched && (rc = batched_stage(c.s, [&] { return launch_classes<false>(c, P.items, nullptr, r.counts[0], r.counts[1]); }))) return rc;
     if (r.counts[2] == 0) return RDST_OK;
     std::vector<rdst_segment_item> long_items((size_t)r.counts[2]);
     std::vector<uint64_t> long_lens((size_t)r.counts[2]);
-    SEG_HIP_TRY(hipMemcpyAsync(long_items.data(), P.items + batched, long_items.size() * sizeof(rdst_segment_item), hipMemcpyDeviceToHost, s));
-    SEG_HIP_TRY(hipMemcpyAsync(long_lens.data(), P.long_lens, long_lens.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, s));
-    SEG_HIP_TRY(hipStreamSynchronize(s));
+    SEG_HIP_TRY(hipMemcpyAsync(long_items.data(), P.items + batched, long_items.size() * sizeof(rdst_segment_item), hipMemcpyDeviceToHost, c.s));
+    SEG_HIP_TRY(hipMemcpyAsync(long_lens.data(), P.long_lens, long_lens.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, c.s));
+    SEG_HIP_TRY(hipStreamSynchronize(c.s));
     for (size_t i = 0; i < long_items.size(); ++i) {
         const uint64_t start = long_items[i].start, n = long_lens[i];
-        if (n > tmp_elems || start > len || n > len - start) return set_error(RDST_ERR_DEVICE, "segments: a long item of the device plan lies outside the array");
-        char* k = static_cast<char*>(keys) + start * key_bytes;
-        rc = pairs ? rdst_internal::sort_pairs_slice_locked(k, static_cast<char*>(vals) + start * val_bytes, tmp_keys, tmp_vals, n, key_bytes, kind, val_bytes, s)
-                   : rdst_internal::sort_slice_locked(k, tmp_keys, n, key_bytes, kind, s);
-        if (rc) return rc;
+        if (n > tmp_elems || start > c.len || n > c.len - start) return set_error(RDST_ERR_DEVICE, "segments: a long item of the device plan lies outside the array");
+        if ((rc = sort_long_slice(c, start, n))) return rc;
     }
     return RDST_OK;
 }
@@ -1056,41 +1045,23 @@ __global__ __launch_bounds__(BLOCK_THREADS) void segment_tile_copy_kernel(const 
     }
 }
 
-// The tiled layout behind the plan's; checked against the one statement of it.
-int tile_scratch(void* scratch, uint64_t n_segments, uint64_t len, uint32_t key_bytes, uint32_t val_bytes, uint32_t tile, TileBounds* B, TileScratch* out) {
-    B->n_segments = (uint32_t)n_segments;
-    B->n_long_bound = (uint32_t)std::min<uint64_t>(n_segments, len / ((uint64_t)tile + 1));
-    B->tiles_bound = (uint32_t)(len / tile) + B->n_long_bound;
-    B->tile = tile;
-    B->len = len;
-    const auto up = [](size_t bytes) { return (bytes + 255) / 256 * 256; };
+// The tiled route's bounds and its arrays behind the plan's, where rdst_segments_layout.h puts them.
+void tile_scratch(void* scratch, uint64_t n_segments, uint64_t len, uint32_t tile, TileBounds* B, TileScratch* out) {
+    const L::TileLayout at = L::tile_layout(n_segments, len, tile);
+    *B = {(uint32_t)n_segments, at.n_long_bound, at.tiles_bound, tile, len};
     char* base = static_cast<char*>(scratch);
-    char* at = base + rdst_hip_sort_segments_device_offsets_scratch_bytes(n_segments);
-    out->tile_base = reinterpret_cast<uint32_t*>(at);
-    at += up(((size_t)B->n_long_bound + 1) * sizeof(uint32_t));
-    out->digit_base = reinterpret_cast<uint32_t*>(at);
-    at += up((size_t)B->n_long_bound * RADIX * sizeof(uint32_t));
-    out->tile_counts = reinterpret_cast<uint32_t*>(at);
-    at += up((size_t)B->tiles_bound * RADIX * sizeof(uint32_t));
-    if ((uint64_t)(at - base) != rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes(n_segments, len, key_bytes, val_bytes))
-        return set_error(RDST_ERR_ARG, "segments: the tiled scratch layout and rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes disagree");
-    return RDST_OK;
+    *out = {reinterpret_cast<uint32_t*>(base + at.tile_base), reinterpret_cast<uint32_t*>(base + at.digit_base),
+            reinterpret_cast<uint32_t*>(base + at.tile_counts)};
 }
 
 template <typename K, typename V>
-int launch_tiled(K* keys, V* vals, K* tmp_keys, V* tmp_vals, const PlanScratch& P, const TileScratch& S, const TileBounds& B, int cus, uint32_t* err,
-                 rdst_key_kind kind, hipStream_t s) {
+int launch_tiled_t(K* keys, V* vals, K* tmp_keys, V* tmp_vals, const PlanScratch& P, const TileScratch& S, const TileBounds& B, int cus, uint32_t* err,
+                   rdst_key_kind kind, hipStream_t s) {
     constexpr int LEVELS = (int)sizeof(K);
     static_assert(BLOCK_WAVES * RADIX * sizeof(uint32_t) <= LDS_LIMIT, "a workgroup's LDS stays within 160 KiB");  // the per-wave count tables: 16 KiB
-    if (!limits_match<K, V>() || B.tile != (uint32_t)BLOCK_THREADS * block_kpt(sizeof(K), ValBytes<V>::value))
-        return set_error(RDST_ERR_ARG, "segments: the kernels' shapes and rdst_hip_sort_segments_limits disagree");
-    unsigned __int128 neg128, pos128;
-    rdst_internal::key_xor_masks(kind, (uint32_t)sizeof(K), &neg128, &pos128);
-    const K neg = (K)neg128, pos = (K)pos128;
-    const bool mapped = neg128 != 0 || pos128 != 0;
+    const KeyXor<K> x = key_xor<K>(kind);
     const rdst_segment_item* items = P.items;
-    const uint32_t* hdr = P.hdr;
-    const uint32_t* tile_base = S.tile_base;
+    const uint32_t *hdr = P.hdr, *tile_base = S.tile_base, *counts = S.tile_counts, *bases = S.digit_base;
     const dim3 block(BLOCK_THREADS);
     const dim3 tile_grid(std::min<uint32_t>(B.tiles_bound, (uint32_t)(TILE_GRID_PER_CU * cus)));
     const dim3 item_grid(B.n_long_bound);
@@ -1102,19 +1073,17 @@ int launch_tiled(K* keys, V* vals, K* tmp_keys, V* tmp_vals, const PlanScratch& 
         K* dst = level & 1 ? keys : tmp_keys;
         const V* vsrc = level & 1 ? tmp_vals : vals;
         V* vdst = level & 1 ? vals : tmp_vals;
-        rc = mapped ? launch("segment_tile_count_kernel", segment_tile_count_kernel<K, V, true>, tile_grid, block, 0, s, src, items, hdr, tile_base,
-                             S.tile_counts, B, shift, neg, pos)
-                    : launch("segment_tile_count_kernel", segment_tile_count_kernel<K, V, false>, tile_grid, block, 0, s, src, items, hdr, tile_base,
-                             S.tile_counts, B, shift, neg, pos);
+        rc = with_bools([&](auto mapped) {
+            return launch("segment_tile_count_kernel", segment_tile_count_kernel<K, V, decltype(mapped)::value>, tile_grid, block, 0, s, src, items, hdr,
+                          tile_base, S.tile_counts, B, shift, x.neg, x.pos);
+        }, x.mapped);
         if (rc) return rc;
         if ((rc = launch("segment_tile_offsets_kernel", segment_tile_offsets_kernel, item_grid, block, 0, s, hdr, tile_base, S.tile_counts, S.digit_base, B)))
             return rc;
-        const uint32_t* counts = S.tile_counts;
-        const uint32_t* bases = S.digit_base;
-        rc = mapped ? launch("segment_tile_scatter_kernel", segment_tile_scatter_kernel<K, V, true>, tile_grid, block, 0, s, src, dst, vsrc, vdst, items, hdr,
-                             tile_base, counts, bases, B, shift, neg, pos)
-                    : launch("segment_tile_scatter_kernel", segment_tile_scatter_kernel<K, V, false>, tile_grid, block, 0, s, src, dst, vsrc, vdst, items, hdr,
-                             tile_base, counts, bases, B, shift, neg, pos);
+        rc = with_bools([&](auto mapped) {
+            return launch("segment_tile_scatter_kernel", segment_tile_scatter_kernel<K, V, decltype(mapped)::value>, tile_grid, block, 0, s, src, dst, vsrc,
+                          vdst, items, hdr, tile_base, counts, bases, B, shift, x.neg, x.pos);
+        }, x.mapped);
         if (rc) return rc;
     }
     if constexpr (LEVELS & 1) {
@@ -1125,68 +1094,41 @@ int launch_tiled(K* keys, V* vals, K* tmp_keys, V* tmp_vals, const PlanScratch& 
     return rc;
 }
 
-int dispatch_tiled(void* keys, void* vals, void* tmp_keys, void* tmp_vals, uint32_t key_bytes, uint32_t val_bytes, const PlanScratch& P,
-                   const TileScratch& S, const TileBounds& B, int cus, uint32_t* err, rdst_key_kind kind, hipStream_t s) {
-    NoVal* const none = nullptr;
-    if (val_bytes == 0) {
-        switch (key_bytes) {
-            case 1: return launch_tiled(static_cast<uint8_t*>(keys), none, static_cast<uint8_t*>(tmp_keys), none, P, S, B, cus, err, kind, s);
-            case 2: return launch_tiled(static_cast<uint16_t*>(keys), none, static_cast<uint16_t*>(tmp_keys), none, P, S, B, cus, err, kind, s);
-            case 4: return launch_tiled(static_cast<uint32_t*>(keys), none, static_cast<uint32_t*>(tmp_keys), none, P, S, B, cus, err, kind, s);
-            case 8: return launch_tiled(static_cast<uint64_t*>(keys), none, static_cast<uint64_t*>(tmp_keys), none, P, S, B, cus, err, kind, s);
-            default: return launch_tiled(static_cast<u128*>(keys), none, static_cast<u128*>(tmp_keys), none, P, S, B, cus, err, kind, s);
-        }
-    }
-    if (key_bytes == 4)
-        return val_bytes == 4 ? launch_tiled(static_cast<uint32_t*>(keys), static_cast<uint32_t*>(vals), static_cast<uint32_t*>(tmp_keys),
-                                             static_cast<uint32_t*>(tmp_vals), P, S, B, cus, err, kind, s)
-                              : launch_tiled(static_cast<uint32_t*>(keys), static_cast<uint64_t*>(vals), static_cast<uint32_t*>(tmp_keys),
-                                             static_cast<uint64_t*>(tmp_vals), P, S, B, cus, err, kind, s);
-    return val_bytes == 4 ? launch_tiled(static_cast<uint64_t*>(keys), static_cast<uint32_t*>(vals), static_cast<uint64_t*>(tmp_keys),
-                                         static_cast<uint32_t*>(tmp_vals), P, S, B, cus, err, kind, s)
-                          : launch_tiled(static_cast<uint64_t*>(keys), static_cast<uint64_t*>(vals), static_cast<uint64_t*>(tmp_keys),
-                                         static_cast<uint64_t*>(tmp_vals), P, S, B, cus, err, kind, s);
+int launch_tiled(const SegCall& c, const PlanScratch& P, const TileScratch& S, const TileBounds& B, int cus, uint32_t* err) {
+    return with_key_value_types(c.key_bytes, c.val_bytes, [&](auto k, auto v) {
+        using K = decltype(k);
+        using V = decltype(v);
+        return launch_tiled_t(static_cast<K*>(c.keys), static_cast<V*>(c.vals), static_cast<K*>(c.tmp_keys), static_cast<V*>(c.tmp_vals), P, S, B, cus, err,
+                              c.kind, c.s);
+    });
 }
 
-// Both nowait entries.  val_bytes == 0: keys only.  Nothing between here and the return waits for the device or copies to
-// the host: the plan, the two counted launches and the tiled launches are enqueued and the call returns.
-int sort_segments_nowait(void* keys, void* vals, void* tmp_keys, void* tmp_vals, uint64_t len, const void* dev_offsets, uint32_t offset_bytes,
-                         uint64_t n_segments, uint32_t key_bytes, rdst_key_kind kind, uint32_t levels, uint32_t val_bytes, void* scratch,
-                         uint64_t scratch_bytes, void* stream) {
-    const bool pairs = val_bytes != 0;
-    int rc = rdst_internal::check_key_args(keys, n_segments ? len : 0, key_bytes, kind, levels);
-    if (rc) return rc;
-    if (n_segments == 0) return RDST_OK;
-    if ((rc = check_offsets_table(dev_offsets, offset_bytes, n_segments, len))) return rc;
-    if (len >= (1ull << 32)) return set_error(RDST_ERR_UNSUPPORTED, "segments: the nowait entries take len below 2^32 (tile indices and positions inside an item are u32)");
-    if (scratch == nullptr) return set_error(RDST_ERR_ARG, "segments: null scratch");
-    if (reinterpret_cast<uintptr_t>(scratch) % 256) return set_error(RDST_ERR_ALIGN, "segments: scratch not aligned to 256 bytes");
-    if (scratch_bytes < rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes(n_segments, len, key_bytes, val_bytes))
-        return set_error(RDST_ERR_ARG, "segments: scratch_bytes is below rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes(n_segments, len, ...)");
-    if (pairs && vals == nullptr && len != 0) return set_error(RDST_ERR_ARG, "null value pointer");
-    if (pairs && reinterpret_cast<uintptr_t>(vals) % val_bytes) return set_error(RDST_ERR_ALIGN, "value pointer not aligned to the value size");
-    if (len != 0 && (tmp_keys == nullptr || (pairs && tmp_vals == nullptr))) return set_error(RDST_ERR_ARG, "segments: the nowait entries need a tmp array of len elements");
-    if (reinterpret_cast<uintptr_t>(tmp_keys) % key_bytes) return set_error(RDST_ERR_ALIGN, "tmp pointer not aligned to the element size");
-    if (pairs && reinterpret_cast<uintptr_t>(tmp_vals) % val_bytes) return set_error(RDST_ERR_ALIGN, "tmp value pointer not aligned to the value size");
-    uint32_t lim[2];
-    if ((rc = rdst_hip_sort_segments_limits(key_bytes, val_bytes, lim))) return rc;
-    PlanScratch P;
-    if ((rc = plan_scratch(scratch, n_segments, &P))) return rc;
+// Both nowait entries.  Nothing between here and the return waits for the device or copies to the host: the plan, the two
+// counted launches and the tiled launches are enqueued and the call returns.
+int sort_segments_nowait(const SegCall& c, bool pair_entry, const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments, void* scratch,
+                         uint64_t scratch_bytes) {
+    int rc = check_call(c, pair_entry, n_segments);
+    if (rc || n_segments == 0) return rc;
+    if ((rc = check_offsets_table(dev_offsets, offset_bytes, n_segments, c.len))) return rc;
+    if (c.len >= (1ull << 32)) return set_error(RDST_ERR_UNSUPPORTED, "segments: the nowait entries take len below 2^32 (tile indices and positions inside an item are u32)");
+    const uint32_t tile = L::block_max(c.key_bytes, c.val_bytes);
+    if ((rc = check_scratch(scratch, scratch_bytes, L::tile_layout(n_segments, c.len, tile).total,
+                            "segments: scratch_bytes is below rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes(n_segments, len, ...)")))
+        return rc;
+    if ((rc = check_pointers(c, c.len != 0 ? "segments: the nowait entries need a tmp array of len elements" : nullptr))) return rc;
+    const PlanScratch P = plan_scratch(scratch, n_segments);
     TileBounds B;
     TileScratch S;
-    if ((rc = tile_scratch(scratch, n_segments, len, key_bytes, val_bytes, lim[1], &B, &S))) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
+    tile_scratch(scratch, n_segments, c.len, tile, &B, &S);
     uint32_t* err = nullptr;
     int cus = 0;
     if ((rc = rdst_internal::device_error_word(&err, &cus))) return rc;  // (takes the mutex itself)
     std::lock_guard<std::mutex> lock(rdst_internal::library_mutex());
-    if ((rc = enqueue_plan(dev_offsets, offset_bytes, n_segments, len, key_bytes, val_bytes, P, 2u, err, s))) return rc;
-    if ((rc = rdst_internal::profile_open_run(s))) return rc;
-    if ((rc = dispatch_counted(keys, vals, key_bytes, val_bytes, P, n_segments, len, kind, s))) return rc;
-    if ((rc = rdst_internal::profile_stage_end(s, RDST_STAGE_SEGMENTS))) return rc;
+    if ((rc = enqueue_plan(dev_offsets, offset_bytes, n_segments, c.len, c.key_bytes, c.val_bytes, P, 2u, err, c.s))) return rc;
+    if ((rc = batched_stage(c.s, [&] { return launch_counted(c, P, n_segments); }))) return rc;
     if (B.n_long_bound == 0) return RDST_OK;  // no segment of this table can be longer than block_max
-    if ((rc = dispatch_tiled(keys, vals, tmp_keys, tmp_vals, key_bytes, val_bytes, P, S, B, cus, err, kind, s))) return rc;
-    return rdst_internal::profile_stage_end(s, RDST_STAGE_SEGMENTS_TILED);
+    if ((rc = launch_tiled(c, P, S, B, cus, err))) return rc;
+    return rdst_internal::profile_stage_end(c.s, RDST_STAGE_SEGMENTS_TILED);
 }
 
 }  // namespace
@@ -1194,39 +1136,31 @@ int sort_segments_nowait(void* keys, void* vals, void* tmp_keys, void* tmp_vals,
 extern "C" int rdst_hip_sort_segments_device_offsets(void* dev_keys, void* dev_tmp, uint64_t tmp_elems, uint64_t len, const void* dev_offsets,
                                                      uint32_t offset_bytes, uint64_t n_segments, uint32_t elem_bytes, rdst_key_kind kind,
                                                      uint32_t levels, void* dev_scratch, uint64_t scratch_bytes, void* stream) {
-    return sort_segments_offsets(dev_keys, nullptr, dev_tmp, nullptr, tmp_elems, len, dev_offsets, offset_bytes, n_segments, elem_bytes, kind, levels, 0,
-                                 dev_scratch, scratch_bytes, stream);
+    return sort_segments_offsets({dev_keys, nullptr, dev_tmp, nullptr, len, elem_bytes, 0, kind, levels, static_cast<hipStream_t>(stream)}, false, tmp_elems,
+                                 dev_offsets, offset_bytes, n_segments, dev_scratch, scratch_bytes);
 }
 
 extern "C" int rdst_hip_sort_segments_pairs_device_offsets(void* dev_keys, void* dev_vals, void* dev_tmp_keys, void* dev_tmp_vals, uint64_t tmp_elems,
                                                            uint64_t len, const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments,
                                                            uint32_t key_bytes, rdst_key_kind kind, uint32_t levels, uint32_t val_bytes,
                                                            void* dev_scratch, uint64_t scratch_bytes, void* stream) {
-    int rc = rdst_internal::check_key_args(dev_keys, n_segments ? len : 0, key_bytes, kind, levels);
-    if (rc) return rc;
-    if (key_bytes != 4 && key_bytes != 8) return set_error(RDST_ERR_UNSUPPORTED, "key-value sorts take 4- or 8-byte keys");
-    if (val_bytes != 4 && val_bytes != 8) return set_error(RDST_ERR_UNSUPPORTED, "key-value sorts carry 4- or 8-byte values");
-    return sort_segments_offsets(dev_keys, dev_vals, dev_tmp_keys, dev_tmp_vals, tmp_elems, len, dev_offsets, offset_bytes, n_segments, key_bytes, kind,
-                                 levels, val_bytes, dev_scratch, scratch_bytes, stream);
+    return sort_segments_offsets({dev_keys, dev_vals, dev_tmp_keys, dev_tmp_vals, len, key_bytes, val_bytes, kind, levels, static_cast<hipStream_t>(stream)},
+                                 true, tmp_elems, dev_offsets, offset_bytes, n_segments, dev_scratch, scratch_bytes);
 }
 
 extern "C" int rdst_hip_sort_segments_device_offsets_nowait(void* dev_keys, void* dev_tmp, uint64_t len, const void* dev_offsets, uint32_t offset_bytes,
                                                             uint64_t n_segments, uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels,
                                                             void* dev_scratch, uint64_t scratch_bytes, void* stream) {
-    return sort_segments_nowait(dev_keys, nullptr, dev_tmp, nullptr, len, dev_offsets, offset_bytes, n_segments, elem_bytes, kind, levels, 0, dev_scratch,
-                                scratch_bytes, stream);
+    return sort_segments_nowait({dev_keys, nullptr, dev_tmp, nullptr, len, elem_bytes, 0, kind, levels, static_cast<hipStream_t>(stream)}, false, dev_offsets,
+                                offset_bytes, n_segments, dev_scratch, scratch_bytes);
 }
 
 extern "C" int rdst_hip_sort_segments_pairs_device_offsets_nowait(void* dev_keys, void* dev_vals, void* dev_tmp_keys, void* dev_tmp_vals, uint64_t len,
                                                                   const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments,
                                                                   uint32_t key_bytes, rdst_key_kind kind, uint32_t levels, uint32_t val_bytes,
                                                                   void* dev_scratch, uint64_t scratch_bytes, void* stream) {
-    int rc = rdst_internal::check_key_args(dev_keys, n_segments ? len : 0, key_bytes, kind, levels);
-    if (rc) return rc;
-    if (key_bytes != 4 && key_bytes != 8) return set_error(RDST_ERR_UNSUPPORTED, "key-value sorts take 4- or 8-byte keys");
-    if (val_bytes != 4 && val_bytes != 8) return set_error(RDST_ERR_UNSUPPORTED, "key-value sorts carry 4- or 8-byte values");
-    return sort_segments_nowait(dev_keys, dev_vals, dev_tmp_keys, dev_tmp_vals, len, dev_offsets, offset_bytes, n_segments, key_bytes, kind, levels,
-                                val_bytes, dev_scratch, scratch_bytes, stream);
+    return sort_segments_nowait({dev_keys, dev_vals, dev_tmp_keys, dev_tmp_vals, len, key_bytes, val_bytes, kind, levels, static_cast<hipStream_t>(stream)},
+                                true, dev_offsets, offset_bytes, n_segments, dev_scratch, scratch_bytes);
 }
 
 extern "C" int rdst_hip_debug_segments_plan_device(const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments, uint64_t len,
@@ -1242,8 +1176,7 @@ extern "C" int rdst_hip_debug_segments_plan_device(const void* dev_offsets, uint
     *flags_out = 0;
     if (n_segments == 0) return RDST_OK;
     if ((rc = check_offsets_args(dev_offsets, offset_bytes, n_segments, len, dev_scratch, scratch_bytes))) return rc;
-    PlanScratch P;
-    if ((rc = plan_scratch(dev_scratch, n_segments, &P))) return rc;
+    const PlanScratch P = plan_scratch(dev_scratch, n_segments);
     hipStream_t s = static_cast<hipStream_t>(stream);
     std::lock_guard<std::mutex> lock(rdst_internal::library_mutex());
     if ((rc = enqueue_plan(dev_offsets, offset_bytes, n_segments, len, elem_bytes, val_bytes, P, 0u, nullptr, s))) return rc;
@@ -1263,15 +1196,13 @@ extern "C" int rdst_hip_debug_segments_plan_device(const void* dev_offsets, uint
 
 extern "C" int rdst_hip_sort_segments_device(void* dev_keys, void* dev_tmp, uint64_t tmp_elems, uint64_t len, const uint64_t* offsets,
                                              uint64_t n_segments, uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels, void* stream) {
-    return sort_segments(dev_keys, nullptr, dev_tmp, nullptr, tmp_elems, len, offsets, n_segments, elem_bytes, kind, levels, 0, stream);
+    return sort_segments({dev_keys, nullptr, dev_tmp, nullptr, len, elem_bytes, 0, kind, levels, static_cast<hipStream_t>(stream)}, false, tmp_elems, offsets,
+                         n_segments);
 }
 
 extern "C" int rdst_hip_sort_segments_pairs_device(void* dev_keys, void* dev_vals, void* dev_tmp_keys, void* dev_tmp_vals, uint64_t tmp_elems,
                                                    uint64_t len, const uint64_t* offsets, uint64_t n_segments, uint32_t key_bytes, rdst_key_kind kind,
                                                    uint32_t levels, uint32_t val_bytes, void* stream) {
-    int rc = rdst_internal::check_key_args(dev_keys, n_segments ? len : 0, key_bytes, kind, levels);
-    if (rc) return rc;
-    if (key_bytes != 4 && key_bytes != 8) return set_error(RDST_ERR_UNSUPPORTED, "key-value sorts take 4- or 8-byte keys");
-    if (val_bytes != 4 && val_bytes != 8) return set_error(RDST_ERR_UNSUPPORTED, "key-value sorts carry 4- or 8-byte values");
-    return sort_segments(dev_keys, dev_vals, dev_tmp_keys, dev_tmp_vals, tmp_elems, len, offsets, n_segments, key_bytes, kind, levels, val_bytes, stream);
+    return sort_segments({dev_keys, dev_vals, dev_tmp_keys, dev_tmp_vals, len, key_bytes, val_bytes, kind, levels, static_cast<hipStream_t>(stream)}, true,
+                         tmp_elems, offsets, n_segments);
 }

@@ -1,0 +1,68 @@
+// rdst_segments_layout.h — the segmented sort's shapes and scratch layouts, stated once for the kernels and their launches
+// (rdst_segments.hip) and for the host-only half (rdst_segments.cpp: rdst_hip_sort_segments_limits and the two
+// ..._scratch_bytes functions).  No HIP here, and constexpr throughout: the kernels take the shapes as template arguments.
+#ifndef RDST_SEGMENTS_LAYOUT_H
+#define RDST_SEGMENTS_LAYOUT_H
+
+#include <stddef.h>
+#include <stdint.h>
+
+#include "rdst_hip.h"
+
+namespace rdst_segments_layout {
+
+// ---- widths ----------------------------------------------------------------------------------------------------------
+constexpr bool key_width_ok(uint32_t b) { return b == 1 || b == 2 || b == 4 || b == 8 || b == 16; }
+constexpr bool pair_width_ok(uint32_t b) { return b == 4 || b == 8; }  // the keys and the values of a key-value sort
+
+// ---- shapes ----------------------------------------------------------------------------------------------------------
+// Keys per lane: the wave class holds wave_kpt keys per lane of its one wave, the block class block_kpt per thread of its
+// 1024.  Keys only, the block class is the one-workgroup sort's tile (64 KiB of keys; 16 384 one- and two-byte keys); with
+// values, key and value tiles share the 160 KiB of LDS beside the 16 KiB of count tables.
+constexpr int BLOCK_THREADS = 1024;
+constexpr int wave_kpt(size_t key_bytes) { return key_bytes == 16 ? 4 : 8; }
+constexpr int block_kpt(size_t key_bytes, size_t val_bytes) {
+    return val_bytes != 0 && key_bytes + val_bytes > 8 ? 8 : (key_bytes <= 4 ? 16 : (key_bytes == 8 ? 8 : 4));
+}
+constexpr uint32_t wave_max(size_t key_bytes) { return 64u * (uint32_t)wave_kpt(key_bytes); }  // the longest segment of the wave class
+constexpr uint32_t block_max(size_t key_bytes, size_t val_bytes) {                                // ... of the block class; the tiled route's tile
+    return (uint32_t)BLOCK_THREADS * (uint32_t)block_kpt(key_bytes, val_bytes);
+}
+
+// ---- scratch (byte offsets from its 256-byte aligned base; every array is rounded up to 256 bytes) ----------------------
+constexpr uint64_t MAX_SEGMENTS = 1ull << 30;  // of a table in device memory
+constexpr uint64_t up256(uint64_t bytes) { return (bytes + 255) / 256 * 256; }
+
+// Device-resident offsets: what the plan keeps.  A 256-byte header; four u32 arrays of n_segments (the class keys and
+// segment indices of the plan's pair sort, and that sort's two tmps); the item table (16 bytes per segment): 32 bytes per
+// segment and at most 1 536 bytes besides.
+constexpr uint64_t PLAN_HEADER_BYTES = 256;
+struct PlanLayout {
+    uint64_t keys, segs, tmp_keys, tmp_segs, items, total;
+};
+constexpr PlanLayout plan_layout(uint64_t n_segments) {
+    const uint64_t arr = up256(n_segments * sizeof(uint32_t)), at = PLAN_HEADER_BYTES;
+    return {at, at + arr, at + 2 * arr, at + 3 * arr, at + 4 * arr, at + 4 * arr + up256(n_segments * sizeof(rdst_segment_item))};
+}
+
+// The nowait entries: the plan's layout, then what the tiled route keeps for the long class.  What the host knows bounds
+// that class: a long segment holds more than block_max keys, so there are at most n_long_bound = min(n_segments,
+// len / (block_max + 1)) of them, and with tiles of `tile` = block_max keys item i has ceil(len_i / tile) tiles: at most
+// tiles_bound = len / tile + n_long_bound in all.  Behind the plan: tile_base (n_long_bound + 1 u32), digit_base (256 u32
+// per possible long item), tile_counts (256 u32 per possible tile).  len < 2^32.
+struct TileLayout {
+    uint32_t n_long_bound, tiles_bound;
+    uint64_t tile_base, digit_base, tile_counts, total;
+};
+constexpr TileLayout tile_layout(uint64_t n_segments, uint64_t len, uint32_t tile) {
+    const uint64_t longs = len / ((uint64_t)tile + 1) < n_segments ? len / ((uint64_t)tile + 1) : n_segments;
+    const uint64_t tiles = len / tile + longs;
+    const uint64_t tile_base = plan_layout(n_segments).total;
+    const uint64_t digit_base = tile_base + up256((longs + 1) * sizeof(uint32_t));
+    const uint64_t tile_counts = digit_base + up256(longs * 256 * sizeof(uint32_t));
+    return {(uint32_t)longs, (uint32_t)tiles, tile_base, digit_base, tile_counts, tile_counts + up256(tiles * 256 * sizeof(uint32_t))};
+}
+
+}  // namespace rdst_segments_layout
+
+#endif  // RDST_SEGMENTS_LAYOUT_H

@@ -199,20 +199,10 @@ def segments_plan(offsets, n, dtype, val_bytes=0):
     return [(int(it.start), int(it.len), int(it.seg)) for it in items[:total]], tuple(int(c) for c in counts), int(tmp_elems.value)
 
 
-def sort_segments_device_tensor(keys, offsets, tmp=None, values=None, tmp_values=None, check=True, key=None):
-    """``rdst_hip_sort_segments_device`` (with ``values``: ``rdst_hip_sort_segments_pairs_device``): sort every segment
-    ``keys[offsets[s]:offsets[s + 1]]`` of a contiguous 1-D HIP tensor on its own, in one call (``key="u128"/"i128"``: shape
-    (n, 2), offsets count keys).  ``offsets``: a sequence, a numpy array or a torch tensor of n_segments + 1 non-decreasing
-    element indices; the library reads it on the HOST, so a device tensor is copied to the host once, here.  Elements
-    outside [offsets[0], offsets[-1]) stay as they are.  ``values`` (4- or 8-byte elements, same length as ``keys``) are
-    permuted with their keys; equal keys keep their input order.  ``tmp`` (and ``tmp_values``) are needed only when a segment
-    is longer than ``segments_limits(...)[1]``: at least as many elements as the longest such segment; they are allocated
-    when omitted and needed, and not at all otherwise.  Runs on the tensor's current stream; with ``check`` the call
-    blocks and raises if a kernel reported failure.  Offsets that are computed on the device and should stay there:
-    :func:`sort_segments_device_offsets_tensor`."""
-    import torch
+def _segments_operands(name, keys, values, key):
+    """the keys and values of a segmented tensor wrapper, checked: (kind, nbytes, levels, n, per_key, vbytes)"""
     if not keys.is_cuda:
-        raise ValueError("sort_segments_device_tensor needs a tensor on a HIP device")
+        raise ValueError(f"{name} needs a tensor on a HIP device")
     if _wide(key):
         _check_wide_shape(tuple(keys.shape), keys.element_size())
     elif keys.dim() != 1:
@@ -226,6 +216,42 @@ def sort_segments_device_tensor(keys, offsets, tmp=None, values=None, tmp_values
         if not values.is_cuda or values.device != keys.device or values.dim() != 1 or values.numel() != n or not values.is_contiguous():
             raise ValueError("values must be a contiguous 1-D tensor of the keys' length on the keys' device")
         vbytes = values.element_size()
+    per_key = keys.numel() // n if n else 1      # container elements per key (2 for the 128-bit limbs)
+    return kind, nbytes, levels, n, per_key, vbytes
+
+
+def _mismatch(t, like):
+    """a tmp (tmp_values) tensor that cannot stand in for `like`, whatever its length"""
+    return t.dtype != like.dtype or not t.is_contiguous() or t.device != like.device
+
+
+def _ptr(t, empty_is_null=False):
+    return ctypes.c_void_p(t.data_ptr() if t is not None and (t.numel() or not empty_is_null) else None)
+
+
+def _segments_call(keys, check, entry, *args):
+    """the tail of a segmented tensor wrapper: `entry(*args, stream)` on the keys' device and current stream, then the status"""
+    import torch
+    with torch.cuda.device(keys.device):
+        s = _stream_handle(keys)
+        _lib.check(entry(*args, s))
+        if check:
+            _lib.check(_lib.load().rdst_hip_device_status(s))
+
+
+def sort_segments_device_tensor(keys, offsets, tmp=None, values=None, tmp_values=None, check=True, key=None):
+    """``rdst_hip_sort_segments_device`` (with ``values``: ``rdst_hip_sort_segments_pairs_device``): sort every segment
+    ``keys[offsets[s]:offsets[s + 1]]`` of a contiguous 1-D HIP tensor on its own, in one call (``key="u128"/"i128"``: shape
+    (n, 2), offsets count keys).  ``offsets``: a sequence, a numpy array or a torch tensor of n_segments + 1 non-decreasing
+    element indices; the library reads it on the HOST, so a device tensor is copied to the host once, here.  Elements
+    outside [offsets[0], offsets[-1]) stay as they are.  ``values`` (4- or 8-byte elements, same length as ``keys``) are
+    permuted with their keys; equal keys keep their input order.  ``tmp`` (and ``tmp_values``) are needed only when a segment
+    is longer than ``segments_limits(...)[1]``: at least as many elements as the longest such segment; they are allocated
+    when omitted and needed, and not at all otherwise.  Runs on the tensor's current stream; with ``check`` the call
+    blocks and raises if a kernel reported failure.  Offsets that are computed on the device and should stay there:
+    :func:`sort_segments_device_offsets_tensor`."""
+    import torch
+    kind, nbytes, levels, n, per_key, vbytes = _segments_operands("sort_segments_device_tensor", keys, values, key)
     off = _host_offsets(offsets)
     n_segments = off.size - 1
     lib = _lib.load()
@@ -236,35 +262,26 @@ def sort_segments_device_tensor(keys, offsets, tmp=None, values=None, tmp_values
     if rc != _lib.RDST_OK and counts[0] + counts[1] + counts[2] == 0:   # (a list that does not fit capacity 0 is the expected answer)
         _lib.check(rc)
     need = int(need.value)
-    per_key = keys.numel() // n if n else 1      # container elements per key (2 for the 128-bit limbs)
     tmp_elems = 0
     if need:
         if tmp is None:
             tmp = torch.empty(need * per_key, dtype=keys.dtype, device=keys.device)
-        elif tmp.dtype != keys.dtype or not tmp.is_contiguous() or tmp.device != keys.device or tmp.numel() < need * per_key:
+        elif _mismatch(tmp, keys) or tmp.numel() < need * per_key:
             raise ValueError(f"tmp must be a contiguous tensor of the keys' dtype and device with at least {need} keys")
         tmp_elems = tmp.numel() // per_key
         if values is not None:
             if tmp_values is None:
                 tmp_values = torch.empty(need, dtype=values.dtype, device=values.device)
-            elif tmp_values.dtype != values.dtype or not tmp_values.is_contiguous() or tmp_values.device != values.device or tmp_values.numel() < need:
+            elif _mismatch(tmp_values, values) or tmp_values.numel() < need:
                 raise ValueError(f"tmp_values must be a contiguous tensor of the values' dtype and device with at least {need} elements")
             tmp_elems = min(tmp_elems, tmp_values.numel())
     elif tmp is not None:
         tmp_elems = tmp.numel() // per_key
-
-    def ptr(t):
-        return ctypes.c_void_p(t.data_ptr() if t is not None else None)
-
-    with torch.cuda.device(keys.device):
-        s = _stream_handle(keys)
-        if values is None:
-            _lib.check(lib.rdst_hip_sort_segments_device(ptr(keys), ptr(tmp), tmp_elems, n, offp, n_segments, nbytes, kind, levels, s))
-        else:
-            _lib.check(lib.rdst_hip_sort_segments_pairs_device(ptr(keys), ptr(values), ptr(tmp), ptr(tmp_values), tmp_elems, n, offp,
-                                                               n_segments, nbytes, kind, levels, vbytes, s))
-        if check:
-            _lib.check(lib.rdst_hip_device_status(s))
+    if values is None:
+        _segments_call(keys, check, lib.rdst_hip_sort_segments_device, _ptr(keys), _ptr(tmp), tmp_elems, n, offp, n_segments, nbytes, kind, levels)
+    else:
+        _segments_call(keys, check, lib.rdst_hip_sort_segments_pairs_device, _ptr(keys), _ptr(values), _ptr(tmp), _ptr(tmp_values), tmp_elems, n, offp,
+                       n_segments, nbytes, kind, levels, vbytes)
 
 
 def segments_device_offsets_scratch_bytes(n_segments):
@@ -287,9 +304,9 @@ def _device_offsets(offsets, keys, n):
     return offsets.numel() - 1, offsets.element_size()
 
 
-def _offsets_scratch(scratch, n_segments, device):
+def _segments_scratch(scratch, need, device):
+    """(scratch, its bytes) for an entry that asks for `need` bytes: the caller's tensor, checked, or a fresh one"""
     import torch
-    need = segments_device_offsets_scratch_bytes(n_segments)
     if scratch is None:
         return torch.empty(max(need, 1), dtype=torch.uint8, device=device), need   # the caching allocator hands out 512-byte aligned blocks
     if not scratch.is_cuda or scratch.device != device or not scratch.is_contiguous() or scratch.numel() * scratch.element_size() < need:
@@ -311,7 +328,7 @@ def segments_plan_device(offsets, n, dtype, val_bytes=0, scratch=None):
     tmp_elems = ctypes.c_uint64(0)
     flags = ctypes.c_uint32(0)
     with torch.cuda.device(offsets.device):
-        scratch, sbytes = _offsets_scratch(scratch, n_segments, offsets.device)
+        scratch, sbytes = _segments_scratch(scratch, segments_device_offsets_scratch_bytes(n_segments), offsets.device)
         _lib.check(lib.rdst_hip_debug_segments_plan_device(ctypes.c_void_p(offsets.data_ptr()), obytes, n_segments, int(n), nbytes, int(val_bytes),
                                                            ctypes.c_void_p(scratch.data_ptr()), sbytes, items, n_segments, counts,
                                                            ctypes.byref(tmp_elems), ctypes.byref(flags), _stream_handle(offsets)))
@@ -334,53 +351,31 @@ def sort_segments_device_offsets_tensor(keys, offsets, tmp=None, values=None, tm
     many elements as the longest segment may have) longer segments are sorted too; the call then waits once for the
     stream to read the plan's counts, and an invalid table or a ``tmp`` that is too short raises at once."""
     import torch
-    if not keys.is_cuda:
-        raise ValueError("sort_segments_device_offsets_tensor needs a tensor on a HIP device")
-    if _wide(key):
-        _check_wide_shape(tuple(keys.shape), keys.element_size())
-    elif keys.dim() != 1:
-        raise ValueError("keys must be a contiguous 1-D tensor")
-    if not keys.is_contiguous():
-        raise ValueError("keys must be a contiguous 1-D tensor")
-    kind, nbytes, levels = key_info(key if key else keys.dtype)
-    n = keys.numel() * keys.element_size() // nbytes
-    vbytes = 0
-    if values is not None:
-        if not values.is_cuda or values.device != keys.device or values.dim() != 1 or values.numel() != n or not values.is_contiguous():
-            raise ValueError("values must be a contiguous 1-D tensor of the keys' length on the keys' device")
-        vbytes = values.element_size()
+    kind, nbytes, levels, n, per_key, vbytes = _segments_operands("sort_segments_device_offsets_tensor", keys, values, key)
     n_segments, obytes = _device_offsets(offsets, keys, n)
-    per_key = keys.numel() // n if n else 1      # container elements per key (2 for the 128-bit limbs)
     tmp_elems = 0
     if tmp is not None:
-        if tmp.dtype != keys.dtype or not tmp.is_contiguous() or tmp.device != keys.device:
+        if _mismatch(tmp, keys):
             raise ValueError("tmp must be a contiguous tensor of the keys' dtype and device")
         tmp_elems = tmp.numel() // per_key
         if values is not None:
             if tmp_values is None:
                 tmp_values = torch.empty(tmp_elems, dtype=values.dtype, device=values.device)
-            elif tmp_values.dtype != values.dtype or not tmp_values.is_contiguous() or tmp_values.device != values.device:
+            elif _mismatch(tmp_values, values):
                 raise ValueError("tmp_values must be a contiguous tensor of the values' dtype and device")
             tmp_elems = min(tmp_elems, tmp_values.numel())
     elif tmp_values is not None:
         raise ValueError("tmp_values without tmp")
-
-    def ptr(t):
-        return ctypes.c_void_p(t.data_ptr() if t is not None else None)
-
     lib = _lib.load()
-    with torch.cuda.device(keys.device):
-        scratch, sbytes = _offsets_scratch(scratch, n_segments, keys.device)
-        s = _stream_handle(keys)
-        if values is None:
-            _lib.check(lib.rdst_hip_sort_segments_device_offsets(ptr(keys), ptr(tmp) if tmp_elems else None, tmp_elems, n, ptr(offsets), obytes,
-                                                                 n_segments, nbytes, kind, levels, ptr(scratch), sbytes, s))
-        else:
-            _lib.check(lib.rdst_hip_sort_segments_pairs_device_offsets(ptr(keys), ptr(values), ptr(tmp) if tmp_elems else None,
-                                                                       ptr(tmp_values) if tmp_elems else None, tmp_elems, n, ptr(offsets), obytes,
-                                                                       n_segments, nbytes, kind, levels, vbytes, ptr(scratch), sbytes, s))
-        if check:
-            _lib.check(lib.rdst_hip_device_status(s))
+    scratch, sbytes = _segments_scratch(scratch, segments_device_offsets_scratch_bytes(n_segments), keys.device)
+    if not tmp_elems:
+        tmp = tmp_values = None
+    if values is None:
+        _segments_call(keys, check, lib.rdst_hip_sort_segments_device_offsets, _ptr(keys), _ptr(tmp), tmp_elems, n, _ptr(offsets), obytes, n_segments,
+                       nbytes, kind, levels, _ptr(scratch), sbytes)
+    else:
+        _segments_call(keys, check, lib.rdst_hip_sort_segments_pairs_device_offsets, _ptr(keys), _ptr(values), _ptr(tmp), _ptr(tmp_values), tmp_elems, n,
+                       _ptr(offsets), obytes, n_segments, nbytes, kind, levels, vbytes, _ptr(scratch), sbytes)
 
 
 def segments_nowait_scratch_bytes(n_segments, n, dtype, val_bytes=0):
@@ -402,58 +397,34 @@ def sort_segments_device_offsets_nowait_tensor(keys, offsets, tmp=None, values=N
     omitted); calls on one stream may share it.  A table that decreases or ends past the keys leaves every key, value and
     tmp element as it was and raises from :func:`device_status` (here, with ``check``)."""
     import torch
-    if not keys.is_cuda:
-        raise ValueError("sort_segments_device_offsets_nowait_tensor needs a tensor on a HIP device")
-    if _wide(key):
-        _check_wide_shape(tuple(keys.shape), keys.element_size())
-    elif keys.dim() != 1:
-        raise ValueError("keys must be a contiguous 1-D tensor")
-    if not keys.is_contiguous():
-        raise ValueError("keys must be a contiguous 1-D tensor")
-    kind, nbytes, levels = key_info(key if key else keys.dtype)
-    n = keys.numel() * keys.element_size() // nbytes
+    kind, nbytes, levels, n, _per_key, vbytes = _segments_operands("sort_segments_device_offsets_nowait_tensor", keys, values, key)
     if n >= 2**32:
         raise ValueError("the nowait segmented sort takes fewer than 2^32 keys")
-    vbytes = 0
-    if values is not None:
-        if not values.is_cuda or values.device != keys.device or values.dim() != 1 or values.numel() != n or not values.is_contiguous():
-            raise ValueError("values must be a contiguous 1-D tensor of the keys' length on the keys' device")
-        vbytes = values.element_size()
-    elif tmp_values is not None:
+    if values is None and tmp_values is not None:
         raise ValueError("tmp_values without values")
     n_segments, obytes = _device_offsets(offsets, keys, n)
     if tmp is None:
         tmp = torch.empty_like(keys)
-    elif tmp.dtype != keys.dtype or not tmp.is_contiguous() or tmp.device != keys.device or tmp.numel() < keys.numel():
+    elif _mismatch(tmp, keys) or tmp.numel() < keys.numel():
         raise ValueError("tmp must be a contiguous tensor of the keys' dtype and device with at least as many elements")
     if values is not None:
         if tmp_values is None:
             tmp_values = torch.empty_like(values)
-        elif tmp_values.dtype != values.dtype or not tmp_values.is_contiguous() or tmp_values.device != values.device or tmp_values.numel() < n:
+        elif _mismatch(tmp_values, values) or tmp_values.numel() < n:
             raise ValueError("tmp_values must be a contiguous tensor of the values' dtype and device with at least as many elements")
+    lib = _lib.load()
+    need = int(lib.rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes(n_segments, n, nbytes, vbytes))
+    scratch, sbytes = _segments_scratch(scratch, need, keys.device)
 
     def ptr(t):
-        return ctypes.c_void_p(t.data_ptr() if t is not None and t.numel() else None)
+        return _ptr(t, empty_is_null=True)
 
-    lib = _lib.load()
-    with torch.cuda.device(keys.device):
-        need = int(lib.rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes(n_segments, n, nbytes, vbytes))
-        if scratch is None:
-            scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=keys.device)   # the caching allocator hands out 512-byte aligned blocks
-            sbytes = need
-        elif not scratch.is_cuda or scratch.device != keys.device or not scratch.is_contiguous() or scratch.numel() * scratch.element_size() < need:
-            raise ValueError(f"scratch must be a contiguous tensor on the keys' device with at least {need} bytes")
-        else:
-            sbytes = scratch.numel() * scratch.element_size()
-        s = _stream_handle(keys)
-        if values is None:
-            _lib.check(lib.rdst_hip_sort_segments_device_offsets_nowait(ptr(keys), ptr(tmp), n, ptr(offsets), obytes, n_segments, nbytes, kind, levels,
-                                                                        ptr(scratch), sbytes, s))
-        else:
-            _lib.check(lib.rdst_hip_sort_segments_pairs_device_offsets_nowait(ptr(keys), ptr(values), ptr(tmp), ptr(tmp_values), n, ptr(offsets), obytes,
-                                                                              n_segments, nbytes, kind, levels, vbytes, ptr(scratch), sbytes, s))
-        if check:
-            _lib.check(lib.rdst_hip_device_status(s))
+    if values is None:
+        _segments_call(keys, check, lib.rdst_hip_sort_segments_device_offsets_nowait, ptr(keys), ptr(tmp), n, ptr(offsets), obytes, n_segments, nbytes, kind,
+                       levels, ptr(scratch), sbytes)
+    else:
+        _segments_call(keys, check, lib.rdst_hip_sort_segments_pairs_device_offsets_nowait, ptr(keys), ptr(values), ptr(tmp), ptr(tmp_values), n, ptr(offsets),
+                       obytes, n_segments, nbytes, kind, levels, vbytes, ptr(scratch), sbytes)
 
 
 def sort_records_by_key(records, key_field):
