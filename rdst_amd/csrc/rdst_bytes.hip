@@ -369,11 +369,6 @@ __global__ __launch_bounds__(256) void rows_gather_kernel(const U* __restrict__ 
 // ------------------------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------------------------
-#define BYTES_TRY(expr)                                                           \
-    do {                                                                          \
-        hipError_t e__ = (expr);                                                  \
-        if (e__ != hipSuccess) return set_error(RDST_ERR_HIP, #expr, e__);        \
-    } while (0)
 
 uint64_t align256(uint64_t x) { return (x + 255) / 256 * 256; }
 
@@ -454,8 +449,8 @@ int bytes_order(const uint8_t* rows, uint64_t n, uint32_t stride, uint32_t off, 
                          long_run, err)))
             return rc;
         uint64_t h[4] = {0, 0, 0, 0};
-        BYTES_TRY(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, s));
-        BYTES_TRY(hipStreamSynchronize(s));
+        RDST_HIP_TRY(hipMemcpyAsync(h, cnt, sizeof h, hipMemcpyDeviceToHost, s));
+        RDST_HIP_TRY(hipStreamSynchronize(s));
         const uint64_t tied = h[CNT_TIED], runs = h[CNT_RUNS], long_rows = h[CNT_LONG_ROWS], long_runs = h[CNT_LONG_RUNS];
         if (tied > m || 2 * runs > tied || long_rows > tied || long_runs > runs || (long_runs == 0) != (long_rows == 0))
             return set_error(RDST_ERR_DEVICE, "[u8; N] route: inconsistent tie counts (a kernel before them failed)");
@@ -510,32 +505,22 @@ namespace rdst_internal {
 int sort_bytes_rows_host(void* host_rows, uint64_t len, uint32_t row_bytes, uint32_t key_offset, uint32_t key_bytes,
                          const rdst_hip_opts* opts) {
     HostJob job;
-    if (opts && opts->device >= 0) {
-        BYTES_TRY(hipGetDevice(&job.prev_dev));
-        BYTES_TRY(hipSetDevice(opts->device));
-    }
     uint32_t* err = nullptr;
-    int rc = device_error_word(&err);
-    if (rc) return rc;
+    int rc;
+    if ((rc = job.enter(opts)) || (rc = device_error_word(&err)) || (rc = job.open())) return rc;
     const uint64_t bytes = len * row_bytes;
     void *d_rows = nullptr, *d_out = nullptr, *d_scratch = nullptr;
-    BYTES_TRY(hipStreamCreate(&job.s));
-    BYTES_TRY(job.alloc(&d_rows, bytes));
-    BYTES_TRY(job.alloc(&d_out, bytes));
-    BYTES_TRY(job.alloc(&d_scratch, core_scratch_bytes(len)));
-    BYTES_TRY(hipMemcpyAsync(d_rows, host_rows, bytes, hipMemcpyHostToDevice, job.s));
+    RDST_HIP_TRY(job.alloc(&d_rows, bytes));
+    RDST_HIP_TRY(job.alloc(&d_out, bytes));
+    RDST_HIP_TRY(job.alloc(&d_scratch, core_scratch_bytes(len)));
+    if ((rc = job.upload(d_rows, host_rows, bytes))) return rc;
     const uint8_t* rows = static_cast<const uint8_t*>(d_rows);
     char* scratch = static_cast<char*>(d_scratch);
     rc = bytes_order(rows, len, row_bytes, key_offset, key_bytes, scratch, job.s, err);
     if (rc == RDST_OK)
         rc = bytes_gather(rows, static_cast<uint8_t*>(d_out), reinterpret_cast<const uint32_t*>(scratch + make_layout(len).idx), len,
                           row_bytes, job.s, err);
-    if (rc == RDST_OK) rc = rdst_hip_device_status(job.s);
-    if (rc != RDST_OK) return rc;
-    // the host buffer is written only now, after the device reported success
-    BYTES_TRY(hipMemcpyAsync(host_rows, d_out, bytes, hipMemcpyDeviceToHost, job.s));
-    BYTES_TRY(hipStreamSynchronize(job.s));
-    return RDST_OK;
+    return job.finish(rc, host_rows, d_out, bytes);
 }
 
 }  // namespace rdst_internal
@@ -571,7 +556,7 @@ int rdst_hip_sort_bytes_device(void* dev_rows, uint64_t len, uint32_t n_bytes, v
     if (rc) return rc;
     rc = bytes_gather(rows, staged, reinterpret_cast<const uint32_t*>(scratch + L.idx), len, n_bytes, s, err);
     if (rc) return rc;
-    BYTES_TRY(hipMemcpyAsync(rows, staged, len * n_bytes, hipMemcpyDeviceToDevice, s));
+    RDST_HIP_TRY(hipMemcpyAsync(rows, staged, len * n_bytes, hipMemcpyDeviceToDevice, s));
     return RDST_OK;
 }
 
@@ -796,7 +781,7 @@ int rdst_hip_sort_records_by_fields_device(void* dev_records, uint64_t len, uint
     if ((rc = rdst_internal::device_error_word(&err))) return rc;
     char* scratch = static_cast<char*>(dev_scratch);
     if ((rc = fields_sort_staged(static_cast<const uint8_t*>(dev_records), len, record_bytes, fields, n_fields, L, scratch, s, err))) return rc;
-    BYTES_TRY(hipMemcpyAsync(dev_records, scratch + F.staged, len * record_bytes, hipMemcpyDeviceToDevice, s));
+    RDST_HIP_TRY(hipMemcpyAsync(dev_records, scratch + F.staged, len * record_bytes, hipMemcpyDeviceToDevice, s));
     return RDST_OK;
 }
 
@@ -809,27 +794,17 @@ int rdst_hip_sort_records_by_fields(void* host_records, uint64_t len, uint32_t r
     if (host_records == nullptr) return set_error(RDST_ERR_ARG, "null record pointer");
     if (len >= (1ull << 32)) return set_error(RDST_ERR_UNSUPPORTED, "records with a described key are built for len < 2^32 (row indices are u32)");
     rdst_internal::HostJob job;
-    if (opts && opts->device >= 0) {
-        BYTES_TRY(hipGetDevice(&job.prev_dev));
-        BYTES_TRY(hipSetDevice(opts->device));
-    }
     uint32_t* err = nullptr;
-    if ((rc = rdst_internal::device_error_word(&err))) return rc;
+    if ((rc = job.enter(opts)) || (rc = rdst_internal::device_error_word(&err)) || (rc = job.open())) return rc;
     const uint64_t bytes = len * record_bytes;
     const FieldsLayout F = make_fields_layout(len, record_bytes, L);
     void *d_rows = nullptr, *d_scratch = nullptr;
-    BYTES_TRY(hipStreamCreate(&job.s));
-    BYTES_TRY(job.alloc(&d_rows, bytes));
-    BYTES_TRY(job.alloc(&d_scratch, F.total));
-    BYTES_TRY(hipMemcpyAsync(d_rows, host_records, bytes, hipMemcpyHostToDevice, job.s));
+    RDST_HIP_TRY(job.alloc(&d_rows, bytes));
+    RDST_HIP_TRY(job.alloc(&d_scratch, F.total));
+    if ((rc = job.upload(d_rows, host_records, bytes))) return rc;
     char* scratch = static_cast<char*>(d_scratch);
     rc = fields_sort_staged(static_cast<const uint8_t*>(d_rows), len, record_bytes, fields, n_fields, L, scratch, job.s, err);
-    if (rc == RDST_OK) rc = rdst_hip_device_status(job.s);
-    if (rc != RDST_OK) return rc;
-    // the host buffer is written only now, after the device reported success: straight from the staging area
-    BYTES_TRY(hipMemcpyAsync(host_records, scratch + F.staged, bytes, hipMemcpyDeviceToHost, job.s));
-    BYTES_TRY(hipStreamSynchronize(job.s));
-    return RDST_OK;
+    return job.finish(rc, host_records, scratch + F.staged, bytes);  // straight from the staging area
 }
 
 int rdst_hip_pack_fields_device(const void* dev_records, uint64_t len, uint32_t record_bytes, const rdst_key_field* fields, uint32_t n_fields,

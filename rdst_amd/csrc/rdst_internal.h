@@ -45,27 +45,85 @@ int with_bools(F&& f, bool b, B... rest) {
 template <typename F>
 int by_uint(uint32_t bytes, F&& f) { return bytes == 4 ? f(uint32_t{}) : f(uint64_t{}); }
 
-// What a blocking host entry point owns: its stream, its device buffers and the device it switched away from.  All of it is
-// given back when the entry point returns, on whatever path, after the work still queued on the stream has finished.
+// A failed HIP call inside any function that returns a status: recorded with the expression's text, RDST_ERR_HIP returned.
+#define RDST_HIP_TRY(expr)                                                                  \
+    do {                                                                                    \
+        hipError_t e__ = (expr);                                                            \
+        if (e__ != hipSuccess) return ::rdst_internal::set_error(RDST_ERR_HIP, #expr, e__); \
+    } while (0)
+
+// The frame of every blocking host-slice entry point: switch to the device the caller named (enter), take a stream and
+// device buffers (open + alloc: the job's own; or borrow: a device's cached ones), copy the slice up (upload), run the
+// work, and finish: status, then download, then wait.  finish alone writes the caller's memory, and only after the device
+// reported success.  On whatever path the entry returns, the work still queued on the stream has finished, what the job
+// owns is given back, and the device the caller had selected is selected again.
 struct HostJob {
     hipStream_t s = nullptr;
-    int prev_dev = -1;
-    void* bufs[8] = {};
-    int nbufs = 0;
+    int enter(const rdst_hip_opts* opts) {
+        if (opts && opts->device >= 0) {
+            RDST_HIP_TRY(hipGetDevice(&prev_dev));
+            RDST_HIP_TRY(hipSetDevice(opts->device));
+        }
+        return RDST_OK;
+    }
+    int open() {
+        RDST_HIP_TRY(hipStreamCreate(&s));
+        own_stream = true;
+        return RDST_OK;
+    }
     hipError_t alloc(void** p, size_t bytes) {
         if (nbufs == 8) return hipErrorOutOfMemory;
         const hipError_t e = hipMalloc(p, bytes);
         if (e == hipSuccess) bufs[nbufs++] = *p;
         return e;
     }
-    HostJob() = default;
-    HostJob(const HostJob&) = delete;
+    // A stream that outlives the job, the lock that guards it and its buffers (held until the job ends), and four events
+    // (or none) to record around the upload and around the download.
+    void borrow(hipStream_t stream, std::unique_lock<std::mutex>&& guard, hipEvent_t* events) {
+        s = stream;
+        lock = std::move(guard);
+        ev = events;
+    }
+    int upload(void* dev, const void* host, size_t bytes) {
+        if (ev) (void)hipEventRecord(ev[0], s);
+        RDST_HIP_TRY(hipMemcpyAsync(dev, host, bytes, hipMemcpyHostToDevice, s));
+        if (ev) (void)hipEventRecord(ev[1], s);
+        return RDST_OK;
+    }
+    // rdst_hip_device_status, for work that has to know before it goes on.  What it queues afterwards must not be able to
+    // raise the error word: finish does not ask a second time.
+    int status() {
+        if (!status_ok) {
+            if (int rc = rdst_hip_device_status(s)) return rc;
+            status_ok = true;
+        }
+        return RDST_OK;
+    }
+    // `rc`: what the work returned.  `host` is written if and only if the work and the device both reported success.
+    int finish(int rc, void* host, const void* dev, size_t bytes) {
+        if (rc == RDST_OK) rc = status();
+        if (rc != RDST_OK) return rc;
+        if (ev) (void)hipEventRecord(ev[2], s);
+        RDST_HIP_TRY(hipMemcpyAsync(host, dev, bytes, hipMemcpyDeviceToHost, s));
+        if (ev) (void)hipEventRecord(ev[3], s);
+        RDST_HIP_TRY(hipStreamSynchronize(s));
+        idle = true;
+        return RDST_OK;
+    }
     ~HostJob() {
-        if (s) (void)hipStreamSynchronize(s);
+        if (s && !idle) (void)hipStreamSynchronize(s);
         for (int i = 0; i < nbufs; ++i) (void)hipFree(bufs[i]);
-        if (s) (void)hipStreamDestroy(s);
+        if (own_stream) (void)hipStreamDestroy(s);
         if (prev_dev >= 0) (void)hipSetDevice(prev_dev);
     }
+
+private:
+    int prev_dev = -1;
+    void* bufs[8] = {};
+    int nbufs = 0;
+    bool own_stream = false, status_ok = false, idle = false;
+    hipEvent_t* ev = nullptr;
+    std::unique_lock<std::mutex> lock;  // released last, after the stream has been waited for
 };
 
 // The current device's sticky error word (kernels OR bits into it; rdst_hip_device_status reports and clears it).

@@ -4270,11 +4270,6 @@ int fail(int code, const char* what, hipError_t e = hipSuccess) {
     g_last_error = buf;
     return code;
 }
-#define HIP_TRY(expr)                                                   \
-    do {                                                                \
-        hipError_t e__ = (expr);                                        \
-        if (e__ != hipSuccess) return fail(RDST_ERR_HIP, #expr, e__);   \
-    } while (0)
 
 struct PassCfg { int nwaves, kpt4, kpt8, stages; };
 // Scatter-kernel shapes.  Larger tiles mean longer runs per digit and fewer look-backs;
@@ -4514,17 +4509,17 @@ int current_device_state(DeviceState** out, int* dev_out = nullptr) {
     DeviceState& D = g_dev[dev];
     if (!D.init) {
         hipDeviceProp_t prop;
-        HIP_TRY(hipGetDeviceProperties(&prop, dev));
+        RDST_HIP_TRY(hipGetDeviceProperties(&prop, dev));
         if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) {
             char b[160];
             snprintf(b, sizeof b, "device %d is %s; this library is built for gfx950 only", dev, prop.gcnArchName);
             return fail(RDST_ERR_NO_DEVICE, b);
         }
         D.cus = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-        HIP_TRY(hipHostMalloc((void**)&D.host_err, 128, hipHostMallocDefault));  // [0] the error word, [4] a route, [8..32) a span of the plan
-        HIP_TRY(hipMalloc((void**)&D.err_dev, 256));
-        HIP_TRY(hipMemset(D.err_dev, 0, 256));
-        HIP_TRY(hipEventCreateWithFlags(&D.last_done, hipEventDisableTiming));
+        RDST_HIP_TRY(hipHostMalloc((void**)&D.host_err, 128, hipHostMallocDefault));  // [0] the error word, [4] a route, [8..32) a span of the plan
+        RDST_HIP_TRY(hipMalloc((void**)&D.err_dev, 256));
+        RDST_HIP_TRY(hipMemset(D.err_dev, 0, 256));
+        RDST_HIP_TRY(hipEventCreateWithFlags(&D.last_done, hipEventDisableTiming));
         D.init = true;
     }
     *out = &D;
@@ -4535,8 +4530,8 @@ int current_device_state(DeviceState** out, int* dev_out = nullptr) {
 int ensure_workspace(DeviceState& D, size_t bytes) {
     if (D.ws_bytes >= bytes) return RDST_OK;
     if (D.ws) {
-        HIP_TRY(hipDeviceSynchronize());
-        HIP_TRY(hipFree(D.ws));
+        RDST_HIP_TRY(hipDeviceSynchronize());
+        RDST_HIP_TRY(hipFree(D.ws));
         D.ws = nullptr;
         D.ws_bytes = 0;
     }
@@ -4557,11 +4552,11 @@ int ensure_workspace(DeviceState& D, size_t bytes) {
 // The workspace is shared by every call on the device: work queued on another stream must
 // finish before this stream reuses it.
 int workspace_acquire(DeviceState& D, hipStream_t s) {
-    if (D.have_last && D.last_stream != s) HIP_TRY(hipStreamWaitEvent(s, D.last_done, 0));
+    if (D.have_last && D.last_stream != s) RDST_HIP_TRY(hipStreamWaitEvent(s, D.last_done, 0));
     return RDST_OK;
 }
 int workspace_release(DeviceState& D, hipStream_t s) {
-    HIP_TRY(hipEventRecord(D.last_done, s));
+    RDST_HIP_TRY(hipEventRecord(D.last_done, s));
     D.last_stream = s;
     D.have_last = true;
     return RDST_OK;
@@ -4572,12 +4567,12 @@ int prof_mark(DeviceState& D, hipStream_t s, uint32_t kind = 0) {
     if (!g_tuning.profiling || D.prof_runs.empty() || D.prof_used >= 8192) return RDST_OK;
     if (D.prof_used == D.prof_events.size()) {
         hipEvent_t e;
-        HIP_TRY(hipEventCreate(&e));
+        RDST_HIP_TRY(hipEventCreate(&e));
         D.prof_events.push_back(e);
         D.prof_kinds.push_back(0);
     }
     if (D.prof_used > D.prof_runs.back().begin) D.prof_kinds[D.prof_used - 1] = kind;
-    HIP_TRY(hipEventRecord(D.prof_events[D.prof_used++], s));
+    RDST_HIP_TRY(hipEventRecord(D.prof_events[D.prof_used++], s));
     D.prof_runs.back().count = D.prof_used - D.prof_runs.back().begin;
     return RDST_OK;
 }
@@ -4987,19 +4982,19 @@ int clear_workspace(Pipe<K, V>& p) {
     // kernel behind the route decision (1 B u32: 0.07 ms of clearing -> half)
     const size_t level_rows = (size_t)L.status_bytes * L.tiles * RADIX;  // one level, one copy
     if (p.rp.try_atomic) {
-        HIP_TRY(hipMemsetAsync(ws, 0, L.off_status, s));  // the status rows are the LSD route's: cleared behind the route decision, if it fell that way
+        RDST_HIP_TRY(hipMemsetAsync(ws, 0, L.off_status, s));  // the status rows are the LSD route's: cleared behind the route decision, if it fell that way
     } else if (p.rp.try_hybrid && LEVELS > 2) {
-        HIP_TRY(hipMemsetAsync(ws, 0, L.off_status, s));
-        HIP_TRY(hipMemsetAsync(ws + L.off_status + level_rows * (LEVELS - 2), 0, level_rows * 2, s));
-        HIP_TRY(hipMemsetAsync(ws + L.off_status_near + level_rows * (LEVELS - 2), 0, level_rows * 2, s));
+        RDST_HIP_TRY(hipMemsetAsync(ws, 0, L.off_status, s));
+        RDST_HIP_TRY(hipMemsetAsync(ws + L.off_status + level_rows * (LEVELS - 2), 0, level_rows * 2, s));
+        RDST_HIP_TRY(hipMemsetAsync(ws + L.off_status_near + level_rows * (LEVELS - 2), 0, level_rows * 2, s));
     } else if (p.level_lo == 0 && p.level_hi == (uint32_t)LEVELS) {
-        HIP_TRY(hipMemsetAsync(ws, 0, L.zero_bytes, s));  // header, count tables and both copies of the status rows are contiguous
+        RDST_HIP_TRY(hipMemsetAsync(ws, 0, L.zero_bytes, s));  // header, count tables and both copies of the status rows are contiguous
     } else {  // only the status rows of the passes that can run need clearing
         const size_t status_lo = L.off_status + level_rows * p.level_lo, status_hi = L.off_status + level_rows * p.level_hi;
-        HIP_TRY(hipMemsetAsync(ws, 0, L.off_status, s));
+        RDST_HIP_TRY(hipMemsetAsync(ws, 0, L.off_status, s));
         if (status_hi > status_lo) {
-            HIP_TRY(hipMemsetAsync(ws + status_lo, 0, status_hi - status_lo, s));
-            HIP_TRY(hipMemsetAsync(ws + status_lo + (L.off_status_near - L.off_status), 0, status_hi - status_lo, s));
+            RDST_HIP_TRY(hipMemsetAsync(ws + status_lo, 0, status_hi - status_lo, s));
+            RDST_HIP_TRY(hipMemsetAsync(ws + status_lo + (L.off_status_near - L.off_status), 0, status_hi - status_lo, s));
         }
     }
     return prof_mark(D, s, RDST_STAGE_CLEAR);
@@ -5290,8 +5285,8 @@ int run_split_sort(K* keys, K* tmp, uint64_t n, rdst_key_kind kind, hipStream_t 
     int rc = run_pipeline<K, LV>(keys, tmp, n, kind, LV - 1, LV, false, false, s, &L, &ws);
     if (rc) return rc;
     uint64_t counts[RADIX];
-    HIP_TRY(hipMemcpyAsync(counts, ws + L.off_hist + sizeof(uint64_t) * (size_t)(LV - 1) * RADIX, sizeof counts, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    RDST_HIP_TRY(hipMemcpyAsync(counts, ws + L.off_hist + sizeof(uint64_t) * (size_t)(LV - 1) * RADIX, sizeof counts, hipMemcpyDeviceToHost, s));
+    RDST_HIP_TRY(hipStreamSynchronize(s));
     uint64_t start[RADIX + 1];
     start[0] = 0;
     for (int d = 0; d < RADIX; ++d) start[d + 1] = start[d] + counts[d];
@@ -5320,7 +5315,7 @@ int run_split_sort(K* keys, K* tmp, uint64_t n, rdst_key_kind kind, hipStream_t 
     }
     for (const Part& p : parts) {
         if (p.cnt == 1) {
-            HIP_TRY(hipMemcpyAsync(keys + p.off, tmp + p.off, sizeof(K), hipMemcpyDeviceToDevice, s));
+            RDST_HIP_TRY(hipMemcpyAsync(keys + p.off, tmp + p.off, sizeof(K), hipMemcpyDeviceToDevice, s));
             continue;
         }
         // the part lies in tmp (the split pass put it there); the caller's array is its scratch and its destination
@@ -5391,7 +5386,7 @@ int regions_group_tiles(K* keys, uint64_t n, rdst_key_kind kind, uint32_t level,
                         hipStream_t s) {
     const uint64_t tiles = (n + tile_len - 1) / tile_len;
     DeviceBuf dcounts;
-    HIP_TRY(hipMalloc(&dcounts.p, sizeof(uint64_t) * RADIX * tiles));
+    RDST_HIP_TRY(hipMalloc(&dcounts.p, sizeof(uint64_t) * RADIX * tiles));
     for (uint64_t t = 0; t < tiles; ++t) {
         K* tile = keys + t * tile_len;
         const uint64_t tn = t + 1 < tiles ? tile_len : n - t * tile_len;
@@ -5399,16 +5394,14 @@ int regions_group_tiles(K* keys, uint64_t n, rdst_key_kind kind, uint32_t level,
         char* ws = nullptr;
         int rc = run_pipeline<K, LV>(tile, tmp, tn, kind, level, level + 1, false, false, s, &L, &ws);
         if (rc) return rc;
-        HIP_TRY(hipMemcpyAsync(static_cast<uint64_t*>(dcounts.p) + t * RADIX, ws + L.off_hist + sizeof(uint64_t) * (size_t)level * RADIX,
+        RDST_HIP_TRY(hipMemcpyAsync(static_cast<uint64_t*>(dcounts.p) + t * RADIX, ws + L.off_hist + sizeof(uint64_t) * (size_t)level * RADIX,
                                sizeof(uint64_t) * RADIX, hipMemcpyDeviceToDevice, s));
-        HIP_TRY(hipMemcpyAsync(tile, tmp, sizeof(K) * tn, hipMemcpyDeviceToDevice, s));
-        DeviceState* D;
-        if ((rc = current_device_state(&D))) return rc;
-        if ((rc = workspace_release(*D, s))) return rc;  // the count copy reads the workspace
+        RDST_HIP_TRY(hipMemcpyAsync(tile, tmp, sizeof(K) * tn, hipMemcpyDeviceToDevice, s));
+        if ((rc = rdst_internal::workspace_handback(s))) return rc;  // the count copy reads the workspace
     }
     counts_host.resize(RADIX * tiles);
-    HIP_TRY(hipMemcpyAsync(counts_host.data(), dcounts.p, sizeof(uint64_t) * RADIX * tiles, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    RDST_HIP_TRY(hipMemcpyAsync(counts_host.data(), dcounts.p, sizeof(uint64_t) * RADIX * tiles, hipMemcpyDeviceToHost, s));
+    RDST_HIP_TRY(hipStreamSynchronize(s));
     return RDST_OK;
 }
 
@@ -5438,8 +5431,8 @@ int regions_swap(K* keys, uint64_t n, uint64_t tile_len, const std::vector<uint6
         round_chunk[r + 1] = chunks.size();
     }
     DeviceBuf dchunks;
-    HIP_TRY(hipMalloc(&dchunks.p, sizeof(SwapChunk) * chunks.size()));
-    HIP_TRY(hipMemcpyAsync(dchunks.p, chunks.data(), sizeof(SwapChunk) * chunks.size(), hipMemcpyHostToDevice, s));
+    RDST_HIP_TRY(hipMalloc(&dchunks.p, sizeof(SwapChunk) * chunks.size()));
+    RDST_HIP_TRY(hipMemcpyAsync(dchunks.p, chunks.data(), sizeof(SwapChunk) * chunks.size(), hipMemcpyHostToDevice, s));
     for (uint32_t r = 0; r < nrounds; ++r) {
         const uint64_t c0 = round_chunk[r], c1 = round_chunk[r + 1];
         for (uint64_t c = c0; c < c1; c += (1u << 30)) {  // (a grid dimension holds 2^31 - 1 blocks)
@@ -5448,7 +5441,7 @@ int regions_swap(K* keys, uint64_t n, uint64_t tile_len, const std::vector<uint6
                 return rc;
         }
     }
-    HIP_TRY(hipStreamSynchronize(s));  // `chunks` and the device list go out of scope
+    RDST_HIP_TRY(hipStreamSynchronize(s));  // `chunks` and the device list go out of scope
     return RDST_OK;
 }
 
@@ -5504,16 +5497,48 @@ int partition_entry(void* dev_keys, uint64_t len, rdst_key_kind kind, uint32_t l
     *split_out = starts[1];
     return RDST_OK;
 }
-uint64_t usable_scratch(uint64_t tmp_len) { return tmp_len / 4096 * 4096; }  // tiles start on 16-byte boundaries for every key width
+
+// ---- what the entry points share: argument checks, the locked current device, the blocking tail ----
+// The second buffer of a device entry (its "tmp", or the "dst" of a pass): there, and aligned like the keys.
+int check_second_buffer(const void* p, uint32_t elem_bytes, bool is_dst) {
+    if (p == nullptr) return fail(RDST_ERR_ARG, is_dst ? "null dst pointer" : "null tmp pointer");
+    if (reinterpret_cast<uintptr_t>(p) % elem_bytes)
+        return fail(RDST_ERR_ALIGN, is_dst ? "dst pointer not aligned to the element size" : "tmp pointer not aligned to the element size");
+    return RDST_OK;
+}
+
+// The scratch of the Regions route: used in whole 4096s (tiles start on 16-byte boundaries for every key width).
+int check_regions_scratch(uint64_t* tmp_len) {
+    *tmp_len = *tmp_len / 4096 * 4096;
+    if (*tmp_len < 65536) return fail(RDST_ERR_ARG, "the scratch must hold at least 65536 elements");
+    return RDST_OK;
+}
+
+// The key field of a host slice of records; `natural`: an integer or float field, read as one aligned word.
+int check_record_field(const void* records, uint64_t len, uint32_t record_bytes, uint32_t key_offset, uint32_t key_bytes, bool natural) {
+    if (record_bytes == 0 || (uint64_t)key_offset + key_bytes > record_bytes) return fail(RDST_ERR_ARG, "key field outside the record");
+    if (natural && (key_offset % key_bytes || record_bytes % key_bytes)) return fail(RDST_ERR_ALIGN, "key field not naturally aligned inside the record");
+    if (len > 0 && records == nullptr) return fail(RDST_ERR_ARG, "null record pointer");
+    return RDST_OK;
+}
+
+// The library's mutex and the current device's state, for as long as the object lives.  `rc` is to be looked at first.
+struct LockedDevice {
+    std::lock_guard<std::mutex> lock{g_mutex};
+    DeviceState* D = nullptr;
+    int rc = current_device_state(&D);
+    DeviceState* operator->() const { return D; }
+    DeviceState& operator*() const { return *D; }
+};
 
 int read_device_error(DeviceState& D, hipStream_t s) {
     if (!D.err_dev) return RDST_OK;
-    HIP_TRY(hipMemcpyAsync(D.host_err, D.err_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    RDST_HIP_TRY(hipMemcpyAsync(D.host_err, D.err_dev, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    RDST_HIP_TRY(hipStreamSynchronize(s));
     if (*D.host_err != 0) {
         const uint32_t word = *D.host_err;
-        HIP_TRY(hipMemsetAsync(D.err_dev, 0, sizeof(uint32_t), s));  // reported once: the next check starts clean
-        HIP_TRY(hipStreamSynchronize(s));
+        RDST_HIP_TRY(hipMemsetAsync(D.err_dev, 0, sizeof(uint32_t), s));  // reported once: the next check starts clean
+        RDST_HIP_TRY(hipStreamSynchronize(s));
         char b[448];
         snprintf(b, sizeof b, "device error word = 0x%x (1 = look-back spin bound expired, 2 = scatter destination out of range, 4 = hybrid-route bucket larger than a tile, 8 = [u8; N] route: a row index or run out of range, 16 = segmented sort: offsets table decreasing, past len, or a segment beyond block_max without tmp)", word);
         return fail(RDST_ERR_DEVICE, b);
@@ -5521,15 +5546,21 @@ int read_device_error(DeviceState& D, hipStream_t s) {
     return RDST_OK;
 }
 
+// The blocking tail of an entry point: waits for `s`, then reports and clears the device's error word.  Callers hold g_mutex.
+int wait_and_report(hipStream_t s) {
+    DeviceState* D;
+    if (int rc = current_device_state(&D)) return rc;
+    RDST_HIP_TRY(hipStreamSynchronize(s));
+    return read_device_error(*D, s);
+}
+
 // the streaming yardsticks: MODE 0 copies, 1 only reads, 2 only writes
 template <int MODE>
 int stream_run(void* dev_dst, const void* dev_src, uint64_t bytes, void* stream) {
     if ((MODE != 1 && !dev_dst) || (MODE != 2 && !dev_src)) return fail(RDST_ERR_ARG, "null pointer");
     if ((reinterpret_cast<uintptr_t>(dev_dst) | reinterpret_cast<uintptr_t>(dev_src) | bytes) & 15u) return fail(RDST_ERR_ALIGN, "16-byte alignment");
-    std::lock_guard<std::mutex> lock(g_mutex);
-    DeviceState* D;
-    int rc = current_device_state(&D);
-    if (rc) return rc;
+    LockedDevice D;
+    if (D.rc) return D.rc;
     return launch("stream_kernel", stream_kernel<MODE>, dim3((uint32_t)D->cus * 8), dim3(256), 0, static_cast<hipStream_t>(stream),
                   static_cast<u32x4_t*>(dev_dst), static_cast<const u32x4_t*>(dev_src), bytes / 16, D->err_dev + 8);
 }
@@ -5552,6 +5583,54 @@ int launch_bytes_widen(bool expand, void* raw, void* keys, uint64_t len, uint32_
     return nb <= 4 ? launch_bytes_widen_t<uint32_t>(expand, r, keys, len, nb, s)
                    : (nb <= 8 ? launch_bytes_widen_t<uint64_t>(expand, r, keys, len, nb, s) : launch_bytes_widen_t<u128>(expand, r, keys, len, nb, s));
 }
+
+// Bytes [lo, hi) of the most recent pipeline's Plan, copied to the pinned words at `h`; blocking.  *have = false, and
+// nothing copied: no pipeline yet (or the one-workgroup sort).
+int read_plan_words(DeviceState& D, void* stream, size_t lo, size_t hi, uint32_t* h, bool* have) {
+    *have = D.ws && D.last_plan_valid;
+    if (!*have) return RDST_OK;
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    if (int rc = workspace_acquire(D, s)) return rc;  // the sort may have run on another stream
+    RDST_HIP_TRY(hipMemcpyAsync(h, static_cast<char*>(D.ws) + D.last_plan_off + lo, hi - lo, hipMemcpyDeviceToHost, s));
+    RDST_HIP_TRY(hipStreamSynchronize(s));
+    return RDST_OK;
+}
+
+// The run a profile reader was asked for (`run` < 0: counted from the most recent), after its output checks; *n_out = 0.
+int find_profiled_run(const DeviceState& D, int run, const void* out, uint32_t* n_out, DeviceState::ProfRun* r) {
+    if (!out || !n_out) return fail(RDST_ERR_ARG, "null output");
+    *n_out = 0;
+    if (run < 0) run += (int)D.prof_runs.size();
+    if (run < 0 || run >= (int)D.prof_runs.size()) return fail(RDST_ERR_ARG, "no such profiled run");
+    *r = D.prof_runs[run];
+    return RDST_OK;
+}
+
+#ifdef RDST_EXPERIMENTS
+// A device buffer kernels write records to while the __device__ pointer `symbol` names it (rdst_hip_exp_timeline / _stats).
+// host_out == nullptr: arm (allocate, clear, publish); else wait for the device and read back (`disarm`: un-publish first).
+struct ExpBuffer {
+    void* dev = nullptr;
+    size_t cap = 0;
+    template <typename T>
+    int arm_or_read(const T& symbol, void* host_out, size_t bytes, bool disarm) {  // hipMemcpyToSymbol(const T&, ...): the symbol itself, not its host value
+        if (host_out == nullptr) {
+            if (cap < bytes) {
+                if (dev) (void)hipFree(dev);
+                dev = nullptr, cap = 0;
+                if (hipMalloc(&dev, bytes) != hipSuccess) return -1;
+                cap = bytes;
+            }
+            if (hipMemset(dev, 0, bytes) != hipSuccess) return -1;
+            return hipMemcpyToSymbol(symbol, &dev, sizeof dev) == hipSuccess ? 0 : -1;
+        }
+        if (hipDeviceSynchronize() != hipSuccess || !dev) return -1;
+        void* null_dev = nullptr;
+        if (disarm) (void)hipMemcpyToSymbol(symbol, &null_dev, sizeof null_dev);
+        return hipMemcpy(host_out, dev, bytes, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+    }
+};
+#endif
 
 }  // namespace
 
@@ -5594,29 +5673,22 @@ int rdst_hip_set_hybrid(int enabled, uint64_t min_len) {
 }
 
 int rdst_hip_last_route(void* stream, uint32_t* route_out) {
-    std::lock_guard<std::mutex> lock(g_mutex);
-    DeviceState* D;
-    int rc = current_device_state(&D);
-    if (rc) return rc;
+    LockedDevice D;
+    if (D.rc) return D.rc;
     if (!route_out) return fail(RDST_ERR_ARG, "null output");
     *route_out = RDST_ROUTE_LSD;
-    if (!D->ws || !D->last_plan_valid) return RDST_OK;  // no pipeline yet (or the one-workgroup sort)
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if ((rc = workspace_acquire(*D, s))) return rc;  // the sort may have run on another stream
-    HIP_TRY(hipMemcpyAsync(D->host_err + 4, static_cast<char*>(D->ws) + D->last_plan_off + offsetof(Plan, route), sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    *route_out = D->host_err[4];
+    bool have = false;
+    if (int rc = read_plan_words(*D, stream, offsetof(Plan, route), offsetof(Plan, route) + sizeof(uint32_t), D->host_err + 4, &have)) return rc;
+    if (have) *route_out = D->host_err[4];
     return RDST_OK;
 }
 
 int rdst_hip_release_workspace(void) {
-    std::lock_guard<std::mutex> lock(g_mutex);
-    DeviceState* D;
-    int rc = current_device_state(&D);
-    if (rc) return rc;
+    LockedDevice D;
+    if (D.rc) return D.rc;
     if (!D->ws) return RDST_OK;
-    HIP_TRY(hipDeviceSynchronize());  // sorts still queued on any stream use it
-    HIP_TRY(hipFree(D->ws));
+    RDST_HIP_TRY(hipDeviceSynchronize());  // sorts still queued on any stream use it
+    RDST_HIP_TRY(hipFree(D->ws));
     D->ws = nullptr;
     D->ws_bytes = 0;
     D->last_plan_valid = false;
@@ -5629,30 +5701,24 @@ int rdst_hip_stream_read(const void* dev_src, uint64_t bytes, void* stream) { re
 int rdst_hip_stream_fill(void* dev_dst, uint64_t bytes, void* stream) { return stream_run<2>(dev_dst, nullptr, bytes, stream); }
 
 int rdst_hip_debug_raise_device_error(uint32_t bits, void* stream) {
-    std::lock_guard<std::mutex> lock(g_mutex);
-    DeviceState* D;
-    int rc = current_device_state(&D);
-    if (rc) return rc;
+    LockedDevice D;
+    if (D.rc) return D.rc;
     return launch("raise_error_kernel", raise_error_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), D->err_dev, bits);
 }
 
 int rdst_hip_debug_last_sample(void* stream, uint32_t out[6]) {
-    std::lock_guard<std::mutex> lock(g_mutex);
-    DeviceState* D;
-    int rc = current_device_state(&D);
-    if (rc) return rc;
+    LockedDevice D;
+    if (D.rc) return D.rc;
     if (!out) return fail(RDST_ERR_ARG, "null output");
     for (int i = 0; i < 6; ++i) out[i] = 0;
-    if (!D->ws || !D->last_plan_valid) return RDST_OK;  // no pipeline yet (or the one-workgroup sort)
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    if ((rc = workspace_acquire(*D, s))) return rc;  // the sort may have run on another stream
     // presample_kernel is the only writer of these words (route_kernel and msd_finish_kernel read them): one copy of the
     // plan's span from gross_skew to predict_lsd holds them as the sample left them
     constexpr size_t lo = offsetof(Plan, gross_skew), hi = offsetof(Plan, predict_lsd) + sizeof(uint32_t);
     static_assert(hi > lo && (hi - lo) / sizeof(uint32_t) <= 24, "the span fits the pinned words behind the route's");
     uint32_t* h = D->host_err + 8;
-    HIP_TRY(hipMemcpyAsync(h, static_cast<char*>(D->ws) + D->last_plan_off + lo, hi - lo, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    bool have = false;
+    if (int rc = read_plan_words(*D, stream, lo, hi, h, &have)) return rc;
+    if (!have) return RDST_OK;
     auto word = [&](size_t off) { return h[(off - lo) / sizeof(uint32_t)]; };
     out[0] = word(offsetof(Plan, win_shift));
     out[1] = word(offsetof(Plan, win_top));
@@ -5674,39 +5740,15 @@ int rdst_hip_exp_set_ablation(uint32_t mask) { g_ablate = mask; return 0; }
 int rdst_hip_exp_set_lds(uint32_t bytes) { g_exp_lds_total = bytes; return 0; }
 // per-tile look-back records of level 0: windows fetched, blocked re-polls, tiles consumed, shader clocks
 int rdst_hip_exp_timeline(uint32_t* host_out, uint64_t tiles) {
-    static uint32_t* dev = nullptr;
-    static uint64_t cap = 0;
-    if (host_out == nullptr) {
-        if (cap < tiles) {
-            if (dev) (void)hipFree(dev);
-            if (hipMalloc((void**)&dev, tiles * 48) != hipSuccess) return -1;
-            cap = tiles;
-        }
-        if (hipMemset(dev, 0, tiles * 48) != hipSuccess) return -1;
-        return hipMemcpyToSymbol(HIP_SYMBOL(g_exp_timeline), &dev, sizeof dev) == hipSuccess ? 0 : -1;
-    }
-    if (hipDeviceSynchronize() != hipSuccess || !dev) return -1;
-    uint32_t* null_dev = nullptr;
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(g_exp_timeline), &null_dev, sizeof null_dev);
-    return hipMemcpy(host_out, dev, tiles * 48, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+    static ExpBuffer b;
+    return b.arm_or_read(HIP_SYMBOL(g_exp_timeline), host_out, tiles * 48, true);
 }
 int rdst_hip_exp_timeline_select(uint32_t which) {  // 0 K3 level 0, 1 local_wide2_sort_kernel, 2 / 3 msd_scatter_kernel pass A / B
     return hipMemcpyToSymbol(HIP_SYMBOL(g_exp_timeline_kernel), &which, sizeof which) == hipSuccess ? 0 : -1;
 }
 int rdst_hip_exp_stats(uint32_t* host_out, uint64_t tiles) {
-    static uint32_t* dev = nullptr;
-    static uint64_t cap = 0;
-    if (host_out == nullptr) {  // arm: (re)allocate and clear
-        if (cap < tiles) {
-            if (dev) (void)hipFree(dev);
-            if (hipMalloc((void**)&dev, tiles * 16) != hipSuccess) return -1;
-            cap = tiles;
-        }
-        if (hipMemset(dev, 0, tiles * 16) != hipSuccess) return -1;
-        return hipMemcpyToSymbol(HIP_SYMBOL(g_exp_stats), &dev, sizeof dev) == hipSuccess ? 0 : -1;
-    }
-    if (hipDeviceSynchronize() != hipSuccess || !dev) return -1;
-    return hipMemcpy(host_out, dev, tiles * 16, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+    static ExpBuffer b;
+    return b.arm_or_read(HIP_SYMBOL(g_exp_stats), host_out, tiles * 16, false);
 }
 #endif
 
@@ -5721,41 +5763,29 @@ int rdst_hip_set_profiling(int enabled) {
 }
 
 int rdst_hip_profile_runs(void) {
-    std::lock_guard<std::mutex> lock(g_mutex);
-    DeviceState* D;
-    if (current_device_state(&D)) return 0;
-    return (int)D->prof_runs.size();
+    LockedDevice D;
+    return D.rc ? 0 : (int)D->prof_runs.size();
 }
 
 int rdst_hip_profile_run(int run, float* out_ms, uint32_t capacity, uint32_t* n_out) {
-    std::lock_guard<std::mutex> lock(g_mutex);
-    DeviceState* D;
-    int rc = current_device_state(&D);
-    if (rc) return rc;
-    if (!out_ms || !n_out) return fail(RDST_ERR_ARG, "null output");
-    *n_out = 0;
-    if (run < 0) run += (int)D->prof_runs.size();  // -1 = most recent
-    if (run < 0 || run >= (int)D->prof_runs.size()) return fail(RDST_ERR_ARG, "no such profiled run");
-    const auto r = D->prof_runs[run];
+    LockedDevice D;
+    if (D.rc) return D.rc;
+    DeviceState::ProfRun r;
+    if (int rc = find_profiled_run(*D, run, out_ms, n_out, &r)) return rc;
     if (r.count < 2) return RDST_OK;
-    HIP_TRY(hipEventSynchronize(D->prof_events[r.begin + r.count - 1]));
+    RDST_HIP_TRY(hipEventSynchronize(D->prof_events[r.begin + r.count - 1]));
     const uint32_t n = r.count - 1;
     for (uint32_t i = 0; i < n && i < capacity; ++i)
-        HIP_TRY(hipEventElapsedTime(&out_ms[i], D->prof_events[r.begin + i], D->prof_events[r.begin + i + 1]));
+        RDST_HIP_TRY(hipEventElapsedTime(&out_ms[i], D->prof_events[r.begin + i], D->prof_events[r.begin + i + 1]));
     *n_out = n < capacity ? n : capacity;
     return RDST_OK;
 }
 
 int rdst_hip_profile_run_stages(int run, uint32_t* stages_out, uint32_t capacity, uint32_t* n_out) {
-    std::lock_guard<std::mutex> lock(g_mutex);
-    DeviceState* D;
-    int rc = current_device_state(&D);
-    if (rc) return rc;
-    if (!stages_out || !n_out) return fail(RDST_ERR_ARG, "null output");
-    *n_out = 0;
-    if (run < 0) run += (int)D->prof_runs.size();
-    if (run < 0 || run >= (int)D->prof_runs.size()) return fail(RDST_ERR_ARG, "no such profiled run");
-    const auto r = D->prof_runs[run];
+    LockedDevice D;
+    if (D.rc) return D.rc;
+    DeviceState::ProfRun r;
+    if (int rc = find_profiled_run(*D, run, stages_out, n_out, &r)) return rc;
     if (r.count < 2) return RDST_OK;
     const uint32_t n = r.count - 1;
     for (uint32_t i = 0; i < n && i < capacity; ++i) stages_out[i] = D->prof_kinds[r.begin + i];
@@ -5780,17 +5810,40 @@ uint64_t rdst_hip_workspace_bytes(uint64_t len, uint32_t elem_bytes) {
     return whole;
 }
 
+}  // extern "C"
+
+// One whole slice, the library's mutex held: what rdst_hip_sort_device / rdst_hip_sort_pairs_device do after their checks,
+// and the segmented sort for every long segment (rdst_internal.h).
+namespace rdst_internal {
+int sort_slice_locked(void* keys, void* tmp, uint64_t n, uint32_t elem_bytes, rdst_key_kind kind, hipStream_t s) {
+    int rc = RDST_OK;
+    RDST_BY_WIDTH(elem_bytes, rc = (sort_whole<K, LV>(static_cast<K*>(keys), static_cast<K*>(tmp), n, kind, s)));
+    return rc;
+}
+
+int sort_pairs_slice_locked(void* keys, void* vals, void* tmp_keys, void* tmp_vals, uint64_t n, uint32_t key_bytes, rdst_key_kind kind,
+                            uint32_t val_bytes, hipStream_t s) {
+    return by_uint(key_bytes, [&](auto k) {
+        return by_uint(val_bytes, [&](auto v) {
+            using KT = decltype(k);
+            using VT = decltype(v);
+            return run_pipeline<KT, (int)sizeof(KT), VT>(static_cast<KT*>(keys), static_cast<KT*>(tmp_keys), n, kind, 0, sizeof(KT), true, true, s, nullptr,
+                                                         nullptr, static_cast<VT*>(vals), static_cast<VT*>(tmp_vals));
+        });
+    });
+}
+}  // namespace rdst_internal
+
+extern "C" {
+
 int rdst_hip_sort_device(void* dev_keys, void* dev_tmp, uint64_t len, uint32_t elem_bytes, rdst_key_kind kind,
                          uint32_t levels, void* stream) {
     int rc = check_common(dev_keys, len, elem_bytes, kind, levels);
     if (rc) return rc;
     if (len <= 1) return RDST_OK;  // radix_sort_builder.rs:151
-    if (dev_tmp == nullptr) return fail(RDST_ERR_ARG, "null tmp pointer");
-    if (reinterpret_cast<uintptr_t>(dev_tmp) % elem_bytes) return fail(RDST_ERR_ALIGN, "tmp pointer not aligned to the element size");
+    if ((rc = check_second_buffer(dev_tmp, elem_bytes, false))) return rc;
     std::lock_guard<std::mutex> lock(g_mutex);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    RDST_BY_WIDTH(elem_bytes, rc = (sort_whole<K, LV>(static_cast<K*>(dev_keys), static_cast<K*>(dev_tmp), len, kind, s)));
-    return rc;
+    return rdst_internal::sort_slice_locked(dev_keys, dev_tmp, len, elem_bytes, kind, static_cast<hipStream_t>(stream));
 }
 
 int rdst_hip_sort_pairs_device(void* dev_keys, void* dev_vals, void* dev_tmp_keys, void* dev_tmp_vals, uint64_t len,
@@ -5805,53 +5858,94 @@ int rdst_hip_sort_pairs_device(void* dev_keys, void* dev_vals, void* dev_tmp_key
     if ((reinterpret_cast<uintptr_t>(dev_vals) | reinterpret_cast<uintptr_t>(dev_tmp_vals)) % val_bytes)
         return fail(RDST_ERR_ALIGN, "value pointer not aligned to the value size");
     std::lock_guard<std::mutex> lock(g_mutex);
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    rc = by_uint(key_bytes, [&](auto k) {
-        return by_uint(val_bytes, [&](auto v) {
-            using KT = decltype(k);
-            using VT = decltype(v);
-            return run_pipeline<KT, (int)sizeof(KT), VT>(static_cast<KT*>(dev_keys), static_cast<KT*>(dev_tmp_keys), len, kind, 0, sizeof(KT), true, true, s, nullptr,
-                                                         nullptr, static_cast<VT*>(dev_vals), static_cast<VT*>(dev_tmp_vals));
-        });
-    });
-    return rc;
+    return rdst_internal::sort_pairs_slice_locked(dev_keys, dev_vals, dev_tmp_keys, dev_tmp_vals, len, key_bytes, kind, val_bytes, static_cast<hipStream_t>(stream));
 }
 
 int rdst_hip_device_status(void* stream) {
     std::lock_guard<std::mutex> lock(g_mutex);
-    DeviceState* D;
-    int rc = current_device_state(&D);
-    if (rc) return rc;
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipStreamSynchronize(s));
-    return read_device_error(*D, s);
+    return wait_and_report(static_cast<hipStream_t>(stream));
 }
 
 namespace {
-// [u8; N] host slice: H2D of the raw bytes, expand to W-byte integers, sort those, compact, D2H
+// [u8; N] host slice, N <= 16: the raw bytes up, sort_bytes_widened over them, the raw bytes down
 int sort_byte_keys_host(void* host_data, uint64_t len, uint32_t nb, const rdst_hip_opts* opts) {
     rdst_internal::HostJob job;
-    if (opts && opts->device >= 0) {
-        HIP_TRY(hipGetDevice(&job.prev_dev));
-        HIP_TRY(hipSetDevice(opts->device));
+    int rc;
+    if ((rc = job.enter(opts)) || (rc = job.open())) return rc;
+    const size_t bytes = (size_t)len * nb;
+    void *d_raw = nullptr, *d_scratch = nullptr;
+    RDST_HIP_TRY(job.alloc(&d_raw, bytes));
+    RDST_HIP_TRY(job.alloc(&d_scratch, rdst_internal::widened_scratch_bytes(len, nb)));
+    if ((rc = job.upload(d_raw, host_data, bytes))) return rc;
+    return job.finish(rdst_internal::sort_bytes_widened(d_raw, len, nb, d_scratch, job.s), host_data, d_raw, bytes);
+}
+
+// rdst_hip_sort keeps a stream, a device buffer (keys + tmp) and four events per device: hipMalloc / hipFree pairs and a
+// stream per call were most of the 0.55 ms that entry point cost on small slices.  (A stream-ordered pool allocation per
+// call was tried first: with the system HIP runtime a sort whose buffer the pool had just recycled read stale keys —
+// test_cpp_mirror — so the buffer is plain hipMalloc memory.)  Lends them to `job`, with D.host_mutex held until the job
+// ends: one host-slice sort per device at a time.  *buf: at least `bytes` of device memory (0: the buffer as it is).
+int lend_host_cache(DeviceState& D, size_t bytes, rdst_internal::HostJob& job, void** buf) {
+    std::unique_lock<std::mutex> host_lock(D.host_mutex);
+    hipError_t e;
+    if (!D.host_stream && (e = hipStreamCreateWithFlags(&D.host_stream, hipStreamNonBlocking)) != hipSuccess)
+        return fail(RDST_ERR_HIP, "hipStreamCreate", e);
+    if (D.host_buf_bytes < bytes) {
+        if (D.host_buf) { (void)hipStreamSynchronize(D.host_stream); (void)hipFree(D.host_buf); D.host_buf = nullptr; D.host_buf_bytes = 0; }
+        const size_t want = bytes < (size_t)(64u << 20) ? bytes + bytes / 2 : bytes;  // head room for small slices only
+        if ((e = hipMalloc(&D.host_buf, want)) != hipSuccess) return fail(RDST_ERR_HIP, "hipMalloc(keys + tmp)", e);
+        D.host_buf_bytes = want;
     }
-    const uint32_t w = widened_bytes(nb);
-    void *d_raw = nullptr, *d_keys = nullptr, *d_tmp = nullptr;
-    HIP_TRY(hipStreamCreate(&job.s));
-    HIP_TRY(job.alloc(&d_raw, (size_t)len * nb));
-    HIP_TRY(job.alloc(&d_keys, (size_t)len * w));
-    HIP_TRY(job.alloc(&d_tmp, (size_t)len * w));
-    HIP_TRY(hipMemcpyAsync(d_raw, host_data, (size_t)len * nb, hipMemcpyHostToDevice, job.s));
-    int rc = launch_bytes_widen(true, d_raw, d_keys, len, nb, job.s);
-    if (rc == RDST_OK) rc = rdst_hip_sort_device(d_keys, d_tmp, len, w, RDST_KEY_UNSIGNED, w, job.s);
-    if (rc == RDST_OK) rc = rdst_hip_device_status(job.s);
-    if (rc == RDST_OK) rc = launch_bytes_widen(false, d_raw, d_keys, len, nb, job.s);
-    if (rc != RDST_OK) return rc;
-    // the host buffer is written only now, after the device reported success
-    HIP_TRY(hipMemcpyAsync(host_data, d_raw, (size_t)len * nb, hipMemcpyDeviceToHost, job.s));
-    HIP_TRY(hipStreamSynchronize(job.s));
+    D.host_timed = false;
+    for (auto& ev : D.host_ev)
+        if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return fail(RDST_ERR_HIP, "hipEventCreate", e);
+    *buf = D.host_buf;
+    job.borrow(D.host_stream, std::move(host_lock), D.host_ev);
     return RDST_OK;
 }
+
+// RDST_HOST_ALLOC=pool* and RDST_HOST_DEBUG, tools build only: the allocation scheme of commit 74cafa2 (one stream-ordered
+// pool allocation per call), which produced the round-1 abort examined in DESIGN.md §5, kept for whoever looks further.
+// In the product build every member is empty.
+#ifdef RDST_EXPERIMENTS
+struct HostSortKnobs {
+    static const char* mode() { static const char* m = getenv("RDST_HOST_ALLOC"); return m ? m : ""; }  // pool; pool_sync: + a stream sync between H2D and the sort; pool_nofree: blocks are never returned
+    static bool debug() { static const bool d = getenv("RDST_HOST_DEBUG") != nullptr; return d; }      // print the buffers of every call
+    void* pool_buf = nullptr;
+    hipStream_t s = nullptr;
+    bool pooled() const { return strncmp(mode(), "pool", 4) == 0; }  // the cached buffer is then neither grown nor used
+    int replace_buffer(void** buf, size_t bytes, hipStream_t stream) {
+        s = stream;
+        if (!pooled()) return RDST_OK;
+        const hipError_t e = hipMallocAsync(&pool_buf, bytes, s);
+        if (e != hipSuccess) return fail(RDST_ERR_HIP, "hipMallocAsync(keys + tmp)", e);
+        *buf = pool_buf;
+        return RDST_OK;
+    }
+    void uploaded(const DeviceState& D, uint64_t len, uint32_t elem_bytes, void* d_keys, void* d_tmp) {
+        if (strcmp(mode(), "pool_sync") == 0) (void)hipStreamSynchronize(s);
+        if (!debug()) return;
+        const size_t bytes = (size_t)len * elem_bytes;
+        fprintf(stderr, "[host] len=%llu elem=%u keys=[%p,%p) tmp=[%p,%p) ws=[%p,%p)\n", (unsigned long long)len, elem_bytes, d_keys,
+                (void*)(static_cast<char*>(d_keys) + bytes), d_tmp, (void*)(static_cast<char*>(d_tmp) + bytes), D.ws,
+                (void*)(static_cast<char*>(D.ws) + D.ws_bytes));
+        fflush(stderr);
+    }
+    void enqueued(const DeviceState& D, int rc) {
+        if (!debug()) return;
+        fprintf(stderr, "[host]   after enqueue: ws=[%p,%p) rc=%d\n", D.ws, (void*)(static_cast<char*>(D.ws) + D.ws_bytes), rc);
+        fflush(stderr);
+    }
+    ~HostSortKnobs() { if (pool_buf && strcmp(mode(), "pool_nofree") != 0) (void)hipFreeAsync(pool_buf, s); }
+};
+#else
+struct HostSortKnobs {
+    static constexpr bool pooled() { return false; }
+    int replace_buffer(void**, size_t, hipStream_t) { return RDST_OK; }
+    void uploaded(const DeviceState&, uint64_t, uint32_t, void*, void*) {}
+    void enqueued(const DeviceState&, int) {}
+};
+#endif
 }  // namespace
 
 int rdst_hip_sort(void* host_data, uint64_t len, uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels,
@@ -5869,102 +5963,51 @@ int rdst_hip_sort(void* host_data, uint64_t len, uint32_t elem_bytes, rdst_key_k
     int rc = check_common(host_data, len, elem_bytes, kind, levels);
     if (rc) return rc;
     if (len <= 1) return RDST_OK;
-    int prev_dev = -1;
-    if (opts && opts->device >= 0) {
-        HIP_TRY(hipGetDevice(&prev_dev));
-        HIP_TRY(hipSetDevice(opts->device));
-    }
+    rdst_internal::HostJob job;  // (declared first: it waits for the stream and switches back after everything below has let go)
+    if ((rc = job.enter(opts))) return rc;
     const size_t bytes = (size_t)len * elem_bytes;
     const bool low_memory = opts && opts->low_memory != 0;
     // low-memory route: the scratch is len / 64 elements (at least 65 536) instead of a second array
     const uint64_t scratch_len = low_memory ? (len / 64 > 65536 ? len / 64 : 65536) : len;
     const size_t half = align_up(bytes, 256);
     const size_t second = low_memory ? align_up((size_t)scratch_len * elem_bytes, 256) : half;
-    // Stream and device buffer (keys + tmp) are kept per device: hipMalloc / hipFree pairs and a stream
-    // per call were most of the 0.55 ms this entry point cost on small slices.  (A stream-ordered pool
-    // allocation per call was tried first: with the system HIP runtime a sort whose buffer the pool
-    // had just recycled read stale keys — test_cpp_mirror — so the buffer is plain hipMalloc memory.)
     DeviceState* D = nullptr;
     {
-        std::lock_guard<std::mutex> lock(g_mutex);
-        rc = current_device_state(&D);
+        LockedDevice cur;  // the library's mutex for the lookup only: the device's host_mutex guards the rest
+        if (cur.rc) return cur.rc;
+        D = cur.D;
     }
-    if (rc != RDST_OK) { if (prev_dev >= 0) (void)hipSetDevice(prev_dev); return rc; }
-    std::lock_guard<std::mutex> host_lock(D->host_mutex);
-    auto done = [&](int code) { if (prev_dev >= 0) (void)hipSetDevice(prev_dev); return code; };
-    hipError_t e;
-    if (!D->host_stream && (e = hipStreamCreateWithFlags(&D->host_stream, hipStreamNonBlocking)) != hipSuccess)
-        return done(fail(RDST_ERR_HIP, "hipStreamCreate", e));
-    hipStream_t s = D->host_stream;
-    // (The allocation scheme of commit 74cafa2 — one stream-ordered pool allocation per call — produced the round-1 abort
-    // examined in DESIGN.md §5; it exists only in the tools build, behind RDST_HOST_ALLOC=pool*, never in the product.)
-#ifdef RDST_EXPERIMENTS
-    static const char* alloc_mode = getenv("RDST_HOST_ALLOC");
-    static const bool use_pool = alloc_mode && strncmp(alloc_mode, "pool", 4) == 0;
-    static const bool pool_sync = alloc_mode && strcmp(alloc_mode, "pool_sync") == 0;    // + stream sync between H2D and the sort
-    static const bool host_debug = getenv("RDST_HOST_DEBUG") != nullptr;                // print the buffers of every call
-    static const bool pool_nofree = alloc_mode && strcmp(alloc_mode, "pool_nofree") == 0;  // blocks are never returned: no recycling
-#else
-    constexpr bool use_pool = false, pool_sync = false, host_debug = false, pool_nofree = false;
-#endif
-    void* pool_buf = nullptr;
-    if (use_pool) {
-        if ((e = hipMallocAsync(&pool_buf, half + second, s)) != hipSuccess) return done(fail(RDST_ERR_HIP, "hipMallocAsync(keys + tmp)", e));
-    } else if (D->host_buf_bytes < half + second) {
-        if (D->host_buf) { (void)hipStreamSynchronize(s); (void)hipFree(D->host_buf); D->host_buf = nullptr; D->host_buf_bytes = 0; }
-        const size_t want = half + second < (size_t)(64u << 20) ? (half + second) + (half + second) / 2 : half + second;  // head room for small slices only
-        if ((e = hipMalloc(&D->host_buf, want)) != hipSuccess) return done(fail(RDST_ERR_HIP, "hipMalloc(keys + tmp)", e));
-        D->host_buf_bytes = want;
-    }
-    void* d_keys = use_pool ? pool_buf : D->host_buf;
+    HostSortKnobs knobs;
+    void* d_keys = nullptr;
+    if ((rc = lend_host_cache(*D, knobs.pooled() ? 0 : half + second, job, &d_keys))) return rc;
+    if ((rc = knobs.replace_buffer(&d_keys, half + second, job.s))) return rc;
     void* d_tmp = static_cast<char*>(d_keys) + half;
-    struct PoolGuard { void* p; hipStream_t s; ~PoolGuard() { if (p) (void)hipFreeAsync(p, s); } } pool_guard{pool_nofree ? nullptr : pool_buf, s};
-    D->host_timed = false;
-    for (auto& ev : D->host_ev)
-        if (!ev && (e = hipEventCreate(&ev)) != hipSuccess) return done(fail(RDST_ERR_HIP, "hipEventCreate", e));
-    (void)hipEventRecord(D->host_ev[0], s);
-    if ((e = hipMemcpyAsync(d_keys, host_data, bytes, hipMemcpyHostToDevice, s)) != hipSuccess) { (void)hipStreamSynchronize(s); return done(fail(RDST_ERR_HIP, "H2D", e)); }
-    (void)hipEventRecord(D->host_ev[1], s);
-    if (pool_sync) (void)hipStreamSynchronize(s);
-    if (host_debug) {
-        fprintf(stderr, "[host] len=%llu elem=%u keys=[%p,%p) tmp=[%p,%p) ws=[%p,%p)\n", (unsigned long long)len, elem_bytes, d_keys,
-                (void*)(static_cast<char*>(d_keys) + bytes), d_tmp, (void*)(static_cast<char*>(d_tmp) + bytes), D->ws,
-                (void*)(static_cast<char*>(D->ws) + D->ws_bytes));
-        fflush(stderr);
-    }
-    if (low_memory) rc = rdst_hip_sort_device_lowmem(d_keys, len, elem_bytes, kind, levels, d_tmp, scratch_len, s);
-    else rc = rdst_hip_sort_device(d_keys, d_tmp, len, elem_bytes, kind, levels, s);
-    if (host_debug) {
-        fprintf(stderr, "[host]   after enqueue: ws=[%p,%p) rc=%d\n", D->ws, (void*)(static_cast<char*>(D->ws) + D->ws_bytes), rc);
-        fflush(stderr);
-    }
-    if (rc == RDST_OK) rc = rdst_hip_device_status(s);
-    if (rc != RDST_OK) { (void)hipStreamSynchronize(s); return done(rc); }
-    // the host buffer is written only now, after the device reported success
-    (void)hipEventRecord(D->host_ev[2], s);
-    if ((e = hipMemcpyAsync(host_data, d_keys, bytes, hipMemcpyDeviceToHost, s)) != hipSuccess) { (void)hipStreamSynchronize(s); return done(fail(RDST_ERR_HIP, "D2H", e)); }
-    (void)hipEventRecord(D->host_ev[3], s);
-    if ((e = hipStreamSynchronize(s)) != hipSuccess) return done(fail(RDST_ERR_HIP, "sync", e));
-    D->host_timed = true;
+    if ((rc = job.upload(d_keys, host_data, bytes))) return rc;
+    knobs.uploaded(*D, len, elem_bytes, d_keys, d_tmp);
+    if (low_memory) rc = rdst_hip_sort_device_lowmem(d_keys, len, elem_bytes, kind, levels, d_tmp, scratch_len, job.s);
+    else rc = rdst_hip_sort_device(d_keys, d_tmp, len, elem_bytes, kind, levels, job.s);
+    knobs.enqueued(*D, rc);
+    if ((rc = job.finish(rc, host_data, d_keys, bytes))) return rc;
+    D->host_timed = true;  // (the job still holds host_mutex)
     if (D->host_buf_bytes > ((size_t)1 << 30)) {  // do not sit on gigabytes between calls
         (void)hipFree(D->host_buf);
         D->host_buf = nullptr;
         D->host_buf_bytes = 0;
     }
-    return done(RDST_OK);
+    return RDST_OK;
 }
 
 int rdst_hip_host_timing(float* h2d_ms, float* sort_ms, float* d2h_ms) {
     DeviceState* D = nullptr;
     {
-        std::lock_guard<std::mutex> lock(g_mutex);
-        int rc = current_device_state(&D);
-        if (rc) return rc;
+        LockedDevice cur;  // the library's mutex for the lookup only: the device's host_mutex guards the rest
+        if (cur.rc) return cur.rc;
+        D = cur.D;
     }
     std::lock_guard<std::mutex> host_lock(D->host_mutex);
     if (!D->host_timed) return fail(RDST_ERR_ARG, "no host-slice sort has completed on this device yet");
     float t[3] = {0, 0, 0};
-    for (int i = 0; i < 3; ++i) HIP_TRY(hipEventElapsedTime(&t[i], D->host_ev[i], D->host_ev[i + 1]));
+    for (int i = 0; i < 3; ++i) RDST_HIP_TRY(hipEventElapsedTime(&t[i], D->host_ev[i], D->host_ev[i + 1]));
     if (h2d_ms) *h2d_ms = t[0];
     if (sort_ms) *sort_ms = t[1];
     if (d2h_ms) *d2h_ms = t[2];
@@ -5975,46 +6018,40 @@ int rdst_hip_sort_records(void* host_records, uint64_t len, uint32_t record_byte
                           rdst_key_kind kind, const rdst_hip_opts* opts) {
     if (kind == RDST_KEY_BYTES_BE) {  // a [u8; N] field: any offset, any row size (rdst_bytes.hip)
         if (key_bytes == 0 || key_bytes > RDST_BYTES_MAX_N) return fail(RDST_ERR_UNSUPPORTED, "[u8; N] key fields are built for N in 1..RDST_BYTES_MAX_N");
-        if (record_bytes == 0 || (uint64_t)key_offset + key_bytes > record_bytes) return fail(RDST_ERR_ARG, "key field outside the record");
-        if (len > 0 && host_records == nullptr) return fail(RDST_ERR_ARG, "null record pointer");
+        if (int rc = check_record_field(host_records, len, record_bytes, key_offset, key_bytes, false)) return rc;
         if (len >= (1ull << 32)) return fail(RDST_ERR_UNSUPPORTED, "records with a [u8; N] key are built for len < 2^32");
         if (len <= 1) return RDST_OK;
         return rdst_internal::sort_bytes_rows_host(host_records, len, record_bytes, key_offset, key_bytes, opts);
     }
     if (key_bytes != 4 && key_bytes != 8) return fail(RDST_ERR_UNSUPPORTED, "record sorts take a 4- or 8-byte key field");
     if (kind == RDST_KEY_FLOAT || kind == RDST_KEY_SIGNED || kind == RDST_KEY_UNSIGNED) {} else return fail(RDST_ERR_ARG, "unknown key kind");
-    if (record_bytes == 0 || (uint64_t)key_offset + key_bytes > record_bytes) return fail(RDST_ERR_ARG, "key field outside the record");
-    if (key_offset % key_bytes || record_bytes % key_bytes) return fail(RDST_ERR_ALIGN, "key field not naturally aligned inside the record");
-    if (len > 0 && host_records == nullptr) return fail(RDST_ERR_ARG, "null record pointer");
+    int rc = check_record_field(host_records, len, record_bytes, key_offset, key_bytes, true);
+    if (rc) return rc;
     if (len >= (1ull << 36)) return fail(RDST_ERR_ARG, "len too large");
     if (len <= 1) return RDST_OK;
     rdst_internal::HostJob job;
-    if (opts && opts->device >= 0) {
-        HIP_TRY(hipGetDevice(&job.prev_dev));
-        HIP_TRY(hipSetDevice(opts->device));
-    }
+    if ((rc = job.enter(opts)) || (rc = job.open())) return rc;
     const size_t bytes = (size_t)len * record_bytes;
     const uint32_t idx_bytes = len < (1ull << 32) ? 4 : 8;
     void *d_rec = nullptr, *d_out = nullptr, *d_keys = nullptr, *d_tk = nullptr, *d_idx = nullptr, *d_ti = nullptr;
-    HIP_TRY(hipStreamCreate(&job.s));
     hipStream_t s = job.s;
-    HIP_TRY(job.alloc(&d_rec, bytes));
-    HIP_TRY(job.alloc(&d_out, bytes));
-    HIP_TRY(job.alloc(&d_keys, (size_t)len * key_bytes));
-    HIP_TRY(job.alloc(&d_tk, (size_t)len * key_bytes));
-    HIP_TRY(job.alloc(&d_idx, (size_t)len * idx_bytes));
-    HIP_TRY(job.alloc(&d_ti, (size_t)len * idx_bytes));
-    HIP_TRY(hipMemcpyAsync(d_rec, host_records, bytes, hipMemcpyHostToDevice, s));
+    RDST_HIP_TRY(job.alloc(&d_rec, bytes));
+    RDST_HIP_TRY(job.alloc(&d_out, bytes));
+    RDST_HIP_TRY(job.alloc(&d_keys, (size_t)len * key_bytes));
+    RDST_HIP_TRY(job.alloc(&d_tk, (size_t)len * key_bytes));
+    RDST_HIP_TRY(job.alloc(&d_idx, (size_t)len * idx_bytes));
+    RDST_HIP_TRY(job.alloc(&d_ti, (size_t)len * idx_bytes));
+    if ((rc = job.upload(d_rec, host_records, bytes))) return rc;
     uint64_t blocks = (len + 255) / 256;
     if (blocks > 256 * 16) blocks = 256 * 16;
-    int rc = by_uint(key_bytes, [&](auto k) {
+    rc = by_uint(key_bytes, [&](auto k) {
         return by_uint(idx_bytes, [&](auto i) {
             return launch("extract_key_kernel", extract_key_kernel<decltype(k), decltype(i)>, dim3((uint32_t)blocks), dim3(256), 0, s,
                           static_cast<const unsigned char*>(d_rec), len, record_bytes, key_offset, static_cast<decltype(k)*>(d_keys), static_cast<decltype(i)*>(d_idx));
         });
     });
     if (rc == RDST_OK) rc = rdst_hip_sort_pairs_device(d_keys, d_idx, d_tk, d_ti, len, key_bytes, kind, key_bytes, idx_bytes, s);
-    if (rc == RDST_OK) rc = rdst_hip_device_status(s);
+    if (rc == RDST_OK) rc = job.status();  // the gather follows the indices unchecked: they have to be the sort's
     if (rc != RDST_OK) return rc;
     // rows in the order of the sorted indices, in the widest units the row size allows
     const uint32_t unit = record_bytes % 16 == 0 ? 16 : (record_bytes % 8 == 0 ? 8 : 4);
@@ -6029,11 +6066,7 @@ int rdst_hip_sort_records(void* host_records, uint64_t len, uint32_t record_byte
                       static_cast<UT*>(d_out), static_cast<const IT*>(d_idx), len, record_bytes / unit);
     };
     rc = by_uint(idx_bytes, [&](auto i) { return unit == 16 ? gather(U16{}, i) : (unit == 8 ? gather(uint64_t{}, i) : gather(uint32_t{}, i)); });
-    if (rc != RDST_OK) return rc;
-    // the host buffer is written only now, after the device reported success
-    HIP_TRY(hipMemcpyAsync(host_records, d_out, bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
-    return RDST_OK;
+    return job.finish(rc, host_records, d_out, bytes);
 }
 
 int rdst_hip_all_level_counts(const void* dev_keys, uint64_t len, uint32_t elem_bytes, rdst_key_kind kind,
@@ -6050,8 +6083,8 @@ int rdst_hip_all_level_counts(const void* dev_keys, uint64_t len, uint32_t elem_
     // levels [0,0): histogram + scan only, no pass runs
     RDST_BY_WIDTH(elem_bytes, rc = (run_pipeline<K, LV>(const_cast<K*>(static_cast<const K*>(dev_keys)), nullptr, len, kind, 0, 0, false, false, s, &L, &ws)));
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(counts_out, ws + L.off_hist, sizeof(uint64_t) * levels * RADIX, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    RDST_HIP_TRY(hipMemcpyAsync(counts_out, ws + L.off_hist, sizeof(uint64_t) * levels * RADIX, hipMemcpyDeviceToHost, s));
+    RDST_HIP_TRY(hipStreamSynchronize(s));
     return RDST_OK;
 }
 
@@ -6062,8 +6095,7 @@ int rdst_hip_scatter_level(const void* dev_src, void* dev_dst, uint64_t len, uin
     if (level >= elem_bytes) return fail(RDST_ERR_ARG, "level out of range");
     if (counts_out) memset(counts_out, 0, sizeof(uint64_t) * RADIX);
     if (len == 0) return RDST_OK;
-    if (dev_dst == nullptr) return fail(RDST_ERR_ARG, "null dst pointer");
-    if (reinterpret_cast<uintptr_t>(dev_dst) % elem_bytes) return fail(RDST_ERR_ALIGN, "dst pointer not aligned to the element size");
+    if ((rc = check_second_buffer(dev_dst, elem_bytes, true))) return rc;
     std::lock_guard<std::mutex> lock(g_mutex);
     hipStream_t s = static_cast<hipStream_t>(stream);
     Layout L;
@@ -6072,12 +6104,8 @@ int rdst_hip_scatter_level(const void* dev_src, void* dev_dst, uint64_t len, uin
     RDST_BY_WIDTH(elem_bytes, rc = (run_pipeline<K, LV>(const_cast<K*>(static_cast<const K*>(dev_src)), static_cast<K*>(dev_dst), len, kind, level, level + 1, false, false, s, &L, &ws)));
     if (rc) return rc;
     if (counts_out)
-        HIP_TRY(hipMemcpyAsync(counts_out, ws + L.off_hist + sizeof(uint64_t) * (size_t)level * RADIX, sizeof(uint64_t) * RADIX, hipMemcpyDeviceToHost, s));
-    DeviceState* D;
-    rc = current_device_state(&D);
-    if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(s));
-    return read_device_error(*D, s);
+        RDST_HIP_TRY(hipMemcpyAsync(counts_out, ws + L.off_hist + sizeof(uint64_t) * (size_t)level * RADIX, sizeof(uint64_t) * RADIX, hipMemcpyDeviceToHost, s));
+    return wait_and_report(s);
 }
 
 int rdst_hip_sort_device_lowmem(void* dev_keys, uint64_t len, uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels, void* dev_tmp,
@@ -6085,18 +6113,11 @@ int rdst_hip_sort_device_lowmem(void* dev_keys, uint64_t len, uint32_t elem_byte
     int rc = check_common(dev_keys, len, elem_bytes, kind, levels);
     if (rc) return rc;
     if (len <= 1) return RDST_OK;
-    if (dev_tmp == nullptr) return fail(RDST_ERR_ARG, "null tmp pointer");
-    if (reinterpret_cast<uintptr_t>(dev_tmp) % elem_bytes) return fail(RDST_ERR_ALIGN, "tmp pointer not aligned to the element size");
-    tmp_len = usable_scratch(tmp_len);
-    if (tmp_len < 65536) return fail(RDST_ERR_ARG, "the scratch must hold at least 65536 elements");
+    if ((rc = check_second_buffer(dev_tmp, elem_bytes, false)) || (rc = check_regions_scratch(&tmp_len))) return rc;
     std::lock_guard<std::mutex> lock(g_mutex);
     hipStream_t s = static_cast<hipStream_t>(stream);
     RDST_BY_WIDTH(elem_bytes, rc = (lowmem_entry<K, LV>(dev_keys, len, kind, dev_tmp, tmp_len, s)));
-    if (rc) return rc;
-    DeviceState* D;
-    if ((rc = current_device_state(&D))) return rc;
-    HIP_TRY(hipStreamSynchronize(s));
-    return read_device_error(*D, s);
+    return rc ? rc : wait_and_report(s);
 }
 
 int rdst_hip_partition_device(void* dev_keys, uint64_t len, uint32_t elem_bytes, rdst_key_kind kind, uint32_t level, uint32_t digit,
@@ -6107,18 +6128,11 @@ int rdst_hip_partition_device(void* dev_keys, uint64_t len, uint32_t elem_bytes,
     if (!split_out) return fail(RDST_ERR_ARG, "null split_out");
     *split_out = 0;
     if (len == 0) return RDST_OK;
-    if (dev_tmp == nullptr) return fail(RDST_ERR_ARG, "null tmp pointer");
-    if (reinterpret_cast<uintptr_t>(dev_tmp) % elem_bytes) return fail(RDST_ERR_ALIGN, "tmp pointer not aligned to the element size");
-    tmp_len = usable_scratch(tmp_len);
-    if (tmp_len < 65536) return fail(RDST_ERR_ARG, "the scratch must hold at least 65536 elements");
+    if ((rc = check_second_buffer(dev_tmp, elem_bytes, false)) || (rc = check_regions_scratch(&tmp_len))) return rc;
     std::lock_guard<std::mutex> lock(g_mutex);
     hipStream_t s = static_cast<hipStream_t>(stream);
     RDST_BY_WIDTH(elem_bytes, rc = (partition_entry<K, LV>(dev_keys, len, kind, level, digit, dev_tmp, tmp_len, split_out, s)));
-    if (rc) return rc;
-    DeviceState* D;
-    if ((rc = current_device_state(&D))) return rc;
-    HIP_TRY(hipStreamSynchronize(s));
-    return read_device_error(*D, s);
+    return rc ? rc : wait_and_report(s);
 }
 
 int rdst_hip_split_top_level_device(const void* dev_src, void* dev_dst, uint64_t len, uint32_t elem_bytes, rdst_key_kind kind,
@@ -6128,11 +6142,10 @@ int rdst_hip_split_top_level_device(const void* dev_src, void* dev_dst, uint64_t
     if (!dev_counts) return fail(RDST_ERR_ARG, "null counts pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
     if (len == 0) {
-        HIP_TRY(hipMemsetAsync(dev_counts, 0, sizeof(uint64_t) * RADIX, s));
+        RDST_HIP_TRY(hipMemsetAsync(dev_counts, 0, sizeof(uint64_t) * RADIX, s));
         return RDST_OK;
     }
-    if (dev_dst == nullptr) return fail(RDST_ERR_ARG, "null dst pointer");
-    if (reinterpret_cast<uintptr_t>(dev_dst) % elem_bytes) return fail(RDST_ERR_ALIGN, "dst pointer not aligned to the element size");
+    if ((rc = check_second_buffer(dev_dst, elem_bytes, true))) return rc;
     std::lock_guard<std::mutex> lock(g_mutex);
     Layout L;
     char* ws = nullptr;
@@ -6140,10 +6153,8 @@ int rdst_hip_split_top_level_device(const void* dev_src, void* dev_dst, uint64_t
     // one un-skippable pass src -> dst on the top level; its K1 counts that level only; nothing blocks
     RDST_BY_WIDTH(elem_bytes, rc = (run_pipeline<K, LV>(const_cast<K*>(static_cast<const K*>(dev_src)), static_cast<K*>(dev_dst), len, kind, top, top + 1, false, false, s, &L, &ws)));
     if (rc) return rc;
-    HIP_TRY(hipMemcpyAsync(dev_counts, ws + L.off_hist + sizeof(uint64_t) * (size_t)top * RADIX, sizeof(uint64_t) * RADIX, hipMemcpyDeviceToDevice, s));
-    DeviceState* D;
-    if ((rc = current_device_state(&D))) return rc;
-    return workspace_release(*D, s);  // the copy reads the workspace: later calls on other streams wait for it too
+    RDST_HIP_TRY(hipMemcpyAsync(dev_counts, ws + L.off_hist + sizeof(uint64_t) * (size_t)top * RADIX, sizeof(uint64_t) * RADIX, hipMemcpyDeviceToDevice, s));
+    return rdst_internal::workspace_handback(s);  // the copy reads the workspace: later calls on other streams wait for it too
 }
 
 int rdst_hip_split_top16_device(void* dev_keys, void* dev_tmp, uint64_t len, uint32_t elem_bytes, rdst_key_kind kind,
@@ -6153,13 +6164,11 @@ int rdst_hip_split_top16_device(void* dev_keys, void* dev_tmp, uint64_t len, uin
     if (elem_bytes < 2) return fail(RDST_ERR_UNSUPPORTED, "a 16-bit split needs keys of at least two bytes");
     if (!dev_counts16) return fail(RDST_ERR_ARG, "null counts pointer");
     hipStream_t s = static_cast<hipStream_t>(stream);
-    HIP_TRY(hipMemsetAsync(dev_counts16, 0, sizeof(uint64_t) * H16_BINS, s));
+    RDST_HIP_TRY(hipMemsetAsync(dev_counts16, 0, sizeof(uint64_t) * H16_BINS, s));
     if (len == 0) return RDST_OK;
-    if (dev_tmp == nullptr) return fail(RDST_ERR_ARG, "null tmp pointer");
-    if (reinterpret_cast<uintptr_t>(dev_tmp) % elem_bytes) return fail(RDST_ERR_ALIGN, "tmp pointer not aligned to the element size");
-    std::lock_guard<std::mutex> lock(g_mutex);
-    DeviceState* D;
-    if ((rc = current_device_state(&D))) return rc;
+    if ((rc = check_second_buffer(dev_tmp, elem_bytes, false))) return rc;
+    LockedDevice D;
+    if (D.rc) return D.rc;
     const KeyMap km = key_map_for(kind, elem_bytes);
     uint64_t blocks = (len + 255) / 256;
     if (blocks > (uint64_t)D->cus * 16) blocks = (uint64_t)D->cus * 16;
@@ -6180,10 +6189,8 @@ int rdst_hip_level_counts(const void* dev_keys, uint64_t len, uint32_t elem_byte
     if (first_digit) *first_digit = 0;
     if (last_digit) *last_digit = 0;
     if (len == 0) return RDST_OK;  // sort_utils.rs:116-118
-    std::lock_guard<std::mutex> lock(g_mutex);
-    DeviceState* D;
-    rc = current_device_state(&D);
-    if (rc) return rc;
+    LockedDevice D;
+    if (D.rc) return D.rc;
     rc = ensure_workspace(*D, 1 << 20);
     if (rc) return rc;
     hipStream_t s = static_cast<hipStream_t>(stream);
@@ -6193,7 +6200,7 @@ int rdst_hip_level_counts(const void* dev_keys, uint64_t len, uint32_t elem_byte
     uint32_t* d_flag = reinterpret_cast<uint32_t*>(ws + 4096 + sizeof(uint64_t) * RADIX);
     rc = workspace_acquire(*D, s);
     if (rc) return rc;
-    HIP_TRY(hipMemsetAsync(d_counts, 0, sizeof(uint64_t) * RADIX + 16, s));
+    RDST_HIP_TRY(hipMemsetAsync(d_counts, 0, sizeof(uint64_t) * RADIX + 16, s));
     const KeyMap km = key_map_for(kind, elem_bytes);
     uint64_t blocks = (len + 255) / 256;
     const uint64_t cap = (uint64_t)D->cus * 8;
@@ -6203,13 +6210,13 @@ int rdst_hip_level_counts(const void* dev_keys, uint64_t len, uint32_t elem_byte
     if (rc) return rc;
     uint32_t flag = 0;
     u128 first = 0, last = 0;
-    HIP_TRY(hipMemcpyAsync(counts, d_counts, sizeof(uint64_t) * RADIX, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&first, dev_keys, elem_bytes, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipMemcpyAsync(&last, static_cast<const char*>(dev_keys) + (len - 1) * elem_bytes, elem_bytes, hipMemcpyDeviceToHost, s));
+    RDST_HIP_TRY(hipMemcpyAsync(counts, d_counts, sizeof(uint64_t) * RADIX, hipMemcpyDeviceToHost, s));
+    RDST_HIP_TRY(hipMemcpyAsync(&flag, d_flag, sizeof flag, hipMemcpyDeviceToHost, s));
+    RDST_HIP_TRY(hipMemcpyAsync(&first, dev_keys, elem_bytes, hipMemcpyDeviceToHost, s));
+    RDST_HIP_TRY(hipMemcpyAsync(&last, static_cast<const char*>(dev_keys) + (len - 1) * elem_bytes, elem_bytes, hipMemcpyDeviceToHost, s));
     rc = workspace_release(*D, s);
     if (rc) return rc;
-    HIP_TRY(hipStreamSynchronize(s));
+    RDST_HIP_TRY(hipStreamSynchronize(s));
     auto host_digit = [&](u128 raw) -> uint8_t {
         const bool sign = ((raw >> (elem_bytes * 8 - 1)) & 1) != 0;
         const u128 m = raw ^ (sign ? km.neg : km.pos);
@@ -6240,24 +6247,6 @@ void key_xor_masks(rdst_key_kind kind, uint32_t elem_bytes, unsigned __int128* n
     const KeyMap km = key_map_for(kind, elem_bytes);
     *neg = km.neg;
     *pos = km.pos;
-}
-
-int sort_slice_locked(void* keys, void* tmp, uint64_t n, uint32_t elem_bytes, rdst_key_kind kind, hipStream_t s) {
-    int rc = RDST_OK;
-    RDST_BY_WIDTH(elem_bytes, rc = (sort_whole<K, LV>(static_cast<K*>(keys), static_cast<K*>(tmp), n, kind, s)));
-    return rc;
-}
-
-int sort_pairs_slice_locked(void* keys, void* vals, void* tmp_keys, void* tmp_vals, uint64_t n, uint32_t key_bytes, rdst_key_kind kind,
-                            uint32_t val_bytes, hipStream_t s) {
-    return by_uint(key_bytes, [&](auto k) {
-        return by_uint(val_bytes, [&](auto v) {
-            using KT = decltype(k);
-            using VT = decltype(v);
-            return run_pipeline<KT, (int)sizeof(KT), VT>(static_cast<KT*>(keys), static_cast<KT*>(tmp_keys), n, kind, 0, sizeof(KT), true, true, s, nullptr,
-                                                         nullptr, static_cast<VT*>(vals), static_cast<VT*>(tmp_vals));
-        });
-    });
 }
 
 namespace {
@@ -6323,10 +6312,8 @@ int profile_stage_end(hipStream_t s, uint32_t stage) {
 }
 
 int device_error_word(uint32_t** out, int* cus_out) {
-    std::lock_guard<std::mutex> lock(g_mutex);
-    DeviceState* D;
-    int rc = current_device_state(&D);
-    if (rc) return rc;
+    LockedDevice D;
+    if (D.rc) return D.rc;
     *out = D->err_dev;
     if (cus_out) *cus_out = D->cus;
     return RDST_OK;
@@ -6348,10 +6335,10 @@ int sort_bytes_widened(void* dev_rows, uint64_t len, uint32_t nb, void* scratch,
 int ensure_lds_attr(const void* fn, size_t lds) {
     static std::map<std::pair<int, const void*>, size_t> done;  // callers hold g_mutex
     int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
+    RDST_HIP_TRY(hipGetDevice(&dev));
     auto it = done.find({dev, fn});
     if (it != done.end() && it->second == lds) return RDST_OK;
-    HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    RDST_HIP_TRY(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     done[{dev, fn}] = lds;
     return RDST_OK;
 }

@@ -403,30 +403,24 @@ struct Staging {
 };
 Staging g_staging[16];
 
-#define SEG_HIP_TRY(expr)                                                   \
-    do {                                                                    \
-        hipError_t e__ = (expr);                                            \
-        if (e__ != hipSuccess) return set_error(RDST_ERR_HIP, #expr, e__);  \
-    } while (0)
-
 int stage_items(Staging& st, const rdst_segment_item* items, size_t count, void* dev_dst, hipStream_t s) {
     const size_t bytes = count * sizeof(rdst_segment_item);
     if (st.in_flight) {  // the previous call's copy still reads the buffer
-        SEG_HIP_TRY(hipEventSynchronize(st.copied));
+        RDST_HIP_TRY(hipEventSynchronize(st.copied));
         st.in_flight = false;
     }
-    if (!st.copied) SEG_HIP_TRY(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
+    if (!st.copied) RDST_HIP_TRY(hipEventCreateWithFlags(&st.copied, hipEventDisableTiming));
     if (st.bytes < bytes) {
-        if (st.host) SEG_HIP_TRY(hipHostFree(st.host));
+        if (st.host) RDST_HIP_TRY(hipHostFree(st.host));
         st.host = nullptr;
         st.bytes = 0;
         const size_t want = (bytes + bytes / 4 + 4095) / 4096 * 4096;
-        SEG_HIP_TRY(hipHostMalloc(&st.host, want, hipHostMallocDefault));
+        RDST_HIP_TRY(hipHostMalloc(&st.host, want, hipHostMallocDefault));
         st.bytes = want;
     }
     memcpy(st.host, items, bytes);
-    SEG_HIP_TRY(hipMemcpyAsync(dev_dst, st.host, bytes, hipMemcpyHostToDevice, s));
-    SEG_HIP_TRY(hipEventRecord(st.copied, s));
+    RDST_HIP_TRY(hipMemcpyAsync(dev_dst, st.host, bytes, hipMemcpyHostToDevice, s));
+    RDST_HIP_TRY(hipEventRecord(st.copied, s));
     st.in_flight = true;
     return RDST_OK;
 }
@@ -659,7 +653,7 @@ int enqueue_plan_t(const void* dev_offsets, uint64_t n_segments, uint64_t len, u
     const Off* off = static_cast<const Off*>(dev_offsets);
     const uint32_t nseg = (uint32_t)n_segments;
     const dim3 grid((uint32_t)((n_segments + PLAN_THREADS - 1) / PLAN_THREADS));
-    SEG_HIP_TRY(hipMemsetAsync(P.hdr, 0, HDR_WORDS * sizeof(uint32_t), s));
+    RDST_HIP_TRY(hipMemsetAsync(P.hdr, 0, HDR_WORDS * sizeof(uint32_t), s));
     int rc = launch("segments_keygen_kernel", segments_keygen_kernel<Off>, grid, dim3(PLAN_THREADS), 0, s, off, nseg, len, wave_max, block_max, P.keys, P.segs, P.hdr);
     if (rc) return rc;
     if (n_segments > 1 && (rc = rdst_internal::sort_pairs_slice_locked(P.keys, P.segs, P.tmp_keys, P.tmp_segs, n_segments, 4, RDST_KEY_UNSIGNED, 4, s))) return rc;
@@ -689,8 +683,8 @@ struct PlanResult {
 };
 int read_plan(const PlanScratch& P, PlanResult* r, hipStream_t s) {
     uint32_t h[8] = {};
-    SEG_HIP_TRY(hipMemcpyAsync(h, P.hdr, sizeof h, hipMemcpyDeviceToHost, s));
-    SEG_HIP_TRY(hipStreamSynchronize(s));
+    RDST_HIP_TRY(hipMemcpyAsync(h, P.hdr, sizeof h, hipMemcpyDeviceToHost, s));
+    RDST_HIP_TRY(hipStreamSynchronize(s));
     r->counts[0] = h[HDR_N_WAVE];
     r->counts[1] = h[HDR_N_BLOCK];
     r->counts[2] = h[HDR_N_LONG];
@@ -727,9 +721,9 @@ int sort_segments_offsets(const SegCall& c, bool pair_entry, uint64_t tmp_elems,
     if (r.counts[2] == 0) return RDST_OK;
     std::vector<rdst_segment_item> long_items((size_t)r.counts[2]);
     std::vector<uint64_t> long_lens((size_t)r.counts[2]);
-    SEG_HIP_TRY(hipMemcpyAsync(long_items.data(), P.items + batched, long_items.size() * sizeof(rdst_segment_item), hipMemcpyDeviceToHost, c.s));
-    SEG_HIP_TRY(hipMemcpyAsync(long_lens.data(), P.long_lens, long_lens.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, c.s));
-    SEG_HIP_TRY(hipStreamSynchronize(c.s));
+    RDST_HIP_TRY(hipMemcpyAsync(long_items.data(), P.items + batched, long_items.size() * sizeof(rdst_segment_item), hipMemcpyDeviceToHost, c.s));
+    RDST_HIP_TRY(hipMemcpyAsync(long_lens.data(), P.long_lens, long_lens.size() * sizeof(uint64_t), hipMemcpyDeviceToHost, c.s));
+    RDST_HIP_TRY(hipStreamSynchronize(c.s));
     for (size_t i = 0; i < long_items.size(); ++i) {
         const uint64_t start = long_items[i].start, n = long_lens[i];
         if (n > tmp_elems || start > c.len || n > c.len - start) return set_error(RDST_ERR_DEVICE, "segments: a long item of the device plan lies outside the array");
@@ -1189,8 +1183,8 @@ extern "C" int rdst_hip_debug_segments_plan_device(const void* dev_offsets, uint
     if (r.flags || total == 0) return RDST_OK;  // (an invalid table: the flags are the answer, the items mean nothing)
     if (total > capacity) return set_error(RDST_ERR_ARG, "segments_plan_device: capacity too small for the work list");
     if (!items_out) return set_error(RDST_ERR_ARG, "segments_plan_device: null item table");
-    SEG_HIP_TRY(hipMemcpyAsync(items_out, P.items, (size_t)total * sizeof(rdst_segment_item), hipMemcpyDeviceToHost, s));
-    SEG_HIP_TRY(hipStreamSynchronize(s));
+    RDST_HIP_TRY(hipMemcpyAsync(items_out, P.items, (size_t)total * sizeof(rdst_segment_item), hipMemcpyDeviceToHost, s));
+    RDST_HIP_TRY(hipStreamSynchronize(s));
     return RDST_OK;
 }
 
