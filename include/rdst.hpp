@@ -6,6 +6,8 @@
 //   rdst::radix_sort_unstable(v)                        RadixSort::radix_sort_unstable     src/radix_sort.rs:21-45
 //   rdst::radix_sort_unstable_by_field(v, &T::key)      the same on structs keyed by a field benches/struct_sort.rs:11-27
 //   rdst::sort_records_by(v, {RDST_FIELD(T, a, kind), ...})  `impl RadixKey for T` stated as a field table  src/radix_key.rs, examples/impl_radix_key.rs:32-56
+//   rdst::sort_bytes_device_nowait<N>(rows, n, ...)     [u8; N] rows in device memory, asynchronous  src/radix_key_impl.rs:78-85
+//   rdst::sort_records_by_device_nowait<T>(recs, n, {...}, ...)  the field table on device records, asynchronous  src/radix_key.rs
 //   rdst::radix_sort_builder(v).with_*().sort()         RadixSortBuilder                   src/radix_sort_builder.rs:8-158
 //   rdst::RadixKey<T>::LEVELS / kind                    RadixKey for the built-in types    src/radix_key_impl.rs:1-185
 //   rdst::tuner::{Tuner, TuningParams, Algorithm, ...}  pub mod tuner                      src/tuner.rs:1-40, src/tuners/*.rs
@@ -271,6 +273,28 @@ void sort_segments_device_offsets_nowait(T* dev_keys, V* dev_vals, T* dev_tmp_ke
                                                                       n_segments, sizeof(T), RadixKey<T>::kind,
                                                                       static_cast<std::uint32_t>(RadixKey<T>::LEVELS), sizeof(V), dev_scratch,
                                                                       scratch_bytes, stream);
+    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+}
+
+// DEVICE-resident [u8; N] rows (src/radix_key_impl.rs:78-85) and DEVICE-resident structs ordered by a described key
+// (src/radix_key.rs; examples/impl_radix_key.rs:32-56), in place and with no host involvement
+// (rdst_hip_sort_bytes_device_nowait, rdst_hip_sort_records_by_fields_device_nowait): N, or the sum of the fields' widths,
+// up to RDST_BYTES_NOWAIT_MAX_N.  Nothing is copied to the host and nothing waited for; failures of the kernels surface in
+// rdst_hip_device_status.  Equal keys keep their input order.  dev_scratch: at least rdst_hip_sort_bytes_scratch_bytes(n, N) /
+// rdst_hip_sort_records_by_fields_scratch_bytes(n, sizeof(T), fields, n_fields) bytes, 256-byte aligned.
+template <std::size_t N>
+void sort_bytes_device_nowait(std::array<std::uint8_t, N>* dev_rows, std::size_t n, void* dev_scratch, std::size_t scratch_bytes,
+                              void* stream = nullptr) {
+    static_assert(N >= 1 && N <= RDST_BYTES_NOWAIT_MAX_N, "the nowait entry takes [u8; N] keys with N in 1..RDST_BYTES_NOWAIT_MAX_N");
+    const int rc = rdst_hip_sort_bytes_device_nowait(dev_rows, n, static_cast<std::uint32_t>(N), dev_scratch, scratch_bytes, stream);
+    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+}
+template <typename T>
+void sort_records_by_device_nowait(T* dev_records, std::size_t n, std::initializer_list<rdst_key_field> fields, void* dev_scratch,
+                                   std::size_t scratch_bytes, void* stream = nullptr) {
+    static_assert(std::is_trivially_copyable<T>::value, "rows are moved as bytes");
+    const int rc = rdst_hip_sort_records_by_fields_device_nowait(dev_records, n, sizeof(T), fields.begin(),
+                                                                 static_cast<std::uint32_t>(fields.size()), dev_scratch, scratch_bytes, stream);
     if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
 }
 

@@ -313,12 +313,26 @@ int rdst_hip_debug_segments_plan_device(const void* dev_offsets, uint32_t offset
  * N > 16 (needs len < 2^32, else RDST_ERR_UNSUPPORTED): one stable (u64 prefix, u32 row) pair sort, then rounds over
  * the rows still tied — short runs by a comparison kernel, long ones by another pair sort on (run, next bytes) — and a
  * gather of the rows.  BLOCKING: the tie counts of every round come to the host (one copy and one wait per
- * round; keys that differ in their first 8 bytes take exactly one).  Equal rows keep their input order.  Kernel failures
- * are reported by rdst_hip_device_status. */
+ * round; keys that differ in their first 8 bytes take exactly one; rdst_hip_sort_bytes_device_nowait below does without).
+ * Equal rows keep their input order.  Kernel failures are reported by rdst_hip_device_status. */
 #define RDST_BYTES_MAX_N 4096u
 int rdst_hip_sort_bytes_device(void* dev_rows, uint64_t len, uint32_t n_bytes,
                                void* dev_scratch, uint64_t scratch_bytes, void* stream);
 uint64_t rdst_hip_sort_bytes_scratch_bytes(uint64_t len, uint32_t n_bytes);   /* 0 for n_bytes outside 1..RDST_BYTES_MAX_N */
+
+/* rdst_hip_sort_bytes_device without the host in the loop (src/radix_key_impl.rs:78-85: the same lexicographic order,
+ * bit for bit the blocking entry's result; equal rows keep their input order).  The arguments, the scratch size
+ * (rdst_hip_sort_bytes_scratch_bytes), the alignment rules, the argument errors and their order are those of the blocking
+ * entry.  N <= 16 forwards to the widened integer route.  N > 16: the prefix pair sort, one kernel that raises a flag word
+ * on the device if any two 8-byte prefixes tie, then ceil(N / 8) rounds, last chunk first, each a chunk-key kernel and a
+ * stable (u64 chunk, u32 row) pair sort; with the flag down every key of a round is 0 and its pair sort skips all its
+ * levels.  The rounds are enqueued whether or not they are needed, so the entry is built for 16 rounds at
+ * most: N > RDST_BYTES_NOWAIT_MAX_N -> RDST_ERR_UNSUPPORTED (wider keys take rdst_hip_sort_bytes_device).
+ * ASYNCHRONOUS on `stream`: no copy to the host, no stream or event wait; the one exception is the one every entry shares,
+ * a library workspace that has to grow.  Kernel failures are reported by rdst_hip_device_status. */
+#define RDST_BYTES_NOWAIT_MAX_N 128u
+int rdst_hip_sort_bytes_device_nowait(void* dev_rows, uint64_t len, uint32_t n_bytes,
+                                      void* dev_scratch, uint64_t scratch_bytes, void* stream);
 
 /* ---- records ordered by a described key ------------------------------------------------------
  * `impl RadixKey for MyStruct` as data (src/radix_key.rs: `const LEVELS` and `get_level`; examples/impl_radix_key.rs:32-56
@@ -362,6 +376,18 @@ int rdst_hip_sort_records_by_fields_device(void* dev_records, uint64_t len, uint
                                            void* dev_scratch, uint64_t scratch_bytes, void* stream);
 uint64_t rdst_hip_sort_records_by_fields_scratch_bytes(uint64_t len, uint32_t record_bytes,
                                                        const rdst_key_field* fields, uint32_t n_fields);  /* 0 for an invalid description */
+
+/* rdst_hip_sort_records_by_fields_device without the host in the loop (src/radix_key.rs, examples/impl_radix_key.rs:32-56:
+ * the same described RadixKey, bit for bit the blocking entry's result; records with equal keys keep their input order).
+ * The arguments, the scratch size (rdst_hip_sort_records_by_fields_scratch_bytes), the alignment rules, the argument errors
+ * and their order are those of the blocking entry.  L <= 8 forwards to the one pair sort.  L > 8: the packed keys take the
+ * rounds of rdst_hip_sort_bytes_device_nowait, which are enqueued whether or not they are needed; hence
+ * L > RDST_BYTES_NOWAIT_MAX_N -> RDST_ERR_UNSUPPORTED (longer keys take rdst_hip_sort_records_by_fields_device).
+ * ASYNCHRONOUS on `stream` for every L, but for a library workspace that has to grow.  Kernel failures are reported by
+ * rdst_hip_device_status. */
+int rdst_hip_sort_records_by_fields_device_nowait(void* dev_records, uint64_t len, uint32_t record_bytes,
+                                                  const rdst_key_field* fields, uint32_t n_fields,
+                                                  void* dev_scratch, uint64_t scratch_bytes, void* stream);
 
 /* Parity and timing hook: pack_fields_kernel alone.  dev_keys receives K for every record in the form the route sorts:
  * L <= 4: len u32 keys, L <= 8: len u64 keys (K left-justified, zero-filled; aligned to their size), L > 8: len dense

@@ -28,6 +28,7 @@ from .radix_sort import (  # noqa: F401
     profile_run,
     profile_runs,
     sort_bytes_device_tensor,
+    sort_bytes_device_nowait_tensor,
     sort_device_tensor,
     sort_device_tensor_lowmem,
     partition_device,
@@ -44,6 +45,7 @@ from .radix_sort import (  # noqa: F401
     segments_nowait_scratch_bytes,
     sort_records_by_key,
     sort_records_device_tensor,
+    sort_records_device_nowait_tensor,
     KeyField,
     key_fields_of,
 )
@@ -54,5 +56,5 @@ __all__ = [
     "sort_device_tensor", "sort_bytes_device_tensor", "sort_device_tensor_lowmem", "partition_device", "sort_host_array", "sort_host_records", "sort_pairs_device_tensor", "sort_segments_device_tensor", "segments_limits", "segments_plan",
     "sort_segments_device_offsets_tensor", "sort_segments_device_offsets_nowait_tensor", "segments_nowait_scratch_bytes", "segments_device_offsets_scratch_bytes", "segments_plan_device", "sort_records_by_key", "level_counts", "all_level_counts", "scatter_level",
     "device_status", "set_tuning", "set_profiling", "set_hybrid", "last_route", "last_sample", "release_workspace", "last_profile", "key_info",
-    "KeyField", "key_fields_of", "sort_records_device_tensor",
+    "KeyField", "key_fields_of", "sort_records_device_tensor", "sort_bytes_device_nowait_tensor", "sort_records_device_nowait_tensor",
 ]

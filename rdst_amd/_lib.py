@@ -14,6 +14,7 @@ LIB_PATH = os.environ.get("RDST_HIP_LIB") or os.path.join(_HERE, "librdst_hip.so
 RDST_KEY_UNSIGNED, RDST_KEY_SIGNED, RDST_KEY_FLOAT, RDST_KEY_BYTES_BE = 0, 1, 2, 3
 RDST_OK = 0
 RDST_BYTES_MAX_N = 4096  # longest [u8; N] key the device route takes (include/rdst_hip.h)
+RDST_BYTES_NOWAIT_MAX_N = 128  # longest key the nowait [u8; N] and described-key entries take
 RDST_FIELD_DESCENDING = 1  # rdst_key_field.flags: complement the field's mapped bytes
 RDST_KEY_FIELDS_MAX = 16   # fields in one key description
 RDST_STAGE_SEGMENTS = 13   # rdst_stage: the batched launches of the segmented sort
@@ -42,9 +43,11 @@ SYMBOLS = (
     "rdst_hip_sort_records",
     "rdst_hip_sort_bytes_device",
     "rdst_hip_sort_bytes_scratch_bytes",
+    "rdst_hip_sort_bytes_device_nowait",
     "rdst_hip_sort_records_by_fields",
     "rdst_hip_sort_records_by_fields_device",
     "rdst_hip_sort_records_by_fields_scratch_bytes",
+    "rdst_hip_sort_records_by_fields_device_nowait",
     "rdst_hip_pack_fields_device",
     "rdst_hip_device_status",
     "rdst_hip_level_counts",
@@ -146,11 +149,13 @@ def load():
                                                         ctypes.POINTER(u32), vp]
     lib.rdst_hip_sort_records.argtypes = [vp, u64, u32, u32, u32, ci, ctypes.POINTER(HipOptsC)]
     lib.rdst_hip_sort_bytes_device.argtypes = [vp, u64, u32, vp, u64, vp]
+    lib.rdst_hip_sort_bytes_device_nowait.argtypes = [vp, u64, u32, vp, u64, vp]
     lib.rdst_hip_sort_bytes_scratch_bytes.argtypes = [u64, u32]
     lib.rdst_hip_sort_bytes_scratch_bytes.restype = u64
     kfp = ctypes.POINTER(KeyFieldC)
     lib.rdst_hip_sort_records_by_fields.argtypes = [vp, u64, u32, kfp, u32, ctypes.POINTER(HipOptsC)]
     lib.rdst_hip_sort_records_by_fields_device.argtypes = [vp, u64, u32, kfp, u32, vp, u64, vp]
+    lib.rdst_hip_sort_records_by_fields_device_nowait.argtypes = [vp, u64, u32, kfp, u32, vp, u64, vp]
     lib.rdst_hip_sort_records_by_fields_scratch_bytes.argtypes = [u64, u32, kfp, u32]
     lib.rdst_hip_sort_records_by_fields_scratch_bytes.restype = u64
     lib.rdst_hip_pack_fields_device.argtypes = [vp, u64, u32, kfp, u32, vp, vp, vp]

@@ -19,6 +19,10 @@
 // Stability: the prefix sort is stable on row indices, every later sort is stable on positions that are in row order
 // within a run, and the comparison kernel breaks ties on the row index — equal keys keep their input order.
 //
+// bytes_order_nowait is the same order without the host in the loop, for N up to RDST_BYTES_NOWAIT_MAX_N: after step 1 a
+// kernel raises a flag on the device if any two prefixes tie, and ceil(N / 8) rounds of (chunk keys, stable pair sort)
+// follow whatever it says — with the flag down their keys are all 0 and the pair sorts skip every level.
+//
 // The second half of the file is the records route for keys described by a field table (rdst_key_field): one kernel
 // that packs the mapped key bytes, then the pair sort or the core above, then the same gather.
 
@@ -351,6 +355,35 @@ __global__ __launch_bounds__(256) void slots_scatter_kernel(const uint32_t* __re
     }
 }
 
+// ---- nowait rounds (bytes_order_nowait): tie flag, chunk keys ------------------------------------------------------------
+// *flag |= 1 if two neighbours among the n sorted prefix keys are equal.  Item j reads keys[j - 1] from memory, so a pair
+// that straddles two workgroups or two grid trips is seen like any other.  The caller cleared the word on the stream.
+__global__ __launch_bounds__(256) void tie_flag_kernel(const uint64_t* __restrict__ keys, uint64_t n, uint32_t* flag) {
+    const uint64_t step = (uint64_t)gridDim.x * 256;
+    bool tie = false;
+    for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x + 1; j < n; j += step) tie |= keys[j] == keys[j - 1];
+    if (tie) atomicOr(flag, 1u);
+}
+
+// key[j] = *flag ? key bytes [from, from + k) of row idx[j], big-endian, left-justified, zero-filled : 0.  idx stays as it
+// is: it is the value array of the pair sort that follows.
+__global__ __launch_bounds__(256) void chunk_keys_kernel(const uint8_t* __restrict__ rows, uint32_t stride, uint32_t off, uint32_t n_bytes,
+                                                         uint32_t from, uint32_t k, const uint32_t* __restrict__ idx,
+                                                         const uint32_t* __restrict__ flag, uint64_t n, uint64_t* __restrict__ keys,
+                                                         uint32_t* err) {
+    const bool up = *flag != 0;
+    const uint64_t step = (uint64_t)gridDim.x * 256;
+    for (uint64_t j = (uint64_t)blockIdx.x * 256 + threadIdx.x; j < n; j += step) {
+        uint64_t key = 0;
+        if (up) {
+            const uint32_t row = idx[j];
+            if (row >= n) raise(err, ERR_BYTES_RANGE);
+            else key = load_be(rows + (uint64_t)row * stride + off, from, k, n_bytes) << (64 - 8 * k);
+        }
+        keys[j] = key;
+    }
+}
+
 // ---- 5: gather --------------------------------------------------------------------------------------------------------
 struct alignas(16) Unit16 { uint64_t a, b; };
 template <typename U>
@@ -482,6 +515,38 @@ int bytes_order(const uint8_t* rows, uint64_t n, uint32_t stride, uint32_t off, 
     return RDST_OK;
 }
 
+// The same order without the host in the loop (n_bytes <= RDST_BYTES_NOWAIT_MAX_N): every launch is fixed by n and n_bytes
+// alone.  After the prefix sort one kernel raises a flag word if any two prefixes tie; then ceil(n_bytes / 8) rounds, last
+// chunk first, each a chunk-key kernel and a stable pair sort of (chunk, row).  Flag down: every key is 0, the pair sorts
+// skip all their levels and idx stays as the prefix sort left it.  Flag up: an LSD sort over all chunks on top of the prefix
+// order; rows equal in every byte have equal prefixes, so they are in row order already and every later sort keeps them so.
+// Uses keys, keys_tmp, idx, vals_tmp and the first word of cnt.
+int bytes_order_nowait(const uint8_t* rows, uint64_t n, uint32_t stride, uint32_t off, uint32_t n_bytes, char* scratch,
+                       hipStream_t s, uint32_t* err) {
+    const Layout L = make_layout(n);
+    uint64_t* keys = reinterpret_cast<uint64_t*>(scratch + L.keys);
+    uint64_t* keys_tmp = reinterpret_cast<uint64_t*>(scratch + L.keys_tmp);
+    uint32_t* idx = reinterpret_cast<uint32_t*>(scratch + L.idx);
+    uint32_t* vals_tmp = reinterpret_cast<uint32_t*>(scratch + L.vals_tmp);
+    uint32_t* flag = reinterpret_cast<uint32_t*>(scratch + L.cnt);
+
+    RDST_HIP_TRY(hipMemsetAsync(flag, 0, sizeof(uint32_t), s));
+    const uint32_t k0 = n_bytes < 8 ? n_bytes : 8;
+    int rc = launch("bytes_keys_kernel", bytes_keys_kernel, dim3(grid_for(n)), dim3(256), 0, s, rows, stride, off, n_bytes, 0u, k0, 0u, nullptr, nullptr,
+                    nullptr, n, n, keys, idx, err);
+    if (rc) return rc;
+    std::lock_guard<std::mutex> lock(rdst_internal::library_mutex());  // once, around all the pair sorts
+    if ((rc = rdst_internal::sort_pairs_slice_locked(keys, idx, keys_tmp, vals_tmp, n, 8, RDST_KEY_UNSIGNED, 4, s))) return rc;
+    if ((rc = launch("tie_flag_kernel", tie_flag_kernel, dim3(grid_for(n)), dim3(256), 0, s, keys, n, flag))) return rc;
+    for (uint32_t c = (n_bytes + 7) / 8; c-- > 0;) {
+        const uint32_t from = 8 * c, k = n_bytes - from < 8 ? n_bytes - from : 8;
+        if ((rc = launch("chunk_keys_kernel", chunk_keys_kernel, dim3(grid_for(n)), dim3(256), 0, s, rows, stride, off, n_bytes, from, k, idx, flag, n, keys, err)))
+            return rc;
+        if ((rc = rdst_internal::sort_pairs_slice_locked(keys, idx, keys_tmp, vals_tmp, n, 8, RDST_KEY_UNSIGNED, 4, s))) return rc;
+    }
+    return RDST_OK;
+}
+
 int bytes_gather(const uint8_t* src, uint8_t* dst, const uint32_t* idx, uint64_t n, uint32_t stride, hipStream_t s, uint32_t* err) {
     const uintptr_t a = reinterpret_cast<uintptr_t>(src) | reinterpret_cast<uintptr_t>(dst) | stride;
     const uint32_t unit = a % 16 == 0 ? 16 : (a % 8 == 0 ? 8 : (a % 4 == 0 ? 4 : 1));
@@ -525,17 +590,12 @@ int sort_bytes_rows_host(void* host_rows, uint64_t len, uint32_t row_bytes, uint
 
 }  // namespace rdst_internal
 
-extern "C" {
-
-uint64_t rdst_hip_sort_bytes_scratch_bytes(uint64_t len, uint32_t n_bytes) {
-    if (n_bytes == 0 || n_bytes > RDST_BYTES_MAX_N) return 0;
-    if (n_bytes <= 16) return rdst_internal::widened_scratch_bytes(len, n_bytes);
-    return core_scratch_bytes(len) + align256(len * n_bytes);
-}
-
-int rdst_hip_sort_bytes_device(void* dev_rows, uint64_t len, uint32_t n_bytes, void* dev_scratch, uint64_t scratch_bytes, void* stream) {
+namespace {
+// Both device entries for [u8; N] rows; `max_n` and `order` are what tells them apart.
+int sort_bytes_device(void* dev_rows, uint64_t len, uint32_t n_bytes, void* dev_scratch, uint64_t scratch_bytes, void* stream, uint32_t max_n,
+                      const char* too_wide, decltype(bytes_order)* order) {
     if (n_bytes == 0) return set_error(RDST_ERR_ARG, "[u8; N] needs N >= 1 (RadixKey::LEVELS == 0 panics in rdst)");
-    if (n_bytes > RDST_BYTES_MAX_N) return set_error(RDST_ERR_UNSUPPORTED, "[u8; N] keys are built for N in 1..RDST_BYTES_MAX_N");
+    if (n_bytes > max_n) return set_error(RDST_ERR_UNSUPPORTED, too_wide);
     if (len <= 1) return RDST_OK;  // radix_sort_builder.rs:151
     if (dev_rows == nullptr) return set_error(RDST_ERR_ARG, "null rows pointer");
     if (n_bytes > 16 && len >= (1ull << 32)) return set_error(RDST_ERR_UNSUPPORTED, "[u8; N] keys with N > 16 are built for len < 2^32");
@@ -552,12 +612,32 @@ int rdst_hip_sort_bytes_device(void* dev_rows, uint64_t len, uint32_t n_bytes, v
     const Layout L = make_layout(len);
     uint8_t* rows = static_cast<uint8_t*>(dev_rows);
     uint8_t* staged = reinterpret_cast<uint8_t*>(scratch + L.total);
-    rc = bytes_order(rows, len, n_bytes, 0, n_bytes, scratch, s, err);
+    rc = order(rows, len, n_bytes, 0, n_bytes, scratch, s, err);
     if (rc) return rc;
     rc = bytes_gather(rows, staged, reinterpret_cast<const uint32_t*>(scratch + L.idx), len, n_bytes, s, err);
     if (rc) return rc;
     RDST_HIP_TRY(hipMemcpyAsync(rows, staged, len * n_bytes, hipMemcpyDeviceToDevice, s));
     return RDST_OK;
+}
+}  // namespace
+
+extern "C" {
+
+uint64_t rdst_hip_sort_bytes_scratch_bytes(uint64_t len, uint32_t n_bytes) {
+    if (n_bytes == 0 || n_bytes > RDST_BYTES_MAX_N) return 0;
+    if (n_bytes <= 16) return rdst_internal::widened_scratch_bytes(len, n_bytes);
+    return core_scratch_bytes(len) + align256(len * n_bytes);
+}
+
+int rdst_hip_sort_bytes_device(void* dev_rows, uint64_t len, uint32_t n_bytes, void* dev_scratch, uint64_t scratch_bytes, void* stream) {
+    return sort_bytes_device(dev_rows, len, n_bytes, dev_scratch, scratch_bytes, stream, RDST_BYTES_MAX_N,
+                             "[u8; N] keys are built for N in 1..RDST_BYTES_MAX_N", bytes_order);
+}
+
+int rdst_hip_sort_bytes_device_nowait(void* dev_rows, uint64_t len, uint32_t n_bytes, void* dev_scratch, uint64_t scratch_bytes, void* stream) {
+    return sort_bytes_device(dev_rows, len, n_bytes, dev_scratch, scratch_bytes, stream, RDST_BYTES_NOWAIT_MAX_N,
+                             "the nowait [u8; N] entry is built for N in 1..RDST_BYTES_NOWAIT_MAX_N; wider keys take rdst_hip_sort_bytes_device",
+                             bytes_order_nowait);
 }
 
 }  // extern "C"
@@ -670,7 +750,8 @@ __global__ __launch_bounds__(256) void pack_fields_kernel(const uint8_t* __restr
 }
 
 // The description's rules (rdst_hip.h); *L_out = the key's length in bytes.
-int check_fields(uint32_t record_bytes, const rdst_key_field* fields, uint32_t n_fields, uint32_t* L_out) {
+// `max_L`: the longest key the calling entry takes.
+int check_fields(uint32_t record_bytes, const rdst_key_field* fields, uint32_t n_fields, uint32_t* L_out, uint32_t max_L = RDST_BYTES_MAX_N) {
     if (n_fields == 0) return set_error(RDST_ERR_ARG, "a key needs at least one field (RadixKey::LEVELS == 0 panics in rdst)");
     if (n_fields > RDST_KEY_FIELDS_MAX) return set_error(RDST_ERR_UNSUPPORTED, "key descriptions are built for at most RDST_KEY_FIELDS_MAX fields");
     if (fields == nullptr) return set_error(RDST_ERR_ARG, "null field table");
@@ -688,6 +769,8 @@ int check_fields(uint32_t record_bytes, const rdst_key_field* fields, uint32_t n
         L += b;
     }
     if (L > RDST_BYTES_MAX_N) return set_error(RDST_ERR_UNSUPPORTED, "described keys are built for at most RDST_BYTES_MAX_N bytes in all");
+    if (L > max_L)
+        return set_error(RDST_ERR_UNSUPPORTED, "the nowait entry is built for described keys of at most RDST_BYTES_NOWAIT_MAX_N bytes in all; longer keys take rdst_hip_sort_records_by_fields_device");
     *L_out = (uint32_t)L;
     return RDST_OK;
 }
@@ -735,9 +818,10 @@ FieldTable make_table(const rdst_key_field* fields, uint32_t n_fields) {
     return d;
 }
 
-// Packs, orders and gathers into the scratch's staging area; `rows` is only read.  Asynchronous for L <= 8.
+// Packs, orders and gathers into the scratch's staging area; `rows` is only read.  Asynchronous for L <= 8, and for every
+// L with `nowait` (bytes_order_nowait in place of bytes_order).
 int fields_sort_staged(const uint8_t* rows, uint64_t n, uint32_t R, const rdst_key_field* fields, uint32_t n_fields, uint32_t L,
-                       char* scratch, hipStream_t s, uint32_t* err) {
+                       char* scratch, hipStream_t s, uint32_t* err, bool nowait = false) {
     const FieldsLayout F = make_fields_layout(n, R, L);
     const FieldTable d = make_table(fields, n_fields);
     uint32_t* idx = reinterpret_cast<uint32_t*>(scratch + F.idx);
@@ -749,9 +833,32 @@ int fields_sort_staged(const uint8_t* rows, uint64_t n, uint32_t R, const rdst_k
     } else {
         uint8_t* packed = reinterpret_cast<uint8_t*>(scratch + F.packed);
         if ((rc = launch_pack(rows, n, R, d, L, packed, nullptr, s))) return rc;
-        if ((rc = bytes_order(packed, n, L, 0, L, scratch, s, err))) return rc;
+        if ((rc = (nowait ? bytes_order_nowait : bytes_order)(packed, n, L, 0, L, scratch, s, err))) return rc;
     }
     return bytes_gather(rows, reinterpret_cast<uint8_t*>(scratch + F.staged), idx, n, R, s, err);
+}
+
+
+// Both device entries for records with a described key; `max_L` and `nowait` are what tells them apart.
+int sort_records_by_fields_device(void* dev_records, uint64_t len, uint32_t record_bytes, const rdst_key_field* fields, uint32_t n_fields,
+                                  void* dev_scratch, uint64_t scratch_bytes, void* stream, uint32_t max_L, bool nowait) {
+    uint32_t L = 0;
+    int rc = check_fields(record_bytes, fields, n_fields, &L, max_L);
+    if (rc) return rc;
+    if (len <= 1) return RDST_OK;  // radix_sort_builder.rs:151
+    if (dev_records == nullptr) return set_error(RDST_ERR_ARG, "null record pointer");
+    if (len >= (1ull << 32)) return set_error(RDST_ERR_UNSUPPORTED, "records with a described key are built for len < 2^32 (row indices are u32)");
+    if (dev_scratch == nullptr) return set_error(RDST_ERR_ARG, "null scratch pointer");
+    const FieldsLayout F = make_fields_layout(len, record_bytes, L);
+    if (scratch_bytes < F.total) return set_error(RDST_ERR_ARG, "scratch smaller than rdst_hip_sort_records_by_fields_scratch_bytes(...)");
+    if (reinterpret_cast<uintptr_t>(dev_scratch) % 256) return set_error(RDST_ERR_ALIGN, "scratch not 256-byte aligned");
+    hipStream_t s = static_cast<hipStream_t>(stream);
+    uint32_t* err = nullptr;
+    if ((rc = rdst_internal::device_error_word(&err))) return rc;
+    char* scratch = static_cast<char*>(dev_scratch);
+    if ((rc = fields_sort_staged(static_cast<const uint8_t*>(dev_records), len, record_bytes, fields, n_fields, L, scratch, s, err, nowait))) return rc;
+    RDST_HIP_TRY(hipMemcpyAsync(dev_records, scratch + F.staged, len * record_bytes, hipMemcpyDeviceToDevice, s));
+    return RDST_OK;
 }
 
 }  // namespace
@@ -766,23 +873,13 @@ uint64_t rdst_hip_sort_records_by_fields_scratch_bytes(uint64_t len, uint32_t re
 
 int rdst_hip_sort_records_by_fields_device(void* dev_records, uint64_t len, uint32_t record_bytes, const rdst_key_field* fields,
                                            uint32_t n_fields, void* dev_scratch, uint64_t scratch_bytes, void* stream) {
-    uint32_t L = 0;
-    int rc = check_fields(record_bytes, fields, n_fields, &L);
-    if (rc) return rc;
-    if (len <= 1) return RDST_OK;  // radix_sort_builder.rs:151
-    if (dev_records == nullptr) return set_error(RDST_ERR_ARG, "null record pointer");
-    if (len >= (1ull << 32)) return set_error(RDST_ERR_UNSUPPORTED, "records with a described key are built for len < 2^32 (row indices are u32)");
-    if (dev_scratch == nullptr) return set_error(RDST_ERR_ARG, "null scratch pointer");
-    const FieldsLayout F = make_fields_layout(len, record_bytes, L);
-    if (scratch_bytes < F.total) return set_error(RDST_ERR_ARG, "scratch smaller than rdst_hip_sort_records_by_fields_scratch_bytes(...)");
-    if (reinterpret_cast<uintptr_t>(dev_scratch) % 256) return set_error(RDST_ERR_ALIGN, "scratch not 256-byte aligned");
-    hipStream_t s = static_cast<hipStream_t>(stream);
-    uint32_t* err = nullptr;
-    if ((rc = rdst_internal::device_error_word(&err))) return rc;
-    char* scratch = static_cast<char*>(dev_scratch);
-    if ((rc = fields_sort_staged(static_cast<const uint8_t*>(dev_records), len, record_bytes, fields, n_fields, L, scratch, s, err))) return rc;
-    RDST_HIP_TRY(hipMemcpyAsync(dev_records, scratch + F.staged, len * record_bytes, hipMemcpyDeviceToDevice, s));
-    return RDST_OK;
+    return sort_records_by_fields_device(dev_records, len, record_bytes, fields, n_fields, dev_scratch, scratch_bytes, stream, RDST_BYTES_MAX_N, false);
+}
+
+int rdst_hip_sort_records_by_fields_device_nowait(void* dev_records, uint64_t len, uint32_t record_bytes, const rdst_key_field* fields,
+                                                  uint32_t n_fields, void* dev_scratch, uint64_t scratch_bytes, void* stream) {
+    return sort_records_by_fields_device(dev_records, len, record_bytes, fields, n_fields, dev_scratch, scratch_bytes, stream,
+                                         RDST_BYTES_NOWAIT_MAX_N, true);
 }
 
 int rdst_hip_sort_records_by_fields(void* host_records, uint64_t len, uint32_t record_bytes, const rdst_key_field* fields, uint32_t n_fields,

@@ -107,9 +107,21 @@ def sort_bytes_device_tensor(rows, scratch=None, check=True):
     optional uint8 HIP tensor of at least ``rdst_hip_sort_bytes_scratch_bytes(n, N)`` bytes (allocated when omitted).  Runs on
     the tensor's current stream; N > 16 blocks (the tie counts come to the host), N <= 16 stays asynchronous unless
     ``check``."""
+    _sort_bytes_rows("sort_bytes_device_tensor", "rdst_hip_sort_bytes_device", rows, scratch, check)
+
+
+def sort_bytes_device_nowait_tensor(rows, scratch=None, check=True):
+    """``rdst_hip_sort_bytes_device_nowait``: :func:`sort_bytes_device_tensor` without the host in the loop, for N up to
+    ``RDST_BYTES_NOWAIT_MAX_N`` (128); the same arguments, the same scratch size and, bit for bit, the same result.  The
+    call only enqueues work on the tensor's current stream; ``check=False`` makes no blocking call at all (kernel failures
+    then surface in :func:`device_status`)."""
+    _sort_bytes_rows("sort_bytes_device_nowait_tensor", "rdst_hip_sort_bytes_device_nowait", rows, scratch, check)
+
+
+def _sort_bytes_rows(name, entry, rows, scratch, check):
     import torch
     if not rows.is_cuda:
-        raise ValueError("sort_bytes_device_tensor needs a tensor on a HIP device")
+        raise ValueError(f"{name} needs a tensor on a HIP device")
     _check_bytes_rows(tuple(rows.shape), rows.dtype == torch.uint8)
     if not rows.is_contiguous():
         raise ValueError("rows must be a contiguous (n, N) tensor")
@@ -124,8 +136,8 @@ def sort_bytes_device_tensor(rows, scratch=None, check=True):
         raise ValueError(f"scratch must be a contiguous tensor on the rows' device with at least {need} bytes")
     with torch.cuda.device(rows.device):
         s = _stream_handle(rows)
-        _lib.check(lib.rdst_hip_sort_bytes_device(ctypes.c_void_p(rows.data_ptr()), n, n_bytes, ctypes.c_void_p(scratch.data_ptr()),
-                                                  scratch.numel() * scratch.element_size(), s))
+        _lib.check(getattr(lib, entry)(ctypes.c_void_p(rows.data_ptr()), n, n_bytes, ctypes.c_void_p(scratch.data_ptr()),
+                                       scratch.numel() * scratch.element_size(), s))
         if check:
             _lib.check(lib.rdst_hip_device_status(s))
 
@@ -562,9 +574,21 @@ def sort_records_device_tensor(records, fields, scratch=None, check=True):
     ``rdst_hip_sort_records_by_fields_scratch_bytes`` bytes, 256-byte aligned (allocated when omitted).  Runs on the
     tensor's current stream: keys of up to 8 bytes stay asynchronous unless ``check``, longer ones block (the tie counts
     come to the host)."""
+    _sort_records_rows("sort_records_device_tensor", "rdst_hip_sort_records_by_fields_device", records, fields, scratch, check)
+
+
+def sort_records_device_nowait_tensor(records, fields, scratch=None, check=True):
+    """``rdst_hip_sort_records_by_fields_device_nowait``: :func:`sort_records_device_tensor` without the host in the loop,
+    for keys of up to ``RDST_BYTES_NOWAIT_MAX_N`` (128) bytes; the same arguments, the same scratch size and, bit for bit,
+    the same result.  The call only enqueues work on the tensor's current stream; ``check=False`` makes no blocking call
+    at all (kernel failures then surface in :func:`device_status`)."""
+    _sort_records_rows("sort_records_device_nowait_tensor", "rdst_hip_sort_records_by_fields_device_nowait", records, fields, scratch, check)
+
+
+def _sort_records_rows(name, entry, records, fields, scratch, check):
     import torch
     if not records.is_cuda:
-        raise ValueError("sort_records_device_tensor needs a tensor on a HIP device")
+        raise ValueError(f"{name} needs a tensor on a HIP device")
     if records.dim() != 2 or records.dtype != torch.uint8 or not records.is_contiguous():
         raise ValueError("records must be a contiguous (n, R) uint8 tensor, one row per record")
     n, rec_bytes = int(records.shape[0]), int(records.shape[1])
@@ -577,8 +601,8 @@ def sort_records_device_tensor(records, fields, scratch=None, check=True):
         raise ValueError(f"scratch must be a contiguous tensor on the records' device with at least {need} bytes")
     with torch.cuda.device(records.device):
         s = _stream_handle(records)
-        _lib.check(lib.rdst_hip_sort_records_by_fields_device(ctypes.c_void_p(records.data_ptr()), n, rec_bytes, table, nf,
-                                                              ctypes.c_void_p(scratch.data_ptr()), scratch.numel() * scratch.element_size(), s))
+        _lib.check(getattr(lib, entry)(ctypes.c_void_p(records.data_ptr()), n, rec_bytes, table, nf,
+                                       ctypes.c_void_p(scratch.data_ptr()), scratch.numel() * scratch.element_size(), s))
         if check and n > 1:
             _lib.check(lib.rdst_hip_device_status(s))
 

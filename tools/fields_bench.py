@@ -1,6 +1,7 @@
 """Timings of the described-key records route (rdst_key_field tables).  A development aid, not the benchmark.
 
     python tools/fields_bench.py [--rows 10000000] [--reps 5] [--out profiles/fields_bench.json]
+    python tools/fields_bench.py --nowait [--rows 10000000] [--reps 5] [--out FILE]
 
 On --rows records of 32 bytes:
   (a) rdst_hip_sort_records with one f32 field                      host entry, wall clock (the call blocks)
@@ -10,6 +11,9 @@ On --rows records of 32 bytes:
       rdst_hip_stream_copy over as many bytes as the kernel reads and writes, in the same run
 Every case runs once untimed, then --reps times; every sort starts from a fresh copy of the same input (not timed).  The
 yardstick for (b) is (a): the ratio of medians is printed next to the spread (max / min) that (a) shows against itself.
+
+--nowait: case (c) alone, through rdst_hip_sort_records_by_fields_device and rdst_hip_sort_records_by_fields_device_nowait
+in the same process, alternating; both medians and their ratio.
 """
 import argparse
 import ctypes
@@ -33,6 +37,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rows", type=int, default=10_000_000)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--nowait", action="store_true", help="case (c) through the blocking and the nowait entry, alternating")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     import numpy as np
@@ -53,6 +58,61 @@ def main():
     one = [KeyField(0, 4, "float")]
     two = rdst_amd.key_fields_of(dt, ["tenant", "ts"])
     results = {}
+
+    if args.nowait:
+        dev_src = torch.from_numpy(src.view(np.uint8).reshape(n, REC)).cuda()
+        dev = torch.empty_like(dev_src)
+        table2, nf2 = _field_table(two)
+        scratch = torch.empty(int(lib.rdst_hip_sort_records_by_fields_scratch_bytes(n, REC, table2, nf2)), dtype=torch.uint8, device="cuda")
+        start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        entries = {"blocking": rdst_amd.sort_records_device_tensor, "nowait": rdst_amd.sort_records_device_nowait_tensor}
+        ms, out = {k: [] for k in entries}, {}
+        for rep in range(reps + 1):
+            for name, sort in entries.items():
+                dev.copy_(dev_src)
+                torch.cuda.synchronize()
+                start.record()
+                sort(dev, two, scratch=scratch, check=False)
+                stop.record()
+                stop.synchronize()
+                if rep:
+                    ms[name].append(start.elapsed_time(stop))
+                else:
+                    out[name] = dev.clone()
+        rdst_amd.device_status()
+        assert torch.equal(out["blocking"], out["nowait"])
+        # rows whose 8-byte prefix (tenant, the top six bytes of the mapped ts) equals another's: one is enough to raise the flag
+        prefix = np.sort((src["tenant"].astype(np.uint64) << np.uint64(48)) | ((src["ts"].astype(np.int64).view(np.uint64) ^ np.uint64(1 << 63)) >> np.uint64(16)))
+        same = prefix[1:] == prefix[:-1]
+        tied = int(np.count_nonzero(np.concatenate(([False], same)) | np.concatenate((same, [False]))))
+        ratio = round(_stats(ms["nowait"])["ms"] / _stats(ms["blocking"])["ms"], 3)
+        results["c_device_u16_i64"] = {"blocking": _stats(ms["blocking"]), "nowait": _stats(ms["nowait"]), "key_bytes": 10, "rounds": 2,
+                                       "rows_with_a_tied_prefix": tied, "nowait_over_blocking": ratio}
+        if ratio > 1.5:                                    # the pair sorts' stage times, one more run each under rdst_hip_set_profiling
+            for name, sort in entries.items():
+                rdst_amd.set_profiling(True)
+                dev.copy_(dev_src)
+                torch.cuda.synchronize()
+                sort(dev, two, scratch=scratch, check=False)
+                torch.cuda.synchronize()
+                runs = []
+                for r in range(rdst_amd.profile_runs()):
+                    got = rdst_amd.profile_run(r, 0)
+                    by = {}
+                    for stage, _level, t in (got["stages"] if got else ()):
+                        by[stage] = round(by.get(stage, 0.0) + t, 3)
+                    runs.append(by)
+                rdst_amd.set_profiling(False)
+                results["c_device_u16_i64"][name + "_pair_sort_stages_ms"] = runs
+            rdst_amd.device_status()
+        summary = {"tool": "tools/fields_bench.py --nowait", "device": torch.cuda.get_device_name(0), "rows": n, "record_bytes": REC, "reps": reps,
+                   "results": results}
+        print(json.dumps(summary))
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(summary, f, indent=1)
+        return
 
     # (a), (b): alternating, one warm-up each
     work = src.copy()
