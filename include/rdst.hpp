@@ -276,6 +276,29 @@ void sort_segments_device_offsets_nowait(T* dev_keys, V* dev_vals, T* dev_tmp_ke
     if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
 }
 
+// One DEVICE-resident slice whose length lives in device memory too (rdst_hip_sort_device_devlen): the first *dev_len of
+// `capacity` keys are sorted as radix_sort_unstable would sort them, the rest is not touched.  dev_len: one value of the
+// unsigned type Len (std::uint32_t or std::uint64_t), read in stream order — the kernel that counts may still be running —
+// and never by the host.  dev_tmp holds `capacity` keys.  Nothing is copied to the host and nothing waited for; a length
+// past the capacity changes nothing and surfaces in rdst_hip_device_status (error bit 32).  `stream` is a hipStream_t.
+template <typename T, typename Len>
+void sort_device_devlen(T* dev_keys, T* dev_tmp, std::size_t capacity, const Len* dev_len, void* stream = nullptr) {
+    static_assert(std::is_unsigned<Len>::value && (sizeof(Len) == 4 || sizeof(Len) == 8), "the length is a 4- or 8-byte unsigned integer");
+    const int rc = rdst_hip_sort_device_devlen(dev_keys, dev_tmp, capacity, dev_len, sizeof(Len), sizeof(T), RadixKey<T>::kind,
+                                               static_cast<std::uint32_t>(RadixKey<T>::LEVELS), stream);
+    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+}
+// Key-value form (rdst_hip_sort_pairs_device_devlen): 4- or 8-byte keys and values; equal keys keep their order.
+template <typename T, typename V, typename Len>
+void sort_pairs_device_devlen(T* dev_keys, V* dev_vals, T* dev_tmp_keys, V* dev_tmp_vals, std::size_t capacity, const Len* dev_len,
+                              void* stream = nullptr) {
+    static_assert(std::is_unsigned<Len>::value && (sizeof(Len) == 4 || sizeof(Len) == 8), "the length is a 4- or 8-byte unsigned integer");
+    static_assert(std::is_trivially_copyable<V>::value, "values are moved as bytes");
+    const int rc = rdst_hip_sort_pairs_device_devlen(dev_keys, dev_vals, dev_tmp_keys, dev_tmp_vals, capacity, dev_len, sizeof(Len), sizeof(T),
+                                                     RadixKey<T>::kind, static_cast<std::uint32_t>(RadixKey<T>::LEVELS), sizeof(V), stream);
+    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+}
+
 // DEVICE-resident [u8; N] rows (src/radix_key_impl.rs:78-85) and DEVICE-resident structs ordered by a described key
 // (src/radix_key.rs; examples/impl_radix_key.rs:32-56), in place and with no host involvement
 // (rdst_hip_sort_bytes_device_nowait, rdst_hip_sort_records_by_fields_device_nowait): N, or the sum of the fields' widths,

@@ -173,6 +173,36 @@ int rdst_hip_sort_pairs_device(void* dev_keys, void* dev_vals, void* dev_tmp_key
                                uint64_t len, uint32_t key_bytes, rdst_key_kind kind, uint32_t levels,
                                uint32_t val_bytes, void* stream);
 
+/* The same two sorts over a prefix whose LENGTH LIVES IN DEVICE MEMORY: the count a compaction, a filter or a join left
+ * there, sorted without the host ever learning it.  `dev_len` points to one unsigned integer of `len_bytes` (4 or 8) bytes
+ * in device memory, aligned to its size; call its value m.  It is read only, and read IN STREAM ORDER: the kernel that
+ * writes it may still be running when the call returns.  The host never reads it.
+ *   - The first m elements end up bit for bit as rdst_hip_sort_device / rdst_hip_sort_pairs_device would leave a slice of
+ *     len = m; pairs with equal keys keep their input order.  Elements [m, capacity) of keys and values are not written.
+ *     Of the tmp arrays (both hold `capacity` elements) only [0, m) may be written, their content afterwards is
+ *     unspecified.  Nothing outside [0, capacity) of any array is touched.  m <= 1 changes nothing.
+ *   - m > capacity: no key, value or tmp element is modified, bit 32 (0x20) of the device error word is set and
+ *     rdst_hip_device_status returns RDST_ERR_DEVICE once.
+ *   - Key widths, kinds, `levels`, alignment rules, argument errors and their order: those of the known-length twins, with
+ *     `capacity` in the place of `len`.  Then, still before any device work: NULL dev_len -> RDST_ERR_ARG, len_bytes not 4
+ *     or 8 -> RDST_ERR_ARG, misaligned dev_len -> RDST_ERR_ALIGN.  capacity <= 1 is RDST_OK and does nothing; dev_len is
+ *     not looked at.
+ *   - ASYNCHRONOUS on `stream` for every capacity: no copy to the host, no stream or event wait (the one exception every
+ *     entry shares: a library workspace that has to grow).
+ *   - The LSD route only (rdst_hip_last_route reports it): the byte-saving routes and the split beyond the window size their
+ *     launches from the length on the host, and the split reads counts back.  A keys-only sort of 4- or 8-byte keys
+ *     therefore runs at the LSD rate, not at rdst_hip_sort_device's; key-value sorts take this route in either form.
+ *     Every launch is sized for `capacity` and returns early past m, so a short prefix of a large capacity still pays
+ *     for the capacity's launches (DESIGN.md §2g has the measured floor).  Level skipping and the whole-slice
+ *     already-sorted exit work as in the twins, decided by the first m elements only. */
+int rdst_hip_sort_device_devlen(void* dev_keys, void* dev_tmp, uint64_t capacity,
+                                const void* dev_len, uint32_t len_bytes,
+                                uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels, void* stream);
+int rdst_hip_sort_pairs_device_devlen(void* dev_keys, void* dev_vals, void* dev_tmp_keys, void* dev_tmp_vals,
+                                      uint64_t capacity, const void* dev_len, uint32_t len_bytes,
+                                      uint32_t key_bytes, rdst_key_kind kind, uint32_t levels,
+                                      uint32_t val_bytes, void* stream);
+
 /* ---- many independent slices in one call ---------------------------------------------------------
  * The reference sorts the 256 buckets of a chunk as slices of their own, in parallel (src/sorter.rs:131-138), and a
  * caller may do the same with `chunks_mut(..).par_for_each(|c| c.radix_sort_unstable())`.  The device form: one array

@@ -39,6 +39,8 @@ from .radix_sort import (  # noqa: F401
     segments_plan_device,
     segments_device_offsets_scratch_bytes,
     sort_pairs_device_tensor,
+    sort_device_devlen_tensor,
+    sort_pairs_device_devlen_tensor,
     sort_segments_device_tensor,
     sort_segments_device_offsets_tensor,
     sort_segments_device_offsets_nowait_tensor,
@@ -57,4 +59,5 @@ __all__ = [
     "sort_segments_device_offsets_tensor", "sort_segments_device_offsets_nowait_tensor", "segments_nowait_scratch_bytes", "segments_device_offsets_scratch_bytes", "segments_plan_device", "sort_records_by_key", "level_counts", "all_level_counts", "scatter_level",
     "device_status", "set_tuning", "set_profiling", "set_hybrid", "last_route", "last_sample", "release_workspace", "last_profile", "key_info",
     "KeyField", "key_fields_of", "sort_records_device_tensor", "sort_bytes_device_nowait_tensor", "sort_records_device_nowait_tensor",
+    "sort_device_devlen_tensor", "sort_pairs_device_devlen_tensor",
 ]

@@ -29,6 +29,8 @@ SYMBOLS = (
     "rdst_regions_plan",
     "rdst_hip_host_timing",
     "rdst_hip_sort_pairs_device",
+    "rdst_hip_sort_device_devlen",
+    "rdst_hip_sort_pairs_device_devlen",
     "rdst_hip_sort_segments_device",
     "rdst_hip_sort_segments_pairs_device",
     "rdst_hip_sort_segments_limits",
@@ -133,6 +135,8 @@ def load():
     lib.rdst_hip_partition_device.argtypes = [vp, u64, u32, ci, u32, u32, vp, u64, u64p, vp]
     lib.rdst_hip_sort_device.argtypes = [vp, vp, u64, u32, ci, u32, vp]
     lib.rdst_hip_sort_pairs_device.argtypes = [vp, vp, vp, vp, u64, u32, ci, u32, u32, vp]
+    lib.rdst_hip_sort_device_devlen.argtypes = [vp, vp, u64, vp, u32, u32, ci, u32, vp]
+    lib.rdst_hip_sort_pairs_device_devlen.argtypes = [vp, vp, vp, vp, u64, vp, u32, u32, ci, u32, u32, vp]
     lib.rdst_hip_sort_segments_device.argtypes = [vp, vp, u64, u64, u64p, u64, u32, ci, u32, vp]
     lib.rdst_hip_sort_segments_pairs_device.argtypes = [vp, vp, vp, vp, u64, u64, u64p, u64, u32, ci, u32, u32, vp]
     lib.rdst_hip_sort_segments_limits.argtypes = [u32, u32, ctypes.POINTER(u32)]

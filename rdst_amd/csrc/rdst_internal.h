@@ -149,6 +149,13 @@ void key_xor_masks(rdst_key_kind kind, uint32_t elem_bytes, unsigned __int128* n
 int sort_slice_locked(void* keys, void* tmp, uint64_t n, uint32_t elem_bytes, rdst_key_kind kind, hipStream_t s);
 int sort_pairs_slice_locked(void* keys, void* vals, void* tmp_keys, void* tmp_vals, uint64_t n, uint32_t key_bytes, rdst_key_kind kind,
                             uint32_t val_bytes, hipStream_t s);
+// The same with the length in device memory (rdst_hip_sort_device_devlen / rdst_hip_sort_pairs_device_devlen after their
+// checks): `dev_len` is one unsigned integer of `len_bytes` (4 or 8) bytes, read on `s`; launches and workspace are sized
+// for `capacity` (> 1).  The LSD route only; no copy to the host, no wait.
+int sort_slice_devlen_locked(void* keys, void* tmp, uint64_t capacity, const void* dev_len, uint32_t len_bytes, uint32_t elem_bytes,
+                             rdst_key_kind kind, hipStream_t s);
+int sort_pairs_slice_devlen_locked(void* keys, void* vals, void* tmp_keys, void* tmp_vals, uint64_t capacity, const void* dev_len, uint32_t len_bytes,
+                                   uint32_t key_bytes, rdst_key_kind kind, uint32_t val_bytes, hipStream_t s);
 // Bytes of workspace such a slice asks for (an upper bound over its routes).
 size_t slice_workspace_bytes(uint64_t n, uint32_t key_bytes, rdst_key_kind kind, uint32_t val_bytes);
 // The current device's workspace, grown to `bytes` if need be and handed over to stream `s` (workspace_acquire); every

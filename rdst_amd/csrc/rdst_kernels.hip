@@ -78,6 +78,7 @@ constexpr uint32_t RDST_FAST_RANK_SELFTEST = 1u << 17;  // treat every round of 
 constexpr uint32_t ERR_LOOKBACK_TIMEOUT = 1;
 constexpr uint32_t ERR_SCATTER_RANGE = 2;  // a computed destination fell outside [0, n): never stored
 constexpr uint32_t ERR_LOCAL_OVERFLOW = 4;  // a bucket larger than the K4 kernel it reached can take (the routes' own tests rule it out): never sorted
+constexpr uint32_t ERR_LEN_PAST_CAPACITY = 32;  // a device-resident length (the _devlen entries) beyond the capacity: nothing is sorted (8, 16: rdst_bytes.hip, rdst_segments.hip)
 
 // Three routes through the kernels, chosen ON THE DEVICE from a sample and the counts of the key multiset — the device
 // form of Tuner::pick_algorithm(params, counts) (src/tuner.rs:33-35, src/sorter.rs:67-76).  Tried in this order; the
@@ -269,8 +270,22 @@ struct HistPlan {
     static_assert(WORDS <= 32768, "K1 LDS budget");
 };
 
-template <typename K, int LEVELS, int VEC, bool PAIR>
-__global__ __launch_bounds__(HIST_THREADS) void hist_kernel(const K* __restrict__ keys, uint64_t n, K neg, K pos,
+// K1's length argument.  A plain uint64_t: the slice's length, known to the host.  DevLen (a device-length pipeline,
+// DESIGN.md §2g): the host knows the CAPACITY only — it sizes the grid and cuts the pieces, so that K1's position ranges
+// and K2's CHAIN_POS borders (hist_first_block * hist_piece) stay the same numbers — and the number of keys to read and
+// count is in device memory (the header word devlen_head_kernel writes).  It is the same for every block: each clamps its
+// piece to it, and whole waves still enter and leave the batched loop together.
+struct DevLen {
+    uint64_t capacity;
+    const uint64_t* eff_len;
+};
+__device__ __forceinline__ uint64_t hist_len_cut(uint64_t n) { return n; }       // what the pieces are cut from
+__device__ __forceinline__ uint64_t hist_len_counted(uint64_t n) { return n; }   // how many keys there are
+__device__ __forceinline__ uint64_t hist_len_cut(const DevLen& n) { return n.capacity; }
+__device__ __forceinline__ uint64_t hist_len_counted(const DevLen& n) { return *n.eff_len; }
+
+template <typename K, int LEVELS, int VEC, bool PAIR, typename N = uint64_t>
+__global__ __launch_bounds__(HIST_THREADS) void hist_kernel(const K* __restrict__ keys, N n_arg /* uint64_t or DevLen */, K neg, K pos,
                                                             unsigned long long* __restrict__ hpos /* [LEVELS][CHAINS][256]: counts per position range */,
                                                             unsigned long long* __restrict__ hpair /* [LEVELS][CHAINS][256]: counts per group of the previous digit (PAIR) */,
                                                             uint32_t* __restrict__ inversion /* set if keys[i-1] > keys[i] anywhere */,
@@ -286,10 +301,11 @@ __global__ __launch_bounds__(HIST_THREADS) void hist_kernel(const K* __restrict_
     __syncthreads();
 
     constexpr uint64_t GRAN = (uint64_t)HIST_THREADS * VEC * 4;  // one unrolled sweep of the block
-    const uint64_t piece = hist_piece(n, gridDim.x, GRAN);
+    const uint64_t piece = hist_piece(hist_len_cut(n_arg), gridDim.x, GRAN);
     const uint64_t p_begin = (uint64_t)blockIdx.x * piece;
     uint64_t p_end = p_begin + piece;
-    if (p_end > n) p_end = n;
+    const uint64_t n = hist_len_counted(n_arg);
+    if (p_end > n) p_end = n;  // (a piece that begins past the end: neither loop below runs)
     uint32_t* mine = s_h + (tid & (COPIES - 1));                    // my bank column, plain tables
     uint32_t* mine_p = s_h + P::PAIR_BASE + (tid & (PCOPIES - 1));  // and of the joint tables
 
@@ -406,6 +422,24 @@ __global__ __launch_bounds__(HIST_THREADS) void hist_kernel(const K* __restrict_
         }
         if (c) atomicAdd(&hpos[((size_t)(l + base_level) * CHAINS + range) * RADIX + d], (unsigned long long)c);
     }
+}
+
+// ------------------------------------------------------------------------------------------
+// The pipeline with its length in device memory (rdst_hip_sort_device_devlen / _pairs_device_devlen).  The
+// host sizes every launch, the pieces of K1 and the workspace for the CAPACITY; one block behind the workspace clear reads
+// the length m, checks it against the capacity and leaves the effective length in the header (HDR_EFF_LEN), where K1 (its
+// DevLen form) and the _devlen forms of K2 and the copy-back find it.  K3 needs no such form: its tiles come from K2's
+// chain tables.
+// ------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void devlen_head_kernel(const void* __restrict__ dev_len, uint32_t len_bytes, uint64_t capacity,
+                                                         uint64_t* __restrict__ eff_len, uint32_t* __restrict__ err) {
+    if (threadIdx.x != 0) return;
+    uint64_t m = len_bytes == 4 ? (uint64_t)*static_cast<const uint32_t*>(dev_len) : *static_cast<const uint64_t*>(dev_len);
+    if (m > capacity) {  // nothing is sorted: every later kernel sees an empty slice
+        atomicOr(err, ERR_LEN_PAST_CAPACITY);
+        m = 0;
+    }
+    *eff_len = m;
 }
 
 // ------------------------------------------------------------------------------------------
@@ -983,7 +1017,7 @@ struct ScanArgs {
 
 constexpr int SCAN_GROUPS = 4;  // levels handled side by side, 256 threads (one per digit) each
 
-__global__ __launch_bounds__(256 * SCAN_GROUPS) void scan_kernel(ScanArgs a) {
+__device__ __forceinline__ void scan_body(const ScanArgs& a) {
     __shared__ uint64_t s_wave_sum[SCAN_GROUPS][4];
     __shared__ uint32_t s_trivial[MAX_LEVELS];
     __shared__ uint32_t s_mode[MAX_LEVELS], s_skip[MAX_LEVELS];
@@ -1101,6 +1135,15 @@ __global__ __launch_bounds__(256 * SCAN_GROUPS) void scan_kernel(ScanArgs a) {
         }
         __syncthreads();
     }
+}
+
+__global__ __launch_bounds__(256 * SCAN_GROUPS) void scan_kernel(ScanArgs a) { scan_body(a); }
+
+// K2 of a device-length pipeline: the length from the header stands wherever `n` stands — the trivial-level test, the
+// segment ends, the CHAINS-th border.  a.hist_piece and a.hist_grid stay the capacity's, as K1's pieces are.
+__global__ __launch_bounds__(256 * SCAN_GROUPS) void scan_devlen_kernel(ScanArgs a, const uint64_t* __restrict__ eff_len) {
+    a.n = *eff_len;
+    scan_body(a);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -4085,9 +4128,7 @@ __global__ __launch_bounds__(WIDE3_THREADS, 8) void local_wide3_sort_kernel(
 // (src/sorts/lsb_sort.rs:117-126)
 // (want_tmp: the other way round — `keys` is the caller's tmp, `tmp` its keys, and the copy runs when the result is NOT in tmp)
 template <typename K, int VEC>
-__global__ __launch_bounds__(256) void copyback_kernel(K* __restrict__ keys, const K* __restrict__ tmp,
-                                                       uint64_t n, const Plan* __restrict__ plan, uint32_t want_tmp) {
-    if ((plan->result_in_tmp != 0u) == (want_tmp != 0u)) return;
+__device__ __forceinline__ void copyback_body(K* __restrict__ keys, const K* __restrict__ tmp, uint64_t n) {
     struct alignas(sizeof(K) * VEC) V { K e[VEC]; };
     const uint64_t nvec = n / VEC;
     const uint64_t stride = (uint64_t)gridDim.x * 256;
@@ -4097,6 +4138,19 @@ __global__ __launch_bounds__(256) void copyback_kernel(K* __restrict__ keys, con
         const uint64_t i = nvec * VEC + threadIdx.x;
         if (i < n) keys[i] = tmp[i];
     }
+}
+template <typename K, int VEC>
+__global__ __launch_bounds__(256) void copyback_kernel(K* __restrict__ keys, const K* __restrict__ tmp,
+                                                       uint64_t n, const Plan* __restrict__ plan, uint32_t want_tmp) {
+    if ((plan->result_in_tmp != 0u) == (want_tmp != 0u)) return;
+    copyback_body<K, VEC>(keys, tmp, n);
+}
+// the copy-back of a device-length pipeline: the first *eff_len elements only (the grid is sized for the capacity)
+template <typename K, int VEC>
+__global__ __launch_bounds__(256) void copyback_devlen_kernel(K* __restrict__ keys, const K* __restrict__ tmp,
+                                                              const uint64_t* __restrict__ eff_len, const Plan* __restrict__ plan) {
+    if (plan->result_in_tmp == 0u) return;
+    copyback_body<K, VEC>(keys, tmp, *eff_len);
 }
 
 // [u8; N] keys (src/radix_key_impl.rs:78-85: level l reads byte N-1-l, i.e. lexicographic order): the
@@ -4625,6 +4679,7 @@ enum HeaderWord : uint32_t {
     HDR_FBLIST_LEN = 3,    // length of K4's first hand-on list (fblist)
     HDR_MSD_OVERFLOW = 4,  // an area or a slot of the atomic route overflowed
     HDR_FBLIST2_LEN = 5,   // length of K4's second list (fblist2)
+    HDR_EFF_LEN = 8,       // words 8 and 9, one uint64_t: the effective length of a device-length pipeline (devlen_head_kernel)
 };
 
 // The workspace of one pipeline as typed pointers: the only place that casts ws + Layout::off_*
@@ -4638,6 +4693,7 @@ struct WsView {
     uint32_t *glist, *gcount_item, *gexp_item, *gtables;  // giants of the hybrid route: buckets, first counting / expanding item, count tables
     GiantItem* gsplit;
     uint64_t* base;
+    uint64_t* eff_len;  // device-length pipelines: how many keys there are (written behind the clear, read by K1, K2 and the copy-back)
 
     WsView() = default;
     WsView(char* ws_, const Layout& L_) : ws(ws_), L(L_) {
@@ -4646,6 +4702,7 @@ struct WsView {
         fblist_len = at<uint32_t>(L.off_err) + HDR_FBLIST_LEN;
         msd_overflow = at<uint32_t>(L.off_err) + HDR_MSD_OVERFLOW;
         fblist2_len = at<uint32_t>(L.off_err) + HDR_FBLIST2_LEN;
+        eff_len = reinterpret_cast<uint64_t*>(at<uint32_t>(L.off_err) + HDR_EFF_LEN);
         plan = at<Plan>(L.off_plan);
         hpos = at<unsigned long long>(L.off_hpos);
         hpair = at<unsigned long long>(L.off_hpair);
@@ -4703,6 +4760,10 @@ struct Pipe {
     WsView w;
     uint32_t blocks = 0;  // K1's grid; K1h and the exact pass A cut the slice the same way
     bool pair = false;    // K1 also fills the joint tables of the chain split
+    // a device-length pipeline (non-null): `n` is the capacity — what every launch, K1's pieces and the workspace are sized
+    // for — and the length is one unsigned integer of len_bytes bytes in device memory, read on the stream
+    const void* dev_len = nullptr;
+    uint32_t len_bytes = 0;
 };
 
 template <int LEVELS, typename K, typename V>
@@ -4711,6 +4772,10 @@ int launch_hist(const Pipe<K, V>& p, bool pair, const Plan* plan, uint64_t* piec
         constexpr int VEC = vec_for<K>(ALIGNED);
         constexpr size_t lds = (size_t)HistPlan<LEVELS, PAIR>::WORDS * sizeof(uint32_t);
         *piece_out = hist_piece(p.n, p.blocks, (uint64_t)HIST_THREADS * VEC * 4);
+        if constexpr (LEVELS == (int)sizeof(K))  // (whole sorts only: run_pipeline)
+            if (p.dev_len)
+                return launch("hist_kernel (device length)", hist_kernel<K, LEVELS, VEC, PAIR, DevLen>, dim3(p.blocks), dim3(HIST_THREADS), lds, p.s, p.keys,
+                              DevLen{p.n, p.w.eff_len}, (K)p.km.neg, (K)p.km.pos, p.w.hpos, p.w.hpair, p.w.inversion, plan, base_level);
         return launch("hist_kernel", hist_kernel<K, LEVELS, VEC, PAIR>, dim3(p.blocks), dim3(HIST_THREADS), lds, p.s, p.keys, p.n, (K)p.km.neg,
                       (K)p.km.pos, p.w.hpos, p.w.hpair, p.w.inversion, plan, base_level);
     };
@@ -4956,7 +5021,7 @@ template <int LEVELS, typename K, typename V>
 int pick_workspace(Pipe<K, V>& p, rdst_key_kind kind) {
     int cfg = g_tuning.pass_cfg;
     if (cfg < 0 || cfg >= kNumPassCfgs) cfg = default_cfg(sizeof(K), p.n, kind != RDST_KEY_UNSIGNED);
-    p.rp = pick_routes<LEVELS>(p, cfg, false);
+    p.rp = pick_routes<LEVELS>(p, cfg, p.dev_len != nullptr);  // (a device-length pipeline: the LSD route only)
     if (p.rp.L.tiles >= (1ull << 31)) return fail(RDST_ERR_ARG, "len too large for one launch");
     int rc = ensure_workspace(*p.D, p.rp.L.total);
     if (rc && (p.rp.try_atomic || p.rp.try_hybrid)) {  // no room for the areas and slots: the LSD route needs an eighth of the slice
@@ -4997,6 +5062,8 @@ int clear_workspace(Pipe<K, V>& p) {
             RDST_HIP_TRY(hipMemsetAsync(ws + status_lo + (L.off_status_near - L.off_status), 0, status_hi - status_lo, s));
         }
     }
+    if (p.dev_len)  // (shares the clear's stage)
+        if ((rc = launch("devlen_head_kernel", devlen_head_kernel, dim3(1), dim3(64), 0, s, p.dev_len, p.len_bytes, p.n, p.w.eff_len, D.err_dev))) return rc;
     return prof_mark(D, s, RDST_STAGE_CLEAR);
 }
 
@@ -5178,7 +5245,9 @@ int count_and_scan(const Pipe<K, V>& p) {
     sa.use_chains = g_tuning.chains ? 1u : 0u;
     sa.halves = p.rp.halves ? 1u : 0u;
     sa.deliver_tmp = p.deliver_tmp ? 1u : 0u;
-    if ((rc = launch("scan_kernel", scan_kernel, dim3(1), dim3(256 * SCAN_GROUPS), 0, p.s, sa))) return rc;
+    if (p.dev_len) rc = launch("scan_devlen_kernel", scan_devlen_kernel, dim3(1), dim3(256 * SCAN_GROUPS), 0, p.s, sa, static_cast<const uint64_t*>(p.w.eff_len));
+    else rc = launch("scan_kernel", scan_kernel, dim3(1), dim3(256 * SCAN_GROUPS), 0, p.s, sa);
+    if (rc) return rc;
     return prof_mark(*p.D, p.s, RDST_STAGE_SCAN);
 }
 
@@ -5194,23 +5263,27 @@ int pass_loop(const Pipe<K, V>& p) {
     return RDST_OK;
 }
 
+// eff_len (non-null: a device-length pipeline): copy the first *eff_len elements, with the grid `n` (the capacity) asks for
 template <typename T>
-int launch_copyback(T* dst, const T* src, uint64_t n, const Plan* plan, uint32_t deliver_tmp, int cus, hipStream_t s) {
+int launch_copyback(T* dst, const T* src, uint64_t n, const Plan* plan, uint32_t deliver_tmp, int cus, hipStream_t s, const uint64_t* eff_len = nullptr) {
     uint64_t blocks = (n * sizeof(T) / 16 + 255) / 256;
     if (blocks > (uint64_t)cus * 16) blocks = (uint64_t)cus * 16;
     if (blocks < 1) blocks = 1;
     return with_bools([&](auto ALIGNED) {
+        if (eff_len)
+            return launch("copyback_devlen_kernel", copyback_devlen_kernel<T, vec_for<T>(ALIGNED)>, dim3((uint32_t)blocks), dim3(256), 0, s, dst, src, eff_len, plan);
         return launch("copyback_kernel", copyback_kernel<T, vec_for<T>(ALIGNED)>, dim3((uint32_t)blocks), dim3(256), 0, s, dst, src, n, plan, deliver_tmp);
     }, aligned16(dst, src));
 }
 
 template <typename K, typename V>
 int copy_back_stage(const Pipe<K, V>& p) {
+    const uint64_t* eff_len = p.dev_len ? p.w.eff_len : nullptr;  // (deliver_tmp and a device length exclude each other: run_pipeline)
     int rc = p.deliver_tmp ? launch_copyback<K>(p.tmp, p.keys, p.n, p.w.plan, 1u, p.D->cus, p.s)
-                           : launch_copyback<K>(p.keys, p.tmp, p.n, p.w.plan, 0u, p.D->cus, p.s);
+                           : launch_copyback<K>(p.keys, p.tmp, p.n, p.w.plan, 0u, p.D->cus, p.s, eff_len);
     if (rc) return rc;
     if constexpr (ValBytes<V>::value != 0) {
-        if ((rc = launch_copyback<V>(p.vals, p.vtmp, p.n, p.w.plan, 0u, p.D->cus, p.s))) return rc;
+        if ((rc = launch_copyback<V>(p.vals, p.vtmp, p.n, p.w.plan, 0u, p.D->cus, p.s, eff_len))) return rc;
     }
     return prof_mark(*p.D, p.s, RDST_STAGE_COPYBACK);
 }
@@ -5221,20 +5294,25 @@ int copy_back_stage(const Pipe<K, V>& p) {
 template <typename K, int LEVELS, typename V = NoVal>
 int run_pipeline(K* keys, K* tmp, uint64_t n, rdst_key_kind kind, uint32_t level_lo, uint32_t level_hi,
                  bool allow_skip, bool copy_back, hipStream_t s, Layout* layout_out, char** ws_out, V* vals = nullptr,
-                 V* vtmp = nullptr, bool deliver_tmp = false /* whole key-only sorts: leave the result in tmp, not in keys */) {
+                 V* vtmp = nullptr, bool deliver_tmp = false /* whole key-only sorts: leave the result in tmp, not in keys */,
+                 const void* dev_len = nullptr /* a device-length pipeline: `n` is the capacity (whole sorts with copy-back only) */, uint32_t len_bytes = 0) {
     constexpr bool HAS_V = ValBytes<V>::value != 0;
     constexpr bool ROUTED = !HAS_V && (sizeof(K) == 4 || sizeof(K) == 8);  // the widths the atomic and the hybrid route are built for
     if (deliver_tmp && (HAS_V || !copy_back)) return fail(RDST_ERR_ARG, "deliver_tmp: whole key-only sorts");
+    if (dev_len && (level_lo != 0 || level_hi != (uint32_t)LEVELS || !allow_skip || !copy_back || deliver_tmp || layout_out))
+        return fail(RDST_ERR_ARG, "a device-resident length: whole sorts only");
     DeviceState* D;
     int rc = current_device_state(&D);
     if (rc) return rc;
     if constexpr (!HAS_V) {
         if (g_tuning.small_sort && level_lo == 0 && level_hi == (uint32_t)LEVELS && allow_skip && copy_back && !layout_out && !deliver_tmp &&
-            n <= (uint64_t)SMALL_THREADS * small_kpt(sizeof(K)))
+            !dev_len /* (the one-workgroup sort is chosen from a length the host knows: DESIGN.md §2g) */ && n <= (uint64_t)SMALL_THREADS * small_kpt(sizeof(K)))
             return run_small_sort<K, LEVELS>(*D, keys, n, kind, s);
     }
     const KeyMap km = key_map_for(kind, sizeof(K));
     Pipe<K, V> p{D, s, keys, tmp, vals, vtmp, n, level_lo, level_hi, allow_skip, copy_back, deliver_tmp, km, km.neg != 0 || km.pos != 0};
+    p.dev_len = dev_len;
+    p.len_bytes = len_bytes;
     if ((rc = pick_workspace<LEVELS>(p, kind))) return rc;
     if ((rc = clear_workspace<LEVELS>(p))) return rc;
     p.blocks = hist_blocks<K>(n, D->cus);
@@ -5540,7 +5618,7 @@ int read_device_error(DeviceState& D, hipStream_t s) {
         RDST_HIP_TRY(hipMemsetAsync(D.err_dev, 0, sizeof(uint32_t), s));  // reported once: the next check starts clean
         RDST_HIP_TRY(hipStreamSynchronize(s));
         char b[448];
-        snprintf(b, sizeof b, "device error word = 0x%x (1 = look-back spin bound expired, 2 = scatter destination out of range, 4 = hybrid-route bucket larger than a tile, 8 = [u8; N] route: a row index or run out of range, 16 = segmented sort: offsets table decreasing, past len, or a segment beyond block_max without tmp)", word);
+        snprintf(b, sizeof b, "device error word = 0x%x (1 = look-back spin bound expired, 2 = scatter destination out of range, 4 = hybrid-route bucket larger than a tile, 8 = [u8; N] route: a row index or run out of range, 16 = segmented sort: offsets table decreasing, past len, or a segment beyond block_max without tmp, 32 = device-length sort: the length read from device memory is past the capacity)", word);
         return fail(RDST_ERR_DEVICE, b);
     }
     return RDST_OK;
@@ -5832,9 +5910,80 @@ int sort_pairs_slice_locked(void* keys, void* vals, void* tmp_keys, void* tmp_va
         });
     });
 }
+
+// The same two with the length in device memory: the LSD pipeline sized for `capacity`, the length read on the stream.
+int sort_slice_devlen_locked(void* keys, void* tmp, uint64_t capacity, const void* dev_len, uint32_t len_bytes, uint32_t elem_bytes,
+                             rdst_key_kind kind, hipStream_t s) {
+    int rc = RDST_OK;
+    RDST_BY_WIDTH(elem_bytes, rc = (run_pipeline<K, LV, NoVal>(static_cast<K*>(keys), static_cast<K*>(tmp), capacity, kind, 0, LV, true, true, s, nullptr,
+                                                               nullptr, nullptr, nullptr, false, dev_len, len_bytes)));
+    return rc;
+}
+
+int sort_pairs_slice_devlen_locked(void* keys, void* vals, void* tmp_keys, void* tmp_vals, uint64_t capacity, const void* dev_len, uint32_t len_bytes,
+                                   uint32_t key_bytes, rdst_key_kind kind, uint32_t val_bytes, hipStream_t s) {
+    return by_uint(key_bytes, [&](auto k) {
+        return by_uint(val_bytes, [&](auto v) {
+            using KT = decltype(k);
+            using VT = decltype(v);
+            return run_pipeline<KT, (int)sizeof(KT), VT>(static_cast<KT*>(keys), static_cast<KT*>(tmp_keys), capacity, kind, 0, sizeof(KT), true, true, s,
+                                                         nullptr, nullptr, static_cast<VT*>(vals), static_cast<VT*>(tmp_vals), false, dev_len, len_bytes);
+        });
+    });
+}
 }  // namespace rdst_internal
 
+namespace {
+// The argument checks of the key-value entries, in their order.  *nothing_to_do: a slice of at most one pair, for which no
+// pointer but the keys' is looked at.
+int check_pair_args(const void* dev_keys, const void* dev_vals, const void* dev_tmp_keys, const void* dev_tmp_vals, uint64_t len, uint32_t key_bytes,
+                    rdst_key_kind kind, uint32_t levels, uint32_t val_bytes, bool* nothing_to_do) {
+    const int rc = check_common(dev_keys, len, key_bytes, kind, levels);
+    if (rc) return rc;
+    if (key_bytes != 4 && key_bytes != 8) return fail(RDST_ERR_UNSUPPORTED, "key-value sorts take 4- or 8-byte keys");
+    if (val_bytes != 4 && val_bytes != 8) return fail(RDST_ERR_UNSUPPORTED, "key-value sorts carry 4- or 8-byte values");
+    *nothing_to_do = len <= 1;
+    if (*nothing_to_do) return RDST_OK;
+    if (!dev_vals || !dev_tmp_keys || !dev_tmp_vals) return fail(RDST_ERR_ARG, "null value / tmp pointer");
+    if (reinterpret_cast<uintptr_t>(dev_tmp_keys) % key_bytes) return fail(RDST_ERR_ALIGN, "tmp key pointer not aligned to the key size");
+    if ((reinterpret_cast<uintptr_t>(dev_vals) | reinterpret_cast<uintptr_t>(dev_tmp_vals)) % val_bytes)
+        return fail(RDST_ERR_ALIGN, "value pointer not aligned to the value size");
+    return RDST_OK;
+}
+
+// the length argument of the _devlen entries: one unsigned integer of 4 or 8 bytes in device memory (never read here)
+int check_dev_len(const void* dev_len, uint32_t len_bytes) {
+    if (dev_len == nullptr) return fail(RDST_ERR_ARG, "null length pointer");
+    if (len_bytes != 4 && len_bytes != 8) return fail(RDST_ERR_ARG, "the device-resident length is a 4- or 8-byte unsigned integer");
+    if (reinterpret_cast<uintptr_t>(dev_len) % len_bytes) return fail(RDST_ERR_ALIGN, "length pointer not aligned to its size");
+    return RDST_OK;
+}
+}  // namespace
+
 extern "C" {
+
+int rdst_hip_sort_device_devlen(void* dev_keys, void* dev_tmp, uint64_t capacity, const void* dev_len, uint32_t len_bytes,
+                                uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels, void* stream) {
+    int rc = check_common(dev_keys, capacity, elem_bytes, kind, levels);
+    if (rc) return rc;
+    if (capacity <= 1) return RDST_OK;
+    if ((rc = check_second_buffer(dev_tmp, elem_bytes, false))) return rc;
+    if ((rc = check_dev_len(dev_len, len_bytes))) return rc;
+    std::lock_guard<std::mutex> lock(g_mutex);
+    return rdst_internal::sort_slice_devlen_locked(dev_keys, dev_tmp, capacity, dev_len, len_bytes, elem_bytes, kind, static_cast<hipStream_t>(stream));
+}
+
+int rdst_hip_sort_pairs_device_devlen(void* dev_keys, void* dev_vals, void* dev_tmp_keys, void* dev_tmp_vals, uint64_t capacity,
+                                      const void* dev_len, uint32_t len_bytes, uint32_t key_bytes, rdst_key_kind kind, uint32_t levels,
+                                      uint32_t val_bytes, void* stream) {
+    bool nothing_to_do = false;
+    int rc = check_pair_args(dev_keys, dev_vals, dev_tmp_keys, dev_tmp_vals, capacity, key_bytes, kind, levels, val_bytes, &nothing_to_do);
+    if (rc || nothing_to_do) return rc;
+    if ((rc = check_dev_len(dev_len, len_bytes))) return rc;
+    std::lock_guard<std::mutex> lock(g_mutex);
+    return rdst_internal::sort_pairs_slice_devlen_locked(dev_keys, dev_vals, dev_tmp_keys, dev_tmp_vals, capacity, dev_len, len_bytes, key_bytes, kind,
+                                                         val_bytes, static_cast<hipStream_t>(stream));
+}
 
 int rdst_hip_sort_device(void* dev_keys, void* dev_tmp, uint64_t len, uint32_t elem_bytes, rdst_key_kind kind,
                          uint32_t levels, void* stream) {
@@ -5848,15 +5997,9 @@ int rdst_hip_sort_device(void* dev_keys, void* dev_tmp, uint64_t len, uint32_t e
 
 int rdst_hip_sort_pairs_device(void* dev_keys, void* dev_vals, void* dev_tmp_keys, void* dev_tmp_vals, uint64_t len,
                                uint32_t key_bytes, rdst_key_kind kind, uint32_t levels, uint32_t val_bytes, void* stream) {
-    int rc = check_common(dev_keys, len, key_bytes, kind, levels);
-    if (rc) return rc;
-    if (key_bytes != 4 && key_bytes != 8) return fail(RDST_ERR_UNSUPPORTED, "key-value sorts take 4- or 8-byte keys");
-    if (val_bytes != 4 && val_bytes != 8) return fail(RDST_ERR_UNSUPPORTED, "key-value sorts carry 4- or 8-byte values");
-    if (len <= 1) return RDST_OK;
-    if (!dev_vals || !dev_tmp_keys || !dev_tmp_vals) return fail(RDST_ERR_ARG, "null value / tmp pointer");
-    if (reinterpret_cast<uintptr_t>(dev_tmp_keys) % key_bytes) return fail(RDST_ERR_ALIGN, "tmp key pointer not aligned to the key size");
-    if ((reinterpret_cast<uintptr_t>(dev_vals) | reinterpret_cast<uintptr_t>(dev_tmp_vals)) % val_bytes)
-        return fail(RDST_ERR_ALIGN, "value pointer not aligned to the value size");
+    bool nothing_to_do = false;
+    const int rc = check_pair_args(dev_keys, dev_vals, dev_tmp_keys, dev_tmp_vals, len, key_bytes, kind, levels, val_bytes, &nothing_to_do);
+    if (rc || nothing_to_do) return rc;
     std::lock_guard<std::mutex> lock(g_mutex);
     return rdst_internal::sort_pairs_slice_locked(dev_keys, dev_vals, dev_tmp_keys, dev_tmp_vals, len, key_bytes, kind, val_bytes, static_cast<hipStream_t>(stream));
 }

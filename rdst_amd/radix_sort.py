@@ -173,6 +173,86 @@ def sort_pairs_device_tensor(keys, values, tmp_keys=None, tmp_values=None, check
             _lib.check(lib.rdst_hip_device_status(s))
 
 
+_LENGTH_DTYPES = {"int32": 4, "uint32": 4, "int64": 8, "uint64": 8}
+
+
+def _device_length(length, keys):
+    """len_bytes of a device-resident length, checked without looking at its value"""
+    name = str(getattr(length, "dtype", None)).replace("torch.", "")
+    if not _is_torch_tensor(length) or name not in _LENGTH_DTYPES or length.numel() != 1 or not length.is_contiguous():
+        raise ValueError("length must be a contiguous one-element tensor of dtype int32, int64, uint32 or uint64")
+    if length.device != keys.device:
+        raise ValueError("length must live on the keys' device")
+    return _LENGTH_DTYPES[name]
+
+
+def sort_device_devlen_tensor(keys, length, tmp=None, check=True, key=None):
+    """``rdst_hip_sort_device_devlen``: :func:`sort_device_tensor` over the first ``m`` keys, where ``m`` is the value of
+    ``length`` — a one-element contiguous tensor on the keys' device (int32, int64, uint32 or uint64, read as unsigned) that is
+    read on the stream, never by the host: the kernel that produces it may still be running.  The capacity is the number of
+    keys (``key="u128"/"i128"``: rows); keys from ``m`` on are not touched.  ``m`` past the capacity changes nothing and
+    raises in :func:`device_status` (error bit 32).  The call only enqueues work on the tensor's current stream;
+    ``check=False`` makes no blocking call at all."""
+    import torch
+    if not keys.is_cuda:
+        raise ValueError("sort_device_devlen_tensor needs a tensor on a HIP device")
+    if _wide(key):
+        _check_wide_shape(tuple(keys.shape), keys.element_size())
+    elif keys.dim() != 1:
+        raise ValueError("keys must be a contiguous 1-D tensor (rdst sorts a slice)")
+    if not keys.is_contiguous():
+        raise ValueError("keys must be a contiguous 1-D tensor (rdst sorts a slice)")
+    kind, nbytes, levels = key_info(key if key else keys.dtype)
+    len_bytes = _device_length(length, keys)
+    capacity = keys.numel() * keys.element_size() // nbytes
+    if capacity <= 1:
+        return
+    if tmp is None:
+        tmp = torch.empty_like(keys)
+    elif tmp.dtype != keys.dtype or tmp.numel() < keys.numel() or not tmp.is_contiguous() or tmp.device != keys.device:
+        raise ValueError("tmp must be a contiguous tensor of the same dtype/device with at least len elements")
+    lib = _lib.load()
+    with torch.cuda.device(keys.device):
+        s = _stream_handle(keys)
+        _lib.check(lib.rdst_hip_sort_device_devlen(ctypes.c_void_p(keys.data_ptr()), ctypes.c_void_p(tmp.data_ptr()), capacity,
+                                                   ctypes.c_void_p(length.data_ptr()), len_bytes, nbytes, kind, levels, s))
+        if check:
+            _lib.check(lib.rdst_hip_device_status(s))
+
+
+def sort_pairs_device_devlen_tensor(keys, values, length, tmp_keys=None, tmp_values=None, check=True):
+    """``rdst_hip_sort_pairs_device_devlen``: :func:`sort_pairs_device_tensor` over the first ``m`` pairs, ``m`` being the
+    value of the device-resident ``length`` (see :func:`sort_device_devlen_tensor`); the capacity is ``keys.numel()``.
+    Stable; keys and values from ``m`` on are not touched."""
+    import torch
+    if not (keys.is_cuda and values.is_cuda) or keys.device != values.device:
+        raise ValueError("keys and values must live on the same HIP device")
+    if keys.dim() != 1 or values.dim() != 1 or keys.numel() != values.numel():
+        raise ValueError("keys and values must be 1-D tensors of the same length")
+    if not (keys.is_contiguous() and values.is_contiguous()):
+        raise ValueError("keys and values must be contiguous")
+    kind, nbytes, levels = key_info(keys.dtype)
+    vbytes = values.element_size()
+    len_bytes = _device_length(length, keys)
+    capacity = keys.numel()
+    if capacity <= 1:
+        return
+    tmp_keys = torch.empty_like(keys) if tmp_keys is None else tmp_keys
+    tmp_values = torch.empty_like(values) if tmp_values is None else tmp_values
+    for t, ref in ((tmp_keys, keys), (tmp_values, values)):
+        if t.dtype != ref.dtype or t.numel() < capacity or not t.is_contiguous() or t.device != ref.device:
+            raise ValueError("tmp tensors must match their originals in dtype, device and length")
+    lib = _lib.load()
+    with torch.cuda.device(keys.device):
+        s = _stream_handle(keys)
+        _lib.check(lib.rdst_hip_sort_pairs_device_devlen(ctypes.c_void_p(keys.data_ptr()), ctypes.c_void_p(values.data_ptr()),
+                                                         ctypes.c_void_p(tmp_keys.data_ptr()), ctypes.c_void_p(tmp_values.data_ptr()),
+                                                         capacity, ctypes.c_void_p(length.data_ptr()), len_bytes, nbytes, kind, levels,
+                                                         vbytes, s))
+        if check:
+            _lib.check(lib.rdst_hip_device_status(s))
+
+
 def segments_limits(dtype, val_bytes=0):
     """``rdst_hip_sort_segments_limits``: (wave_max, block_max) of the segmented sort for keys of ``dtype`` (a numpy / torch
     dtype or its name, ``"u128"`` / ``"i128"``) and values of ``val_bytes`` bytes (0: keys only) — the longest segment one
