@@ -299,6 +299,37 @@ void sort_pairs_device_devlen(T* dev_keys, V* dev_vals, T* dev_tmp_keys, V* dev_
     if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
 }
 
+// Partial sort of one DEVICE-resident slice (rdst_hip_topk_device): dev_out_keys[0..k) receives the k keys that
+// radix_sort_unstable would put first — `largest`: last, in descending order —, in that order; dev_keys is only read.  The
+// second form also writes the input position of every output key to dev_out_index (Idx: std::uint32_t or std::uint64_t;
+// 4- and 8-byte keys): equal keys in ascending position, the lowest positions winning a tie at the k-th key.  dev_scratch:
+// 256-byte aligned, at least topk_scratch_bytes<T>(len, k) / topk_scratch_bytes<T, Idx>(len, k) bytes.  cand_capacity: 0 =
+// the library's default; any value gives the same result.  Nothing is copied to the host and nothing waited for.
+template <typename T>
+std::size_t topk_scratch_bytes(std::size_t len, std::size_t k, std::size_t cand_capacity = 0) {
+    return rdst_hip_topk_scratch_bytes(len, k, sizeof(T), 0, cand_capacity);
+}
+template <typename T, typename Idx>
+std::size_t topk_scratch_bytes(std::size_t len, std::size_t k, std::size_t cand_capacity = 0) {
+    return rdst_hip_topk_scratch_bytes(len, k, sizeof(T), sizeof(Idx), cand_capacity);
+}
+template <typename T>
+void topk_device(const T* dev_keys, std::size_t len, std::size_t k, T* dev_out_keys, void* dev_scratch, std::size_t scratch_bytes,
+                 bool largest = false, std::size_t cand_capacity = 0, void* stream = nullptr) {
+    const int rc = rdst_hip_topk_device(dev_keys, len, k, dev_out_keys, nullptr, 0, dev_scratch, scratch_bytes, cand_capacity, sizeof(T),
+                                        RadixKey<T>::kind, static_cast<std::uint32_t>(RadixKey<T>::LEVELS), largest ? RDST_TOPK_LARGEST : 0u, stream);
+    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+}
+template <typename T, typename Idx>
+void topk_device(const T* dev_keys, std::size_t len, std::size_t k, T* dev_out_keys, Idx* dev_out_index, void* dev_scratch,
+                 std::size_t scratch_bytes, bool largest = false, std::size_t cand_capacity = 0, void* stream = nullptr) {
+    static_assert(std::is_unsigned<Idx>::value && (sizeof(Idx) == 4 || sizeof(Idx) == 8), "positions are 4- or 8-byte unsigned integers");
+    const int rc = rdst_hip_topk_device(dev_keys, len, k, dev_out_keys, dev_out_index, sizeof(Idx), dev_scratch, scratch_bytes, cand_capacity,
+                                        sizeof(T), RadixKey<T>::kind, static_cast<std::uint32_t>(RadixKey<T>::LEVELS),
+                                        largest ? RDST_TOPK_LARGEST : 0u, stream);
+    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+}
+
 // DEVICE-resident [u8; N] rows (src/radix_key_impl.rs:78-85) and DEVICE-resident structs ordered by a described key
 // (src/radix_key.rs; examples/impl_radix_key.rs:32-56), in place and with no host involvement
 // (rdst_hip_sort_bytes_device_nowait, rdst_hip_sort_records_by_fields_device_nowait): N, or the sum of the fields' widths,

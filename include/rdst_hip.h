@@ -100,7 +100,9 @@ typedef enum {
     RDST_STAGE_MSD_B = 11,   /* atomic route: scatter of every area by the second byte into the bucket slots (low halves) */
     RDST_STAGE_SAMPLE = 12,  /* the 8 192-key sample (and, if it flags the keys, K1h + the route decision) before the MSD passes */
     RDST_STAGE_SEGMENTS = 13, /* segmented sort: the item table's copy (host offsets) and the batched wave-class and block-class launches */
-    RDST_STAGE_SEGMENTS_TILED = 14 /* segmented sort, nowait entries: the tiled route's launches for the segments beyond block_max */
+    RDST_STAGE_SEGMENTS_TILED = 14, /* segmented sort, nowait entries: the tiled route's launches for the segments beyond block_max */
+    RDST_STAGE_TOPK = 15     /* partial sort: one select level (counting read + bucket pick; its number in bits 8..15), or with
+                                0xFF there the collection pass */
 } rdst_stage;
 
 /* Device routes (rdst_hip_last_route). */
@@ -202,6 +204,62 @@ int rdst_hip_sort_pairs_device_devlen(void* dev_keys, void* dev_vals, void* dev_
                                       uint64_t capacity, const void* dev_len, uint32_t len_bytes,
                                       uint32_t key_bytes, rdst_key_kind kind, uint32_t levels,
                                       uint32_t val_bytes, void* stream);
+
+/* ---- partial sort: the k smallest or largest keys, in order ---------------------------------------
+ * What `select_nth_unstable` + a sort of the front, or torch.topk, give: the front of the order without sorting the array,
+ * copying it or handing over a tmp of its size.  Call M the mapped key of the sort (the order-preserving map of
+ * src/radix_key_impl.rs); with RDST_TOPK_LARGEST in `flags`, M is its bitwise complement.
+ *   - dev_out_keys[0..k) receives the k keys of dev_keys[0..len) that come first in ascending M, in that order, as their
+ *     original bits: without the flag bit for bit the first k elements rdst_hip_sort_device would leave, with it the last k,
+ *     reversed.  -0.0 / +0.0 and NaN payloads are distinct keys, as in the sort.
+ *   - dev_out_index: NULL for keys only; otherwise it receives k integers of index_bytes (4 or 8) bytes, the input position
+ *     of each output key.  Elements with equal keys appear in ascending position, and among the elements tied with the k-th
+ *     key the lowest positions are taken: keys and indices are the first k of a STABLE argsort by M (with the flag: by the
+ *     complemented M, not a reversed ascending argsort).  Deterministic, bit for bit.  Built for 4- and 8-byte keys, as the
+ *     pair sorts are; other widths with an index: RDST_ERR_UNSUPPORTED.  With a NULL dev_out_index, index_bytes is not looked
+ *     at: the call is keys only, and its scratch need is rdst_hip_topk_scratch_bytes(..., index_bytes = 0, ...).
+ *   - The input is never written.  Of the outputs only [0, k) is written, of the scratch only
+ *     [0, rdst_hip_topk_scratch_bytes(len, k, elem_bytes, index_bytes, cand_capacity)); the scratch needs no clearing between
+ *     calls, and stream order makes it reusable by the next call on the same stream.
+ *   - Keys only: every width and kind of rdst_hip_sort_device (1, 2, 4, 8, 16 bytes; unsigned, signed, f32 / f64).
+ *     RDST_KEY_BYTES_BE: RDST_ERR_UNSUPPORTED.
+ *   - ASYNCHRONOUS on `stream` for every input: no copy to the host, no stream or event wait (the one exception every entry
+ *     shares: a library workspace that has to grow).  Every launch is enqueued unconditionally and sized from len, k and
+ *     cand_capacity on the host; there is no data-dependent failure and no error bit: all keys equal, a sorted input, one
+ *     heavy bucket are answered exactly.  This holds for every k up to len: the k selected elements are ordered by the sort's
+ *     pipeline without the split that rdst_hip_sort_device makes (and waits for) beyond ~10^9 keys; so large a k takes the LSD
+ *     route.
+ *   - The mechanism is a radix select: per level one counting read of the input over the keys that still
+ *     share the k-th key's prefix, digit_bits at a time (rdst_hip_topk_limits), until the keys on the prefix number at most
+ *     cand_capacity; then one more read collects the keys before the prefix (fewer than k) and those on it, and only these
+ *     are sorted.  With an index the levels go on over the position's digits, so ties beyond cand_capacity cost further
+ *     levels, never correctness.  cand_capacity: 0 = the library's default; any value >= 1 is legal and gives the same
+ *     result.  It is the most candidates the collection pass may write and the capacity their sort's launches are sized for.
+ *   - Arguments, checked in this order before any device work: the key arguments as rdst_hip_sort_device checks them
+ *     (its codes and messages; BYTES_BE -> RDST_ERR_UNSUPPORTED); len >= 2^32 -> RDST_ERR_UNSUPPORTED; k > len ->
+ *     RDST_ERR_ARG; unknown flag bits -> RDST_ERR_ARG; k == 0 -> RDST_OK, nothing else is looked at; NULL dev_out_keys ->
+ *     RDST_ERR_ARG; dev_out_keys misaligned to the element -> RDST_ERR_ALIGN; with an index: index_bytes not 4 or 8 ->
+ *     RDST_ERR_ARG, key width not 4 or 8 -> RDST_ERR_UNSUPPORTED, misaligned index pointer -> RDST_ERR_ALIGN; NULL scratch
+ *     -> RDST_ERR_ARG; scratch not 256-byte aligned -> RDST_ERR_ALIGN; scratch_bytes below rdst_hip_topk_scratch_bytes(...)
+ *     -> RDST_ERR_ARG. */
+#define RDST_TOPK_LARGEST 1u
+int rdst_hip_topk_device(const void* dev_keys, uint64_t len, uint64_t k,
+                         void* dev_out_keys, void* dev_out_index, uint32_t index_bytes,
+                         void* dev_scratch, uint64_t scratch_bytes, uint64_t cand_capacity,
+                         uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels,
+                         uint32_t flags, void* stream);
+/* The scratch of the call above.  Pure, monotone in k and in cand_capacity: a 256-byte header, 4 096 counters, two arrays of
+ * min(k, len) elements and two of min(cand_capacity or the default, len) elements, each rounded up to 256 bytes; an element
+ * is a key, or with an index a (key, position) composite of twice the key's width.  0 for unsupported widths. */
+uint64_t rdst_hip_topk_scratch_bytes(uint64_t len, uint64_t k, uint32_t elem_bytes,
+                                     uint32_t index_bytes, uint64_t cand_capacity);
+/* out = { digit_bits, the default cand_capacity, the most levels a call can take } for this key width (index_bytes 0 = keys
+ * only).  Pure.  Unsupported widths: RDST_ERR_UNSUPPORTED. */
+int rdst_hip_topk_limits(uint32_t elem_bytes, uint32_t index_bytes, uint32_t out[3]);
+/* Test hook, BLOCKING, like rdst_hip_debug_last_sample: what the most recent rdst_hip_topk_device on this scratch decided.
+ * out = { levels the device used, keys strictly before the threshold prefix, candidates collected, 1 if the keys-only fill
+ * (digits exhausted with more than cand_capacity keys tied) or a position digit was reached }. */
+int rdst_hip_debug_topk_state(const void* dev_scratch, void* stream, uint64_t out[4]);
 
 /* ---- many independent slices in one call ---------------------------------------------------------
  * The reference sorts the 256 buckets of a chunk as slices of their own, in parallel (src/sorter.rs:131-138), and a

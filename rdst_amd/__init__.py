@@ -41,6 +41,10 @@ from .radix_sort import (  # noqa: F401
     sort_pairs_device_tensor,
     sort_device_devlen_tensor,
     sort_pairs_device_devlen_tensor,
+    topk_device_tensor,
+    topk_scratch_bytes,
+    topk_limits,
+    topk_state,
     sort_segments_device_tensor,
     sort_segments_device_offsets_tensor,
     sort_segments_device_offsets_nowait_tensor,
@@ -60,4 +64,5 @@ __all__ = [
     "device_status", "set_tuning", "set_profiling", "set_hybrid", "last_route", "last_sample", "release_workspace", "last_profile", "key_info",
     "KeyField", "key_fields_of", "sort_records_device_tensor", "sort_bytes_device_nowait_tensor", "sort_records_device_nowait_tensor",
     "sort_device_devlen_tensor", "sort_pairs_device_devlen_tensor",
+    "topk_device_tensor", "topk_scratch_bytes", "topk_limits", "topk_state",
 ]

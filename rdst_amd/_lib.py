@@ -19,6 +19,8 @@ RDST_FIELD_DESCENDING = 1  # rdst_key_field.flags: complement the field's mapped
 RDST_KEY_FIELDS_MAX = 16   # fields in one key description
 RDST_STAGE_SEGMENTS = 13   # rdst_stage: the batched launches of the segmented sort
 RDST_STAGE_SEGMENTS_TILED = 14   # rdst_stage: the tiled route of the nowait entries (segments beyond block_max)
+RDST_STAGE_TOPK = 15       # rdst_stage: one select level of the partial sort (level in bits 8..15; 0xFF: the collection pass)
+RDST_TOPK_LARGEST = 1      # rdst_hip_topk_device flags: the k largest, in descending order
 
 # every symbol include/rdst_hip.h declares; tests check that the library exports all of them
 SYMBOLS = (
@@ -31,6 +33,10 @@ SYMBOLS = (
     "rdst_hip_sort_pairs_device",
     "rdst_hip_sort_device_devlen",
     "rdst_hip_sort_pairs_device_devlen",
+    "rdst_hip_topk_device",
+    "rdst_hip_topk_scratch_bytes",
+    "rdst_hip_topk_limits",
+    "rdst_hip_debug_topk_state",
     "rdst_hip_sort_segments_device",
     "rdst_hip_sort_segments_pairs_device",
     "rdst_hip_sort_segments_limits",
@@ -137,6 +143,11 @@ def load():
     lib.rdst_hip_sort_pairs_device.argtypes = [vp, vp, vp, vp, u64, u32, ci, u32, u32, vp]
     lib.rdst_hip_sort_device_devlen.argtypes = [vp, vp, u64, vp, u32, u32, ci, u32, vp]
     lib.rdst_hip_sort_pairs_device_devlen.argtypes = [vp, vp, vp, vp, u64, vp, u32, u32, ci, u32, u32, vp]
+    lib.rdst_hip_topk_device.argtypes = [vp, u64, u64, vp, vp, u32, vp, u64, u64, u32, ci, u32, u32, vp]
+    lib.rdst_hip_topk_scratch_bytes.argtypes = [u64, u64, u32, u32, u64]
+    lib.rdst_hip_topk_scratch_bytes.restype = u64
+    lib.rdst_hip_topk_limits.argtypes = [u32, u32, ctypes.POINTER(u32)]
+    lib.rdst_hip_debug_topk_state.argtypes = [vp, vp, u64p]
     lib.rdst_hip_sort_segments_device.argtypes = [vp, vp, u64, u64, u64p, u64, u32, ci, u32, vp]
     lib.rdst_hip_sort_segments_pairs_device.argtypes = [vp, vp, vp, vp, u64, u64, u64p, u64, u32, ci, u32, u32, vp]
     lib.rdst_hip_sort_segments_limits.argtypes = [u32, u32, ctypes.POINTER(u32)]
@@ -191,7 +202,7 @@ def load():
     for name in SYMBOLS:
         if name not in ("rdst_hip_workspace_bytes", "rdst_hip_sort_bytes_scratch_bytes", "rdst_hip_sort_records_by_fields_scratch_bytes",
                         "rdst_hip_sort_segments_device_offsets_scratch_bytes", "rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes",
-                        "rdst_hip_last_error"):
+                        "rdst_hip_topk_scratch_bytes", "rdst_hip_last_error"):
             getattr(lib, name).restype = ctypes.c_int
     _lib = lib
     return lib

@@ -1,4 +1,4 @@
-// rdst_device.h — device helpers shared by the library's HIP translation units (rdst_kernels.hip, rdst_segments.hip): the
+// rdst_device.h — device helpers shared by the library's HIP translation units (rdst_kernels.hip, rdst_segments.hip, rdst_topk.hip): the
 // order-preserving key map, digit extraction and the wave-level digit ranking.  Every TU gets its own copy (anonymous
 // namespace, all of it inlined).
 #ifndef RDST_DEVICE_H

@@ -129,6 +129,8 @@ private:
 // The current device's sticky error word (kernels OR bits into it; rdst_hip_device_status reports and clears it).
 // `cus_out`, if given: the device's compute-unit count.
 int device_error_word(uint32_t** out, int* cus_out = nullptr);
+// The current device's compute-unit count alone (takes the library's mutex itself).
+int device_cus(int* cus_out);
 
 // [u8; N] rows with N in 1..16, in place on `s`: widened to 4-, 8- or 16-byte integers in `scratch`, sorted by the integer
 // route, narrowed back (the path rdst_hip_sort takes for these widths).  Asynchronous.
@@ -138,7 +140,7 @@ int sort_bytes_widened(void* dev_rows, uint64_t len, uint32_t nb, void* scratch,
 // The same for host-only translation units (rdst_segments.cpp), which do not see HIP's types.
 int note_error(int code, const char* what);
 
-// ---- hooks for rdst_segments.hip -------------------------------------------------------------------------------------
+// ---- hooks for rdst_segments.hip and rdst_topk.hip -------------------------------------------------------------------
 // The library's mutex; every hook below this line is called with it held.
 std::mutex& library_mutex();
 // The argument checks shared by the device entry points (width, kind, levels, pointer, alignment, length); no lock needed.
@@ -149,6 +151,10 @@ void key_xor_masks(rdst_key_kind kind, uint32_t elem_bytes, unsigned __int128* n
 int sort_slice_locked(void* keys, void* tmp, uint64_t n, uint32_t elem_bytes, rdst_key_kind kind, hipStream_t s);
 int sort_pairs_slice_locked(void* keys, void* vals, void* tmp_keys, void* tmp_vals, uint64_t n, uint32_t key_bytes, rdst_key_kind kind,
                             uint32_t val_bytes, hipStream_t s);
+// sort_slice_locked for entries that promise NO WAIT AT ANY LENGTH: never the split of slices beyond the window, whose 256
+// counts come to the host (the one wait rdst_hip_sort_device documents).  The pipeline alone: the routes the device decides
+// on, the LSD route beyond the window.  Bit for bit the same result.
+int sort_slice_nowait_locked(void* keys, void* tmp, uint64_t n, uint32_t elem_bytes, rdst_key_kind kind, hipStream_t s);
 // The same with the length in device memory (rdst_hip_sort_device_devlen / rdst_hip_sort_pairs_device_devlen after their
 // checks): `dev_len` is one unsigned integer of `len_bytes` (4 or 8) bytes, read on `s`; launches and workspace are sized
 // for `capacity` (> 1).  The LSD route only; no copy to the host, no wait.

@@ -5931,6 +5931,14 @@ int sort_pairs_slice_devlen_locked(void* keys, void* vals, void* tmp_keys, void*
         });
     });
 }
+
+// sort_slice_locked without the split of slices beyond the window (run_split_sort reads its counts back and waits for the
+// stream): the pipeline alone, whose routes the device decides on.  Same result at every length.
+int sort_slice_nowait_locked(void* keys, void* tmp, uint64_t n, uint32_t elem_bytes, rdst_key_kind kind, hipStream_t s) {
+    int rc = RDST_OK;
+    RDST_BY_WIDTH(elem_bytes, rc = (run_pipeline<K, LV>(static_cast<K*>(keys), static_cast<K*>(tmp), n, kind, 0, LV, true, true, s, nullptr, nullptr)));
+    return rc;
+}
 }  // namespace rdst_internal
 
 namespace {
@@ -6459,6 +6467,13 @@ int device_error_word(uint32_t** out, int* cus_out) {
     if (D.rc) return D.rc;
     *out = D->err_dev;
     if (cus_out) *cus_out = D->cus;
+    return RDST_OK;
+}
+
+int device_cus(int* cus_out) {
+    LockedDevice D;
+    if (D.rc) return D.rc;
+    *cus_out = D->cus;
     return RDST_OK;
 }
 

@@ -253,6 +253,77 @@ def sort_pairs_device_devlen_tensor(keys, values, length, tmp_keys=None, tmp_val
             _lib.check(lib.rdst_hip_device_status(s))
 
 
+def topk_limits(dtype, index_bytes=0):
+    """``rdst_hip_topk_limits``: (digit_bits, default cand_capacity, most levels a call can take) of the partial sort for keys
+    of ``dtype`` (a numpy / torch dtype or its name, ``"u128"`` / ``"i128"``); ``index_bytes``: 0 = keys only, 4 or 8."""
+    _kind, nbytes, _levels = key_info(dtype)
+    out = (ctypes.c_uint32 * 3)()
+    _lib.check(_lib.load().rdst_hip_topk_limits(nbytes, int(index_bytes), out))
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def topk_scratch_bytes(n, k, dtype, index_bytes=0, cand_capacity=0):
+    """``rdst_hip_topk_scratch_bytes``: bytes of scratch :func:`topk_device_tensor` needs for ``k`` of ``n`` keys of ``dtype``
+    (0 for widths the entry is not built for)."""
+    _kind, nbytes, _levels = key_info(dtype)
+    return int(_lib.load().rdst_hip_topk_scratch_bytes(int(n), int(k), nbytes, int(index_bytes), int(cand_capacity)))
+
+
+def topk_state(scratch):
+    """``rdst_hip_debug_topk_state`` (test hook, blocking): what the most recent :func:`topk_device_tensor` on ``scratch``
+    decided — dict with ``levels`` (select levels the device used), ``c_below`` (keys strictly before the threshold prefix),
+    ``candidates`` (collected) and ``special`` (the keys-only fill or a position digit was reached)."""
+    import torch
+    out = (ctypes.c_uint64 * 4)()
+    with torch.cuda.device(scratch.device):
+        _lib.check(_lib.load().rdst_hip_debug_topk_state(ctypes.c_void_p(scratch.data_ptr()), _stream_handle(scratch), out))
+    return {"levels": int(out[0]), "c_below": int(out[1]), "candidates": int(out[2]), "special": int(out[3])}
+
+
+def topk_device_tensor(keys, k, largest=False, index=None, scratch=None, cand_capacity=0, check=True, key=None):
+    """``rdst_hip_topk_device``: the ``k`` keys of the 1-D contiguous HIP tensor ``keys`` (``key="u128"/"i128"``: shape (n, 2))
+    that come first in the sort's order — ``largest``: last, in descending order —, in that order, as a new tensor; ``keys`` is
+    not modified.  ``index``: ``None`` for keys only, ``torch.int32`` or ``torch.int64`` to get the input position of every
+    output key as well (4- and 8-byte keys); equal keys appear in ascending position and the lowest positions win a tie at
+    the k-th key, so the pair is the first ``k`` of a stable argsort.  ``scratch``: optional uint8 HIP tensor of at least
+    :func:`topk_scratch_bytes` bytes (allocated when omitted); ``cand_capacity``: 0 = the library's default, any value >= 1
+    gives the same result.  Returns ``(out_keys, out_index or None)``.  The call only enqueues work on the tensor's current
+    stream; ``check=False`` makes no blocking call at all (kernel failures then surface in :func:`device_status`)."""
+    import torch
+    if not keys.is_cuda:
+        raise ValueError("topk_device_tensor needs a tensor on a HIP device")
+    if _wide(key):
+        _check_wide_shape(tuple(keys.shape), keys.element_size())
+    elif keys.dim() != 1:
+        raise ValueError("keys must be a contiguous 1-D tensor (rdst sorts a slice)")
+    if not keys.is_contiguous():
+        raise ValueError("keys must be a contiguous 1-D tensor (rdst sorts a slice)")
+    kind, nbytes, levels = key_info(key if key else keys.dtype)
+    n = keys.numel() * keys.element_size() // nbytes
+    k = int(k)
+    if not 0 <= k <= n:
+        raise ValueError("k must lie in 0..len")
+    if index not in (None, torch.int32, torch.int64):
+        raise ValueError("index must be None, torch.int32 or torch.int64")
+    index_bytes = 0 if index is None else (4 if index == torch.int32 else 8)
+    out_keys = torch.empty((k, 2) if _wide(key) else (k,), dtype=keys.dtype, device=keys.device)
+    out_index = None if index is None else torch.empty(k, dtype=index, device=keys.device)
+    if k == 0:
+        return out_keys, out_index
+    lib = _lib.load()
+    need = int(lib.rdst_hip_topk_scratch_bytes(n, k, nbytes, index_bytes, int(cand_capacity)))
+    with torch.cuda.device(keys.device):
+        scratch, sbytes = _segments_scratch(scratch, need, keys.device)
+        s = _stream_handle(keys)
+        _lib.check(lib.rdst_hip_topk_device(ctypes.c_void_p(keys.data_ptr()), n, k, ctypes.c_void_p(out_keys.data_ptr()),
+                                            ctypes.c_void_p(out_index.data_ptr()) if out_index is not None else None, index_bytes,
+                                            ctypes.c_void_p(scratch.data_ptr()), sbytes, int(cand_capacity), nbytes, kind, levels,
+                                            _lib.RDST_TOPK_LARGEST if largest else 0, s))
+        if check:
+            _lib.check(lib.rdst_hip_device_status(s))
+    return out_keys, out_index
+
+
 def segments_limits(dtype, val_bytes=0):
     """``rdst_hip_sort_segments_limits``: (wave_max, block_max) of the segmented sort for keys of ``dtype`` (a numpy / torch
     dtype or its name, ``"u128"`` / ``"i128"``) and values of ``val_bytes`` bytes (0: keys only) — the longest segment one
@@ -955,7 +1026,7 @@ def profile_runs() -> int:
     return int(_lib.load().rdst_hip_profile_runs())
 
 
-STAGE_NAMES = {1: "clear", 2: "histogram", 3: "scan", 4: "pass", 5: "copy_back", 6: "histogram16", 7: "route", 8: "local_sort", 10: "msd_pass_a", 11: "msd_pass_b", 12: "sample", 13: "segments", 14: "segments_tiled"}
+STAGE_NAMES = {1: "clear", 2: "histogram", 3: "scan", 4: "pass", 5: "copy_back", 6: "histogram16", 7: "route", 8: "local_sort", 10: "msd_pass_a", 11: "msd_pass_b", 12: "sample", 13: "segments", 14: "segments_tiled", 15: "topk"}
 
 
 def profile_run(run: int, levels: int):
@@ -976,7 +1047,7 @@ def profile_run(run: int, levels: int):
         code, level = kinds[i] & 0xFF, (kinds[i] >> 8) & 0xFF
         name = STAGE_NAMES.get(code, f"stage{code}")
         ms = float(buf[i])
-        out["stages"].append((name, level if name == "pass" else None, ms))
+        out["stages"].append((name, level if name in ("pass", "topk") else None, ms))   # (topk: the select level; 255 = the collection pass)
         if name == "pass":
             out["passes"].append(ms)
         else:
