@@ -162,3 +162,31 @@ def tail_case(name, capacity, m, dtype, seed=0):
     keys = H.unmapped(mk, dt.name)
     assert H.same_bits(H.mapped_key(keys), mk)
     return keys
+
+
+# the same for the widths tail_case's two constant bytes do not fit: (key, the levels at which the "tail varies" prefix is
+# constant) — one pass is left for int16 and thirteen for u128, an odd number, so copyback_devlen_kernel moves exactly m keys
+NARROW_WIDE_TAILS = (("int16", (1,)), ("u128", (0, 1, 2)))
+NARROW_WIDE_FAMILIES = ("tail varies", "sorted prefix")
+
+
+def tail_case_levels(name, capacity, m, key, levels, seed=0):
+    """tail_case for "int16" and "u128" (rows of limbs [low, high]):
+      "tail varies"    the prefix is constant at `levels` of the mapped key — K2 skips them if it looks at the prefix alone —
+                       and the tail varies in them
+      "sorted prefix"  the prefix is sorted already and the tail is not, and lies below the prefix's largest key"""
+    if name == "tail varies":
+        if key == "u128":
+            keys = H.wide_with_constant_levels(capacity, key, (), seed=[seed, capacity, m])
+            keys[:m] = H.wide_with_constant_levels(m, key, levels, seed=[seed, m])
+            return keys
+        keys = H.random_bits(capacity, key, seed + capacity).copy()
+        keys[:m] = H.keys_with_constant_levels(m, key, levels, seed + m)
+        return keys
+    assert name == "sorted prefix", name
+    if key == "u128":
+        keys = random_keys(capacity, key, seed + capacity)
+        keys[m:, 1] >>= np.uint64(1)                            # the tail: in the lower half
+        keys[:m] = keys[:m][order_of(keys[:m])]
+        return keys
+    return tail_case(name, capacity, m, key, seed)

@@ -127,9 +127,10 @@ def giant_buckets_input(rng, dtype):
     return a.view(dtype)
 
 
-def heavy_digit_inputs(n, dtype, level, seed):
+def heavy_digit_inputs(n, dtype, level, seed, run=1000):
     """inputs that put the lr variants of out_of_place_sort to work (src/sorts/out_of_place_sort.rs:202-389: a
-    bucket written from both ends when many equal digits sit next to each other) and the heavy-digit ranking of K3"""
+    bucket written from both ends when many equal digits sit next to each other) and the heavy-digit ranking of K3;
+    `run`: the length of the "long equal runs" """
     rng = np.random.default_rng(seed)
     w = np.dtype(dtype).itemsize * 8
     ut = f"uint{w}"
@@ -147,7 +148,7 @@ def heavy_digit_inputs(n, dtype, level, seed):
     out["two digits only"] = with_digits(rng.choice([3, 200], size=n))
     out["one digit per 64-key round"] = with_digits(np.repeat(rng.integers(0, 256, size=(n + 63) // 64), 64)[:n])
     out["sorted by digit"] = with_digits(np.sort(rng.integers(0, 256, size=n)))
-    out["long equal runs"] = with_digits(np.repeat(rng.integers(0, 256, size=(n + 999) // 1000), 1000)[:n])
+    out["long equal runs"] = with_digits(np.repeat(rng.integers(0, 256, size=(n + run - 1) // run), run)[:n])
     return out
 
 
@@ -793,6 +794,61 @@ def chain_split_cases(n, dtype, seed=77, short=40_000, tiny=700):
         "short": full[:short],
         "tiny": full[:tiny],
     }
+
+
+# ---- 16-byte keys ("u128" / "i128"): (n, 2) uint64 rows of limbs [low, high]; level l is byte l % 8 of limb l // 8 -------------
+
+def is_wide(key):
+    return key in ("u128", "i128")
+
+
+def wide_mapped(a, key):
+    """the limbs of the mapped keys: the top bit of `high` flipped for "i128" (its own inverse: mapped limbs -> keys too)"""
+    m = np.array(a, dtype=np.uint64, copy=True)
+    if key == "i128":
+        m[:, 1] ^= np.uint64(1 << 63)
+    return m
+
+
+def wide_order(a, key):
+    """the stable order of 16-byte keys: by the mapped high limb, then the low one"""
+    m = wide_mapped(a, key)
+    return np.lexsort((m[:, 0], m[:, 1]))
+
+
+def wide_sorted(a, key):
+    return a[wide_order(a, key)]
+
+
+def wide_digits(m, level):
+    """the digit of every row of (mapped) limbs at `level`, 0 (the lowest byte of `low`) to 15"""
+    return ((m[:, level // 8] >> np.uint64(8 * (level % 8))) & np.uint64(0xFF)).astype(np.int64)
+
+
+def wide_with_constant_levels(n, key, levels, seed, digit=0x5A):
+    """the limb form of keys_with_constant_levels: random 16-byte keys whose MAPPED bytes at `levels` all hold `digit`"""
+    m = np.random.default_rng(seed).integers(0, 1 << 64, size=(n, 2), dtype=np.uint64, endpoint=False)
+    for l in levels:
+        sh = np.uint64(8 * (l % 8))
+        m[:, l // 8] = (m[:, l // 8] & ~(np.uint64(0xFF) << sh)) | (np.uint64(digit) << sh)
+    return wide_mapped(m, key)
+
+
+def wide_constant_levels(a, key):
+    """the limb form of constant_levels"""
+    m = wide_mapped(a, key)
+    return {l for l in range(16) if (wide_digits(m, l) == wide_digits(m[:1], l)[0]).all()}
+
+
+def wide_heavy_digit_inputs(n, key, level, seed, run=1000):
+    """the limb form of heavy_digit_inputs: its digit shapes at `level` of the MAPPED key, every other byte random"""
+    other = np.random.default_rng([seed, 16]).integers(0, 1 << 64, size=n, dtype=np.uint64, endpoint=False)
+    out = {}
+    for name, limb in heavy_digit_inputs(n, "uint64", level % 8, seed, run).items():
+        m = np.empty((n, 2), dtype=np.uint64)
+        m[:, level // 8], m[:, 1 - level // 8] = limb, other
+        out[name] = wide_mapped(m, key)
+    return out
 
 
 # ---- the wide [u8; N] route's refinement rounds: rows with a known order, and §2d's loop restated --------------------------

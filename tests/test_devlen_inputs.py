@@ -115,6 +115,34 @@ def test_tails_stand_in_the_stated_relation(dtype):
             assert bool((tail[1:] > tail[:-1]).all()) and tail.min() > pre.max()
 
 
+@pytest.mark.parametrize("key,levels", D.NARROW_WIDE_TAILS, ids=[k for k, _ in D.NARROW_WIDE_TAILS])
+def test_narrow_and_wide_tails_stand_in_the_stated_relation(key, levels):
+    wide = key == "u128"
+    kb = 16 if wide else np.dtype(key).itemsize
+    tile = D.pass_tile(kb, not wide and np.dtype(key).kind != "u")
+    cap, m = 3 * tile + 11, 2 * tile - 345
+    assert D.small_tile(kb) < m < cap                      # (the twin of m keys takes the pipeline as well)
+    const = (lambda a: H.wide_constant_levels(a, key)) if wide else H.constant_levels
+
+    def is_sorted(a):
+        order = D.order_of(a)
+        return bool((order == np.arange(len(a))).all())     # (the stable order of sorted keys is the identity)
+
+    a = D.tail_case_levels("tail varies", cap, m, key, levels)
+    assert len(a) == cap and (a.shape == (cap, 2) if wide else a.dtype == np.dtype(key))
+    assert const(a[:m]) == set(levels) and (kb - len(levels)) % 2 == 1     # an odd number of passes: the copy-back moves m keys
+    assert not const(a[m:]) & set(levels) and not const(a) and not is_sorted(a[:m])
+    for l in levels:                                          # the tail varies at the prefix's constant levels: every digit occurs
+        d = H.wide_digits(a[m:], l) if wide else (H.mapped_key(a[m:]) >> np.array(8 * l, dtype=f"u{kb}")) & np.array(0xFF, dtype=f"u{kb}")
+        assert len(np.unique(d)) == 256
+
+    a = D.tail_case_levels("sorted prefix", cap, m, key, levels)
+    assert len(a) == cap and is_sorted(a[:m]) and not is_sorted(a[m:]) and not is_sorted(a)
+    assert H.same_bits(D.expected_prefix_sorted(a, m), a)
+    last = np.concatenate([a[m - 1:m], a[m:]])               # the prefix's largest key, then the tail: a tail key lies below it
+    assert D.order_of(last)[0] != 0
+
+
 @pytest.mark.parametrize("dtype", ("uint8", "int16", "uint32", "float32", "int64", "float64"))
 def test_prefix_sort_is_one_stable_sort_under_the_padded_key(dtype):
     """what a caller of the device-length sort may rely on: sorting the first m elements and leaving the rest equals a stable

@@ -68,6 +68,7 @@ def _check_keys(gpu, a, m, key, length_dtype, what):
     assert np.array_equal(got[:m].view(np.uint8), twin.view(np.uint8)), what
     assert np.array_equal(got[m:].view(np.uint8), a[m:].view(np.uint8)), f"{what}: the tail changed"
     assert _poisoned_from(t, a, m), f"{what}: tmp written from m on"
+    return t
 
 
 def _check_pairs(gpu, a, v, m, length_dtype, what):
@@ -134,6 +135,24 @@ def test_tail_is_never_read(gpu, name):
             assert _poisoned_from(t, a, m if name != "sorted prefix" else 0), what
         if name == "sorted prefix":
             assert H.same_bits(D.expected_prefix_sorted(a, m), a)
+
+
+@pytest.mark.parametrize("key,levels", D.NARROW_WIDE_TAILS, ids=[k for k, _ in D.NARROW_WIDE_TAILS])
+@pytest.mark.parametrize("name", D.NARROW_WIDE_FAMILIES)
+def test_tail_is_never_read_at_2_and_16_byte_keys(gpu, name, key, levels):
+    """K2's trivial-level test must look at the first m keys only: a prefix that is constant at level 1 (int16) or at the
+    levels 0 to 2 (u128) before a tail that varies there leaves an odd number of passes, so copyback_devlen_kernel moves
+    exactly m keys; a sorted prefix before an unsorted tail runs no pass and writes nothing."""
+    wide = key == "u128"
+    kb = 16 if wide else np.dtype(key).itemsize
+    tile = D.pass_tile(kb, not wide and np.dtype(key).kind != "u")
+    cap, m = 3 * tile + 11, 2 * tile - 345
+    a = D.tail_case_levels(name, cap, m, key, levels)
+    what = f"{name} {key} keys"
+    t = _check_keys(gpu, a, m, key, "uint32", what)
+    if name == "sorted prefix":
+        assert H.same_bits(D.expected_prefix_sorted(a, m), a)
+        assert _poisoned_from(t, a, 0), f"{what}: tmp written"
 
 
 # ---- 4: a length past the capacity -------------------------------------------------------------------------------------

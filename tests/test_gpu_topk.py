@@ -128,6 +128,39 @@ def test_every_depth_at_capacities_around_the_bucket(gpu, dtype, j):
     assert T.restate(a, k, False, False, 64)["levels"] in depths
 
 
+@pytest.mark.parametrize("key,bits", T.wide_depth_cases(), ids=[f"{k}-top{b}" for k, b in T.wide_depth_cases()])
+def test_every_depth_with_16_byte_keys(gpu, key, bits):
+    """16-byte keys that share their top bits: the levels 2 to 11 of the select, the level whose digit straddles the two
+    limbs (bits [56, 68)), the narrow last level, a 16-byte prefix in the pick, histogram and collection kernels, and — 120
+    or 128 shared bits at a small capacity — the keys-only fill.  tests/test_topk_inputs.py holds the depth of every case."""
+    a = T.wide_depth_input(key, bits)
+    t = H.to_device(a)
+    k = T.DEPTH_LEN // 3
+    base = T.restate(a, k, False, False, 64, key)
+    depths = set()
+    for cap in T.depth_capacities(base["m"]):
+        for largest in (False, True):
+            order = T.order_of(a, key, largest)
+            depths.add(_check(gpu, a, k, largest, None, cap, key, f"top {bits} bits shared", keys_t=t, order=order)["levels"])
+    assert base["levels"] in depths
+    if bits % 12 == 0 and bits <= 120:
+        assert base["levels"] == bits // 12 + 1
+
+
+@pytest.mark.parametrize("dtype,ib", T.FAR_CASES, ids=[f"{d}-i{8 * ib}" for d, ib in T.FAR_CASES])
+def test_a_kth_element_beyond_position_2_to_the_20(gpu, dtype, ib):
+    """All keys equal, with an index: the select runs through every position level, and the k-th element lies beyond
+    position 2^20, so the top position digit (bits 20 to 31 of the position prefix and mask) is not 0 — in the histogram of
+    the levels below it and in the collection's class of positions below the prefix.  The index must be 0 .. k - 1."""
+    a = T.far_input(dtype)
+    t = H.to_device(a)
+    order = np.arange(T.FAR_LEN)
+    for cap in T.FAR_CAPACITIES:
+        for largest in (False, True):
+            st = _check(gpu, a, T.FAR_K, largest, ib, cap, None, "far k", keys_t=t, order=order)
+            assert st == {"levels": T.max_levels(a.dtype.itemsize, True), "c_below": T.FAR_K - 1, "candidates": 1, "special": 1}, st
+
+
 # ---- 3: ties ------------------------------------------------------------------------------------------------------------------
 
 @pytest.mark.parametrize("dtype", ("uint8", "int16", "uint32", "float32", "int64", "float64"))

@@ -135,6 +135,74 @@ def test_depth_cases_reach_every_depth_they_are_named_for():
         assert depths == set(range(1, T.key_levels(kb) + 1)), (dtype, depths)
 
 
+def test_shared_top_wide_shares_what_it_says():
+    for key in T.WIDE_KEYS:
+        for bits in T.WIDE_DEPTH_BITS + (1, 63, 64, 65, 127):
+            a = T.shared_top_wide(2000, key, bits, 9)
+            v = T.mapped_ints(a, key)
+            assert len({x >> (128 - bits) for x in v}) == 1
+            if bits < 128:                                # the bit below the shared ones takes both values, the lowest one too
+                assert len({(x >> (127 - bits)) & 1 for x in v}) == 2 and len({x & 1 for x in v}) == 2
+            # mapped_ints, mapped_limbs and order_of say the same
+            hi, lo = T.mapped_limbs(a, key)
+            assert v == [(int(h) << 64) | int(l) for h, l in zip(hi.tolist(), lo.tolist())]
+            assert list(T.order_of(a, key)) == sorted(range(2000), key=lambda i: v[i])
+            w = T.mapped_ints(a, key, largest=True)
+            assert w == [x ^ ((1 << 128) - 1) for x in v] and list(T.order_of(a, key, True)) == sorted(range(2000), key=lambda i: w[i])
+
+
+@pytest.mark.parametrize("key", T.WIDE_KEYS)
+def test_wide_depth_cases_reach_every_depth_and_the_fill(key):
+    """the restated loop against the statement in Python integers (shared_counts_wide) on every case and capacity of
+    test_every_depth_with_16_byte_keys — the level of bits [56, 68) takes its digit from both limbs — and the depths the
+    cases are named for: 1 to 11 at capacity 64, none missing, and the fill"""
+    assert T.key_levels(16) == 11 and T.level_shapes(16, False)[5] == (False, 56, 12) and T.level_shapes(16, False)[10] == (False, 0, 8)
+    k = T.DEPTH_LEN // 3
+    reached, fills, straddled = {}, set(), 0
+    for kind, bits in T.wide_depth_cases():
+        if kind != key:
+            continue
+        a = T.wide_depth_input(key, bits)
+        for largest in (False, True):
+            sizes = T.shared_counts_wide(a, k, largest, key)
+            assert len(sizes) == 12 and sizes[0] == T.DEPTH_LEN and sizes == sorted(sizes, reverse=True) and sizes[-1] >= 1
+            base = T.restate(a, k, largest, False, 64, key)
+            for cap in T.depth_capacities(T.restate(a, k, False, False, 64, key)["m"]):
+                r = T.restate(a, k, largest, False, cap, key)
+                depth = T.direct_depth_wide(a, k, largest, cap, key, sizes)
+                assert r["levels"] == depth, (key, bits, largest, cap, r, sizes)
+                assert r["m"] == sizes[depth] and r["c_below"] < k <= r["c_below"] + r["m"]
+                fill = depth == 11 and sizes[11] > cap
+                assert (r["special"], r["candidates"]) == ((1, 0) if fill else (0, sizes[depth])), (key, bits, largest, cap)
+                straddled += int(depth >= 6)
+            reached.setdefault(largest, {})[bits] = base["levels"]
+            if base["special"]:
+                assert base["candidates"] == 0 and base["levels"] == 11
+                fills.add((largest, bits))
+    for largest in (False, True):
+        for d in range(1, 12):
+            assert reached[largest][12 * (d - 1)] == d, (key, largest, d, reached[largest])
+        assert set(reached[largest].values()) == set(range(1, 12))
+        assert reached[largest][60] == 6 and reached[largest][68] == 7 and reached[largest][128] == 11
+        assert {(largest, 120), (largest, 128)} <= fills
+    assert straddled > 0
+
+
+@pytest.mark.parametrize("dtype,ib", T.FAR_CASES)
+def test_far_cases_end_in_the_top_position_digit(dtype, ib):
+    """all keys equal and a k-th element beyond position 2^20: every key level and every position level runs, the digit of
+    the position bits 20 to 31 is 1, and one candidate is left"""
+    a = T.far_input(dtype)
+    kb = a.dtype.itemsize
+    assert len(a) == T.FAR_LEN and len(np.unique(a)) == 1 and (T.FAR_K - 1) >> 20 == 1 and T.FAR_K < T.FAR_LEN < 1 << 21
+    for cap in T.FAR_CAPACITIES:
+        for largest in (False, True):
+            assert np.array_equal(T.order_of(a, None, largest), np.arange(T.FAR_LEN))
+            r = T.restate(a, T.FAR_K, largest, True, cap)
+            assert r == {"levels": T.max_levels(kb, True), "c_below": T.FAR_K - 1, "candidates": 1, "special": 1, "m": 1}, (dtype, cap, r)
+    assert [T.max_levels(np.dtype(d).itemsize, True) for d, _ in T.FAR_CASES] == [6, 9]
+
+
 def test_tie_cases_tie_where_they_say():
     for dtype in ("uint32", "float32", "int64"):
         keys, k, at = T.tie_case(dtype, 3)

@@ -199,6 +199,72 @@ def shared_top(n, dtype, j, seed):
     return H.unmapped(m.view(f"u{kb}"), dtype)
 
 
+def shared_top_wide(n, key, bits, seed):
+    """the limb form of shared_top: n 16-byte keys ("u128" / "i128", rows of limbs [low, high]) whose MAPPED keys share their
+    top `bits` bits (128: all keys equal) and are random below"""
+    m = np.random.default_rng(seed).integers(0, 1 << 64, size=(n, 2), dtype=np.uint64, endpoint=False)
+    pattern = 0xA5C3F00F5A3C0FF0_C33C5AA50FF0F00F                           # its top `bits` bits are shared
+    keep = (1 << (128 - bits)) - 1                                          # the bits that stay random
+    for limb, shift in ((0, 0), (1, 64)):
+        k, p = (keep >> shift) & ((1 << 64) - 1), (pattern >> shift) & ((1 << 64) - 1)
+        m[:, limb] = (m[:, limb] & np.uint64(k)) | np.uint64(p & ~k & ((1 << 64) - 1))
+    return H.wide_mapped(m, key)
+
+
+def mapped_ints(a, key, largest=False):
+    """the mapped keys of rows of limbs as Python integers (complemented for largest)"""
+    flip = (1 << 127 if key == "i128" else 0) ^ ((1 << 128) - 1 if largest else 0)
+    return [((int(hi) << 64) | int(lo)) ^ flip for lo, hi in a.tolist()]
+
+
+def shared_counts_wide(a, k, largest, key):
+    """sizes[i], in Python integers: how many 16-byte keys share the digits of the first i 12-bit levels (the last one is 8
+    bits wide) with the k-th element of the stable order, i = 0 .. 11"""
+    v = mapped_ints(a, key, largest)
+    t = v[int(order_of(a, key, largest)[k - 1])]
+    sizes, hi = [len(v)], 128
+    while hi > 0:
+        lo = max(hi - DIGIT_BITS_WIDE, 0)
+        v = [x for x in v if x >> lo == t >> lo]                            # (every level above already agrees)
+        sizes.append(len(v))
+        hi = lo
+    return sizes
+
+
+def direct_depth_wide(a, k, largest, cand_capacity, key, sizes=None):
+    """direct_depth for 16-byte keys, keys only: the fewest leading levels whose digits, taken from the k-th element of the
+    stable order, are shared by at most cand_capacity elements"""
+    cap = min(cand_capacity or DEFAULT_CAND_CAPACITY, max(len(a), 1))
+    sizes = sizes or shared_counts_wide(a, k, largest, key)
+    return next((i for i, s in enumerate(sizes) if s <= cap), len(sizes) - 1)
+
+
+WIDE_KEYS = ("u128", "i128")
+WIDE_DEPTH_BITS = tuple(sorted({12 * (d - 1) for d in range(1, 12)} | {60, 68, 128}))   # (60 is also 12 * 5)
+
+
+def wide_depth_cases():
+    """(key, bits): the top 12 (d - 1) bits shared reaches depth d = 1 .. 11 at capacity 64 (the level of bits [56, 68)
+    straddles the limbs, the last level is 8 bits wide); 60 and 68 bits end inside and behind the straddling level; 120 and
+    128 shared bits leave more than 64 equal digits at the last level: the fill"""
+    return [(key, bits) for key in WIDE_KEYS for bits in WIDE_DEPTH_BITS]
+
+
+def wide_depth_input(key, bits):
+    return shared_top_wide(DEPTH_LEN, key, bits, 300 + bits)
+
+
+# a k-th element beyond position 2^20 among equal keys: the top position digit (bits 20 to 31) is not 0
+FAR_LEN = (1 << 20) + 4099
+FAR_K = (1 << 20) + 2050
+FAR_CASES = (("uint32", 4), ("int64", 8))
+FAR_CAPACITIES = (64, 1)
+
+
+def far_input(dtype):
+    return np.full(FAR_LEN, H.random_bits(1, dtype, 3)[0], dtype=dtype)
+
+
 DEPTH_LEN = 20_000
 DEPTH_DTYPES = ("uint16", "int32", "float32", "uint64", "float64")
 
