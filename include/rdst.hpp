@@ -38,6 +38,12 @@ struct Error : std::runtime_error {
     Error(int s, const std::string& what) : std::runtime_error(what), status(s) {}
 };
 
+namespace detail {
+inline void check(int rc) {  // the status of a library call: anything but RDST_OK throws, with the library's own words
+    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+}
+}  // namespace detail
+
 // RadixKey (src/radix_key.rs:1-5) for the built-in types whose mapping the device knows.
 template <typename T, typename = void> struct RadixKey;  // not defined: no device mapping for T
 template <typename T>
@@ -135,8 +141,7 @@ class RadixSortBuilder {  // src/radix_sort_builder.rs:8-158
                 throw Error(RDST_ERR_UNSUPPORTED, "tuner picked a CPU algorithm: those stay in the reference crate; this header ships the device route only");
         }
         rdst_hip_opts opts{-1, low_memory_ ? 1 : 0, 0};
-        const int rc = rdst_hip_sort(data_, len_, sizeof(T), RadixKey<T>::kind, RadixKey<T>::LEVELS, &opts);
-        if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+        detail::check(rdst_hip_sort(data_, len_, sizeof(T), RadixKey<T>::kind, RadixKey<T>::LEVELS, &opts));
     }
 
    private:
@@ -172,8 +177,7 @@ void radix_sort_unstable_by_field(T* data, std::size_t len, KeyT T::*field) {
                   "the device route takes 4- or 8-byte key fields and [u8; N] fields");
     if (len <= 1) return;
     const std::size_t offset = static_cast<std::size_t>(reinterpret_cast<const char*>(&(data[0].*field)) - reinterpret_cast<const char*>(&data[0]));
-    const int rc = rdst_hip_sort_records(data, len, sizeof(T), static_cast<std::uint32_t>(offset), sizeof(KeyT), RadixKey<KeyT>::kind, nullptr);
-    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+    detail::check(rdst_hip_sort_records(data, len, sizeof(T), static_cast<std::uint32_t>(offset), sizeof(KeyT), RadixKey<KeyT>::kind, nullptr));
 }
 template <typename T, typename KeyT>
 void radix_sort_unstable_by_field(std::vector<T>& v, KeyT T::*field) { radix_sort_unstable_by_field(v.data(), v.size(), field); }
@@ -191,8 +195,7 @@ void radix_sort_unstable_by_field(std::vector<T>& v, KeyT T::*field) { radix_sor
 template <typename T>
 void sort_records_by(T* data, std::size_t n, std::initializer_list<rdst_key_field> fields) {
     static_assert(std::is_trivially_copyable<T>::value, "rows are moved as bytes");
-    const int rc = rdst_hip_sort_records_by_fields(data, n, sizeof(T), fields.begin(), static_cast<std::uint32_t>(fields.size()), nullptr);
-    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+    detail::check(rdst_hip_sort_records_by_fields(data, n, sizeof(T), fields.begin(), static_cast<std::uint32_t>(fields.size()), nullptr));
 }
 template <typename T>
 void sort_records_by(std::vector<T>& v, std::initializer_list<rdst_key_field> fields) { sort_records_by(v.data(), v.size(), fields); }
@@ -205,9 +208,8 @@ void sort_records_by(std::vector<T>& v, std::initializer_list<rdst_key_field> fi
 template <typename T>
 void sort_segments(T* dev_keys, std::size_t len, const std::uint64_t* offsets, std::size_t n_segments, T* dev_tmp = nullptr,
                    std::size_t tmp_elems = 0, void* stream = nullptr) {
-    const int rc = rdst_hip_sort_segments_device(dev_keys, dev_tmp, tmp_elems, len, offsets, n_segments, sizeof(T), RadixKey<T>::kind,
-                                                 static_cast<std::uint32_t>(RadixKey<T>::LEVELS), stream);
-    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+    detail::check(rdst_hip_sort_segments_device(dev_keys, dev_tmp, tmp_elems, len, offsets, n_segments, sizeof(T), RadixKey<T>::kind,
+                                                static_cast<std::uint32_t>(RadixKey<T>::LEVELS), stream));
 }
 
 // The same with the table of borders in DEVICE memory (rdst_hip_sort_segments_device_offsets): dev_offsets holds
@@ -222,10 +224,9 @@ template <typename T, typename Off>
 void sort_segments_device_offsets(T* dev_keys, std::size_t len, const Off* dev_offsets, std::size_t n_segments, void* dev_scratch,
                                   std::size_t scratch_bytes, T* dev_tmp = nullptr, std::size_t tmp_elems = 0, void* stream = nullptr) {
     static_assert(std::is_unsigned<Off>::value && (sizeof(Off) == 4 || sizeof(Off) == 8), "offsets are 4- or 8-byte unsigned integers");
-    const int rc = rdst_hip_sort_segments_device_offsets(dev_keys, dev_tmp, tmp_elems, len, dev_offsets, sizeof(Off), n_segments, sizeof(T),
-                                                         RadixKey<T>::kind, static_cast<std::uint32_t>(RadixKey<T>::LEVELS), dev_scratch,
-                                                         scratch_bytes, stream);
-    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+    detail::check(rdst_hip_sort_segments_device_offsets(dev_keys, dev_tmp, tmp_elems, len, dev_offsets, sizeof(Off), n_segments, sizeof(T),
+                                                        RadixKey<T>::kind, static_cast<std::uint32_t>(RadixKey<T>::LEVELS), dev_scratch,
+                                                        scratch_bytes, stream));
 }
 // Key-value form (rdst_hip_sort_segments_pairs_device_offsets): 4- or 8-byte keys and values; equal keys keep their order.
 template <typename T, typename V, typename Off>
@@ -234,11 +235,10 @@ void sort_segments_pairs_device_offsets(T* dev_keys, V* dev_vals, std::size_t le
                                         std::size_t tmp_elems = 0, void* stream = nullptr) {
     static_assert(std::is_unsigned<Off>::value && (sizeof(Off) == 4 || sizeof(Off) == 8), "offsets are 4- or 8-byte unsigned integers");
     static_assert(std::is_trivially_copyable<V>::value, "values are moved as bytes");
-    const int rc = rdst_hip_sort_segments_pairs_device_offsets(dev_keys, dev_vals, dev_tmp_keys, dev_tmp_vals, tmp_elems, len, dev_offsets,
-                                                               sizeof(Off), n_segments, sizeof(T), RadixKey<T>::kind,
-                                                               static_cast<std::uint32_t>(RadixKey<T>::LEVELS), sizeof(V), dev_scratch,
-                                                               scratch_bytes, stream);
-    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+    detail::check(rdst_hip_sort_segments_pairs_device_offsets(dev_keys, dev_vals, dev_tmp_keys, dev_tmp_vals, tmp_elems, len, dev_offsets,
+                                                              sizeof(Off), n_segments, sizeof(T), RadixKey<T>::kind,
+                                                              static_cast<std::uint32_t>(RadixKey<T>::LEVELS), sizeof(V), dev_scratch,
+                                                              scratch_bytes, stream));
 }
 
 // Device offsets with no host involvement for segments of ANY length (rdst_hip_sort_segments_device_offsets_nowait): segments
@@ -258,10 +258,9 @@ template <typename T, typename Off>
 void sort_segments_device_offsets_nowait(T* dev_keys, T* dev_tmp, std::size_t len, const Off* dev_offsets, std::size_t n_segments,
                                          void* dev_scratch, std::size_t scratch_bytes, void* stream = nullptr) {
     static_assert(std::is_unsigned<Off>::value && (sizeof(Off) == 4 || sizeof(Off) == 8), "offsets are 4- or 8-byte unsigned integers");
-    const int rc = rdst_hip_sort_segments_device_offsets_nowait(dev_keys, dev_tmp, len, dev_offsets, sizeof(Off), n_segments, sizeof(T),
-                                                                RadixKey<T>::kind, static_cast<std::uint32_t>(RadixKey<T>::LEVELS), dev_scratch,
-                                                                scratch_bytes, stream);
-    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+    detail::check(rdst_hip_sort_segments_device_offsets_nowait(dev_keys, dev_tmp, len, dev_offsets, sizeof(Off), n_segments, sizeof(T),
+                                                               RadixKey<T>::kind, static_cast<std::uint32_t>(RadixKey<T>::LEVELS), dev_scratch,
+                                                               scratch_bytes, stream));
 }
 // Key-value form (rdst_hip_sort_segments_pairs_device_offsets_nowait): 4- or 8-byte keys and values; equal keys keep their order.
 template <typename T, typename V, typename Off>
@@ -269,11 +268,10 @@ void sort_segments_device_offsets_nowait(T* dev_keys, V* dev_vals, T* dev_tmp_ke
                                          std::size_t n_segments, void* dev_scratch, std::size_t scratch_bytes, void* stream = nullptr) {
     static_assert(std::is_unsigned<Off>::value && (sizeof(Off) == 4 || sizeof(Off) == 8), "offsets are 4- or 8-byte unsigned integers");
     static_assert(std::is_trivially_copyable<V>::value, "values are moved as bytes");
-    const int rc = rdst_hip_sort_segments_pairs_device_offsets_nowait(dev_keys, dev_vals, dev_tmp_keys, dev_tmp_vals, len, dev_offsets, sizeof(Off),
-                                                                      n_segments, sizeof(T), RadixKey<T>::kind,
-                                                                      static_cast<std::uint32_t>(RadixKey<T>::LEVELS), sizeof(V), dev_scratch,
-                                                                      scratch_bytes, stream);
-    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+    detail::check(rdst_hip_sort_segments_pairs_device_offsets_nowait(dev_keys, dev_vals, dev_tmp_keys, dev_tmp_vals, len, dev_offsets, sizeof(Off),
+                                                                     n_segments, sizeof(T), RadixKey<T>::kind,
+                                                                     static_cast<std::uint32_t>(RadixKey<T>::LEVELS), sizeof(V), dev_scratch,
+                                                                     scratch_bytes, stream));
 }
 
 // One DEVICE-resident slice whose length lives in device memory too (rdst_hip_sort_device_devlen): the first *dev_len of
@@ -284,9 +282,8 @@ void sort_segments_device_offsets_nowait(T* dev_keys, V* dev_vals, T* dev_tmp_ke
 template <typename T, typename Len>
 void sort_device_devlen(T* dev_keys, T* dev_tmp, std::size_t capacity, const Len* dev_len, void* stream = nullptr) {
     static_assert(std::is_unsigned<Len>::value && (sizeof(Len) == 4 || sizeof(Len) == 8), "the length is a 4- or 8-byte unsigned integer");
-    const int rc = rdst_hip_sort_device_devlen(dev_keys, dev_tmp, capacity, dev_len, sizeof(Len), sizeof(T), RadixKey<T>::kind,
-                                               static_cast<std::uint32_t>(RadixKey<T>::LEVELS), stream);
-    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+    detail::check(rdst_hip_sort_device_devlen(dev_keys, dev_tmp, capacity, dev_len, sizeof(Len), sizeof(T), RadixKey<T>::kind,
+                                              static_cast<std::uint32_t>(RadixKey<T>::LEVELS), stream));
 }
 // Key-value form (rdst_hip_sort_pairs_device_devlen): 4- or 8-byte keys and values; equal keys keep their order.
 template <typename T, typename V, typename Len>
@@ -294,9 +291,8 @@ void sort_pairs_device_devlen(T* dev_keys, V* dev_vals, T* dev_tmp_keys, V* dev_
                               void* stream = nullptr) {
     static_assert(std::is_unsigned<Len>::value && (sizeof(Len) == 4 || sizeof(Len) == 8), "the length is a 4- or 8-byte unsigned integer");
     static_assert(std::is_trivially_copyable<V>::value, "values are moved as bytes");
-    const int rc = rdst_hip_sort_pairs_device_devlen(dev_keys, dev_vals, dev_tmp_keys, dev_tmp_vals, capacity, dev_len, sizeof(Len), sizeof(T),
-                                                     RadixKey<T>::kind, static_cast<std::uint32_t>(RadixKey<T>::LEVELS), sizeof(V), stream);
-    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+    detail::check(rdst_hip_sort_pairs_device_devlen(dev_keys, dev_vals, dev_tmp_keys, dev_tmp_vals, capacity, dev_len, sizeof(Len), sizeof(T),
+                                                    RadixKey<T>::kind, static_cast<std::uint32_t>(RadixKey<T>::LEVELS), sizeof(V), stream));
 }
 
 // Partial sort of one DEVICE-resident slice (rdst_hip_topk_device): dev_out_keys[0..k) receives the k keys that
@@ -316,18 +312,16 @@ std::size_t topk_scratch_bytes(std::size_t len, std::size_t k, std::size_t cand_
 template <typename T>
 void topk_device(const T* dev_keys, std::size_t len, std::size_t k, T* dev_out_keys, void* dev_scratch, std::size_t scratch_bytes,
                  bool largest = false, std::size_t cand_capacity = 0, void* stream = nullptr) {
-    const int rc = rdst_hip_topk_device(dev_keys, len, k, dev_out_keys, nullptr, 0, dev_scratch, scratch_bytes, cand_capacity, sizeof(T),
-                                        RadixKey<T>::kind, static_cast<std::uint32_t>(RadixKey<T>::LEVELS), largest ? RDST_TOPK_LARGEST : 0u, stream);
-    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+    detail::check(rdst_hip_topk_device(dev_keys, len, k, dev_out_keys, nullptr, 0, dev_scratch, scratch_bytes, cand_capacity, sizeof(T),
+                                       RadixKey<T>::kind, static_cast<std::uint32_t>(RadixKey<T>::LEVELS), largest ? RDST_TOPK_LARGEST : 0u, stream));
 }
 template <typename T, typename Idx>
 void topk_device(const T* dev_keys, std::size_t len, std::size_t k, T* dev_out_keys, Idx* dev_out_index, void* dev_scratch,
                  std::size_t scratch_bytes, bool largest = false, std::size_t cand_capacity = 0, void* stream = nullptr) {
     static_assert(std::is_unsigned<Idx>::value && (sizeof(Idx) == 4 || sizeof(Idx) == 8), "positions are 4- or 8-byte unsigned integers");
-    const int rc = rdst_hip_topk_device(dev_keys, len, k, dev_out_keys, dev_out_index, sizeof(Idx), dev_scratch, scratch_bytes, cand_capacity,
-                                        sizeof(T), RadixKey<T>::kind, static_cast<std::uint32_t>(RadixKey<T>::LEVELS),
-                                        largest ? RDST_TOPK_LARGEST : 0u, stream);
-    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+    detail::check(rdst_hip_topk_device(dev_keys, len, k, dev_out_keys, dev_out_index, sizeof(Idx), dev_scratch, scratch_bytes, cand_capacity,
+                                       sizeof(T), RadixKey<T>::kind, static_cast<std::uint32_t>(RadixKey<T>::LEVELS),
+                                       largest ? RDST_TOPK_LARGEST : 0u, stream));
 }
 
 // DEVICE-resident [u8; N] rows (src/radix_key_impl.rs:78-85) and DEVICE-resident structs ordered by a described key
@@ -340,16 +334,14 @@ template <std::size_t N>
 void sort_bytes_device_nowait(std::array<std::uint8_t, N>* dev_rows, std::size_t n, void* dev_scratch, std::size_t scratch_bytes,
                               void* stream = nullptr) {
     static_assert(N >= 1 && N <= RDST_BYTES_NOWAIT_MAX_N, "the nowait entry takes [u8; N] keys with N in 1..RDST_BYTES_NOWAIT_MAX_N");
-    const int rc = rdst_hip_sort_bytes_device_nowait(dev_rows, n, static_cast<std::uint32_t>(N), dev_scratch, scratch_bytes, stream);
-    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+    detail::check(rdst_hip_sort_bytes_device_nowait(dev_rows, n, static_cast<std::uint32_t>(N), dev_scratch, scratch_bytes, stream));
 }
 template <typename T>
 void sort_records_by_device_nowait(T* dev_records, std::size_t n, std::initializer_list<rdst_key_field> fields, void* dev_scratch,
                                    std::size_t scratch_bytes, void* stream = nullptr) {
     static_assert(std::is_trivially_copyable<T>::value, "rows are moved as bytes");
-    const int rc = rdst_hip_sort_records_by_fields_device_nowait(dev_records, n, sizeof(T), fields.begin(),
-                                                                 static_cast<std::uint32_t>(fields.size()), dev_scratch, scratch_bytes, stream);
-    if (rc != RDST_OK) throw Error(rc, rdst_hip_last_error());
+    detail::check(rdst_hip_sort_records_by_fields_device_nowait(dev_records, n, sizeof(T), fields.begin(),
+                                                                static_cast<std::uint32_t>(fields.size()), dev_scratch, scratch_bytes, stream));
 }
 
 }  // namespace rdst

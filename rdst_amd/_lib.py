@@ -22,69 +22,6 @@ RDST_STAGE_SEGMENTS_TILED = 14   # rdst_stage: the tiled route of the nowait ent
 RDST_STAGE_TOPK = 15       # rdst_stage: one select level of the partial sort (level in bits 8..15; 0xFF: the collection pass)
 RDST_TOPK_LARGEST = 1      # rdst_hip_topk_device flags: the k largest, in descending order
 
-# every symbol include/rdst_hip.h declares; tests check that the library exports all of them
-SYMBOLS = (
-    "rdst_hip_sort",
-    "rdst_hip_sort_device",
-    "rdst_hip_sort_device_lowmem",
-    "rdst_hip_partition_device",
-    "rdst_regions_plan",
-    "rdst_hip_host_timing",
-    "rdst_hip_sort_pairs_device",
-    "rdst_hip_sort_device_devlen",
-    "rdst_hip_sort_pairs_device_devlen",
-    "rdst_hip_topk_device",
-    "rdst_hip_topk_scratch_bytes",
-    "rdst_hip_topk_limits",
-    "rdst_hip_debug_topk_state",
-    "rdst_hip_sort_segments_device",
-    "rdst_hip_sort_segments_pairs_device",
-    "rdst_hip_sort_segments_limits",
-    "rdst_segments_plan",
-    "rdst_hip_sort_segments_device_offsets",
-    "rdst_hip_sort_segments_pairs_device_offsets",
-    "rdst_hip_sort_segments_device_offsets_scratch_bytes",
-    "rdst_hip_sort_segments_device_offsets_nowait",
-    "rdst_hip_sort_segments_pairs_device_offsets_nowait",
-    "rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes",
-    "rdst_hip_debug_segments_plan_device",
-    "rdst_hip_sort_records",
-    "rdst_hip_sort_bytes_device",
-    "rdst_hip_sort_bytes_scratch_bytes",
-    "rdst_hip_sort_bytes_device_nowait",
-    "rdst_hip_sort_records_by_fields",
-    "rdst_hip_sort_records_by_fields_device",
-    "rdst_hip_sort_records_by_fields_scratch_bytes",
-    "rdst_hip_sort_records_by_fields_device_nowait",
-    "rdst_hip_pack_fields_device",
-    "rdst_hip_device_status",
-    "rdst_hip_level_counts",
-    "rdst_hip_all_level_counts",
-    "rdst_hip_scatter_level",
-    "rdst_hip_split_top_level_device",
-    "rdst_hip_split_top16_device",
-    "rdst_pick_algorithm",
-    "rdst_hip_workspace_bytes",
-    "rdst_hip_release_workspace",
-    "rdst_hip_set_tuning",
-    "rdst_hip_set_chain_split",
-    "rdst_hip_set_fast_rank",
-    "rdst_hip_set_small_sort",
-    "rdst_hip_set_profiling",
-    "rdst_hip_profile_runs",
-    "rdst_hip_profile_run",
-    "rdst_hip_profile_run_stages",
-    "rdst_hip_set_hybrid",
-    "rdst_hip_last_route",
-    "rdst_hip_debug_raise_device_error",
-    "rdst_hip_debug_last_sample",
-    "rdst_hip_stream_copy",
-    "rdst_hip_stream_read",
-    "rdst_hip_stream_fill",
-    "rdst_hip_last_error",
-    "rdst_hip_abi_version",
-)
-
 
 class TuningParamsC(ctypes.Structure):
     _fields_ = [
@@ -116,6 +53,78 @@ class RdstHipError(RuntimeError):
         self.code = code
 
 
+def _signatures():
+    vp, u64, u32, ci = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int
+    u64p, u32p, u8p, f32p = ctypes.POINTER(u64), ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_float)
+    opts, kfp, items = ctypes.POINTER(HipOptsC), ctypes.POINTER(KeyFieldC), ctypes.POINTER(SegmentItemC)
+    return {
+        "rdst_hip_sort": (ci, [vp, u64, u32, ci, u32, opts]),
+        "rdst_hip_sort_device": (ci, [vp, vp, u64, u32, ci, u32, vp]),
+        "rdst_hip_sort_device_lowmem": (ci, [vp, u64, u32, ci, u32, vp, u64, vp]),
+        "rdst_hip_partition_device": (ci, [vp, u64, u32, ci, u32, u32, vp, u64, u64p, vp]),
+        "rdst_regions_plan": (ci, None),
+        "rdst_hip_host_timing": (ci, [f32p, f32p, f32p]),
+        "rdst_hip_sort_pairs_device": (ci, [vp, vp, vp, vp, u64, u32, ci, u32, u32, vp]),
+        "rdst_hip_sort_device_devlen": (ci, [vp, vp, u64, vp, u32, u32, ci, u32, vp]),
+        "rdst_hip_sort_pairs_device_devlen": (ci, [vp, vp, vp, vp, u64, vp, u32, u32, ci, u32, u32, vp]),
+        "rdst_hip_topk_device": (ci, [vp, u64, u64, vp, vp, u32, vp, u64, u64, u32, ci, u32, u32, vp]),
+        "rdst_hip_topk_scratch_bytes": (u64, [u64, u64, u32, u32, u64]),
+        "rdst_hip_topk_limits": (ci, [u32, u32, u32p]),
+        "rdst_hip_debug_topk_state": (ci, [vp, vp, u64p]),
+        "rdst_hip_sort_segments_device": (ci, [vp, vp, u64, u64, u64p, u64, u32, ci, u32, vp]),
+        "rdst_hip_sort_segments_pairs_device": (ci, [vp, vp, vp, vp, u64, u64, u64p, u64, u32, ci, u32, u32, vp]),
+        "rdst_hip_sort_segments_limits": (ci, [u32, u32, u32p]),
+        "rdst_segments_plan": (ci, [u64p, u64, u64, u32, u32, items, u64, u64p, u64p]),
+        "rdst_hip_sort_segments_device_offsets": (ci, [vp, vp, u64, u64, vp, u32, u64, u32, ci, u32, vp, u64, vp]),
+        "rdst_hip_sort_segments_pairs_device_offsets": (ci, [vp, vp, vp, vp, u64, u64, vp, u32, u64, u32, ci, u32, u32, vp, u64, vp]),
+        "rdst_hip_sort_segments_device_offsets_scratch_bytes": (u64, [u64]),
+        "rdst_hip_sort_segments_device_offsets_nowait": (ci, [vp, vp, u64, vp, u32, u64, u32, ci, u32, vp, u64, vp]),
+        "rdst_hip_sort_segments_pairs_device_offsets_nowait": (ci, [vp, vp, vp, vp, u64, vp, u32, u64, u32, ci, u32, u32, vp, u64, vp]),
+        "rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes": (u64, [u64, u64, u32, u32]),
+        "rdst_hip_debug_segments_plan_device": (ci, [vp, u32, u64, u64, u32, u32, vp, u64, items, u64, u64p, u64p, u32p, vp]),
+        "rdst_hip_sort_records": (ci, [vp, u64, u32, u32, u32, ci, opts]),
+        "rdst_hip_sort_bytes_device": (ci, [vp, u64, u32, vp, u64, vp]),
+        "rdst_hip_sort_bytes_scratch_bytes": (u64, [u64, u32]),
+        "rdst_hip_sort_bytes_device_nowait": (ci, [vp, u64, u32, vp, u64, vp]),
+        "rdst_hip_sort_records_by_fields": (ci, [vp, u64, u32, kfp, u32, opts]),
+        "rdst_hip_sort_records_by_fields_device": (ci, [vp, u64, u32, kfp, u32, vp, u64, vp]),
+        "rdst_hip_sort_records_by_fields_scratch_bytes": (u64, [u64, u32, kfp, u32]),
+        "rdst_hip_sort_records_by_fields_device_nowait": (ci, [vp, u64, u32, kfp, u32, vp, u64, vp]),
+        "rdst_hip_pack_fields_device": (ci, [vp, u64, u32, kfp, u32, vp, vp, vp]),
+        "rdst_hip_device_status": (ci, [vp]),
+        "rdst_hip_level_counts": (ci, [vp, u64, u32, ci, u32, u64p, u8p, u8p, u8p, vp]),
+        "rdst_hip_all_level_counts": (ci, [vp, u64, u32, ci, u32, u64p, vp]),
+        "rdst_hip_scatter_level": (ci, [vp, vp, u64, u32, ci, u32, u64p, vp]),
+        "rdst_hip_split_top_level_device": (ci, [vp, vp, u64, u32, ci, vp, vp]),
+        "rdst_hip_split_top16_device": (ci, [vp, vp, u64, u32, ci, vp, vp]),
+        "rdst_pick_algorithm": (ci, [ci, ctypes.POINTER(TuningParamsC), u64p, u64]),
+        "rdst_hip_workspace_bytes": (u64, [u64, u32]),
+        "rdst_hip_release_workspace": (ci, []),
+        "rdst_hip_set_tuning": (ci, [ci, ci]),
+        "rdst_hip_set_chain_split": (ci, [ci]),
+        "rdst_hip_set_fast_rank": (ci, [ci]),
+        "rdst_hip_set_small_sort": (ci, [ci]),
+        "rdst_hip_set_profiling": (ci, [ci]),
+        "rdst_hip_profile_runs": (ci, None),
+        "rdst_hip_profile_run": (ci, [ci, f32p, u32, u32p]),
+        "rdst_hip_profile_run_stages": (ci, [ci, u32p, u32, u32p]),
+        "rdst_hip_set_hybrid": (ci, [ci, u64]),
+        "rdst_hip_last_route": (ci, [vp, u32p]),
+        "rdst_hip_debug_raise_device_error": (ci, [u32, vp]),
+        "rdst_hip_debug_last_sample": (ci, [vp, u32p]),
+        "rdst_hip_stream_copy": (ci, [vp, vp, u64, vp]),
+        "rdst_hip_stream_read": (ci, [vp, u64, vp]),
+        "rdst_hip_stream_fill": (ci, [vp, u64, vp]),
+        "rdst_hip_last_error": (ctypes.c_char_p, None),
+        "rdst_hip_abi_version": (ci, None),
+    }
+
+
+# every symbol include/rdst_hip.h declares -> (restype, argtypes; None: not declared to ctypes, the caller converts); tests
+# check that the library exports all of them
+SIGNATURES = _signatures()
+SYMBOLS = tuple(SIGNATURES)
+
 _lib = None
 
 
@@ -133,77 +142,11 @@ def load():
     except Exception:  # pragma: no cover - torch is optional for host-only use
         pass
     lib = ctypes.CDLL(LIB_PATH, mode=ctypes.RTLD_GLOBAL)
-    vp, u64, u32, ci = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int
-    u64p, u8p = ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint8)
-    lib.rdst_hip_sort.argtypes = [vp, u64, u32, ci, u32, ctypes.POINTER(HipOptsC)]
-    lib.rdst_hip_host_timing.argtypes = [ctypes.POINTER(ctypes.c_float)] * 3
-    lib.rdst_hip_sort_device_lowmem.argtypes = [vp, u64, u32, ci, u32, vp, u64, vp]
-    lib.rdst_hip_partition_device.argtypes = [vp, u64, u32, ci, u32, u32, vp, u64, u64p, vp]
-    lib.rdst_hip_sort_device.argtypes = [vp, vp, u64, u32, ci, u32, vp]
-    lib.rdst_hip_sort_pairs_device.argtypes = [vp, vp, vp, vp, u64, u32, ci, u32, u32, vp]
-    lib.rdst_hip_sort_device_devlen.argtypes = [vp, vp, u64, vp, u32, u32, ci, u32, vp]
-    lib.rdst_hip_sort_pairs_device_devlen.argtypes = [vp, vp, vp, vp, u64, vp, u32, u32, ci, u32, u32, vp]
-    lib.rdst_hip_topk_device.argtypes = [vp, u64, u64, vp, vp, u32, vp, u64, u64, u32, ci, u32, u32, vp]
-    lib.rdst_hip_topk_scratch_bytes.argtypes = [u64, u64, u32, u32, u64]
-    lib.rdst_hip_topk_scratch_bytes.restype = u64
-    lib.rdst_hip_topk_limits.argtypes = [u32, u32, ctypes.POINTER(u32)]
-    lib.rdst_hip_debug_topk_state.argtypes = [vp, vp, u64p]
-    lib.rdst_hip_sort_segments_device.argtypes = [vp, vp, u64, u64, u64p, u64, u32, ci, u32, vp]
-    lib.rdst_hip_sort_segments_pairs_device.argtypes = [vp, vp, vp, vp, u64, u64, u64p, u64, u32, ci, u32, u32, vp]
-    lib.rdst_hip_sort_segments_limits.argtypes = [u32, u32, ctypes.POINTER(u32)]
-    lib.rdst_segments_plan.argtypes = [u64p, u64, u64, u32, u32, ctypes.POINTER(SegmentItemC), u64, u64p, u64p]
-    lib.rdst_hip_sort_segments_device_offsets.argtypes = [vp, vp, u64, u64, vp, u32, u64, u32, ci, u32, vp, u64, vp]
-    lib.rdst_hip_sort_segments_pairs_device_offsets.argtypes = [vp, vp, vp, vp, u64, u64, vp, u32, u64, u32, ci, u32, u32, vp, u64, vp]
-    lib.rdst_hip_sort_segments_device_offsets_scratch_bytes.argtypes = [u64]
-    lib.rdst_hip_sort_segments_device_offsets_scratch_bytes.restype = u64
-    lib.rdst_hip_sort_segments_device_offsets_nowait.argtypes = [vp, vp, u64, vp, u32, u64, u32, ci, u32, vp, u64, vp]
-    lib.rdst_hip_sort_segments_pairs_device_offsets_nowait.argtypes = [vp, vp, vp, vp, u64, vp, u32, u64, u32, ci, u32, u32, vp, u64, vp]
-    lib.rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes.argtypes = [u64, u64, u32, u32]
-    lib.rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes.restype = u64
-    lib.rdst_hip_debug_segments_plan_device.argtypes = [vp, u32, u64, u64, u32, u32, vp, u64, ctypes.POINTER(SegmentItemC), u64, u64p, u64p,
-                                                        ctypes.POINTER(u32), vp]
-    lib.rdst_hip_sort_records.argtypes = [vp, u64, u32, u32, u32, ci, ctypes.POINTER(HipOptsC)]
-    lib.rdst_hip_sort_bytes_device.argtypes = [vp, u64, u32, vp, u64, vp]
-    lib.rdst_hip_sort_bytes_device_nowait.argtypes = [vp, u64, u32, vp, u64, vp]
-    lib.rdst_hip_sort_bytes_scratch_bytes.argtypes = [u64, u32]
-    lib.rdst_hip_sort_bytes_scratch_bytes.restype = u64
-    kfp = ctypes.POINTER(KeyFieldC)
-    lib.rdst_hip_sort_records_by_fields.argtypes = [vp, u64, u32, kfp, u32, ctypes.POINTER(HipOptsC)]
-    lib.rdst_hip_sort_records_by_fields_device.argtypes = [vp, u64, u32, kfp, u32, vp, u64, vp]
-    lib.rdst_hip_sort_records_by_fields_device_nowait.argtypes = [vp, u64, u32, kfp, u32, vp, u64, vp]
-    lib.rdst_hip_sort_records_by_fields_scratch_bytes.argtypes = [u64, u32, kfp, u32]
-    lib.rdst_hip_sort_records_by_fields_scratch_bytes.restype = u64
-    lib.rdst_hip_pack_fields_device.argtypes = [vp, u64, u32, kfp, u32, vp, vp, vp]
-    lib.rdst_hip_device_status.argtypes = [vp]
-    lib.rdst_hip_level_counts.argtypes = [vp, u64, u32, ci, u32, u64p, u8p, u8p, u8p, vp]
-    lib.rdst_hip_all_level_counts.argtypes = [vp, u64, u32, ci, u32, u64p, vp]
-    lib.rdst_hip_scatter_level.argtypes = [vp, vp, u64, u32, ci, u32, u64p, vp]
-    lib.rdst_hip_split_top_level_device.argtypes = [vp, vp, u64, u32, ci, vp, vp]
-    lib.rdst_hip_split_top16_device.argtypes = [vp, vp, u64, u32, ci, vp, vp]
-    lib.rdst_pick_algorithm.argtypes = [ci, ctypes.POINTER(TuningParamsC), u64p, u64]
-    lib.rdst_hip_workspace_bytes.argtypes = [u64, u32]
-    lib.rdst_hip_workspace_bytes.restype = u64
-    lib.rdst_hip_release_workspace.argtypes = []
-    lib.rdst_hip_set_tuning.argtypes = [ci, ci]
-    lib.rdst_hip_set_chain_split.argtypes = [ci]
-    lib.rdst_hip_set_fast_rank.argtypes = [ci]
-    lib.rdst_hip_set_small_sort.argtypes = [ci]
-    lib.rdst_hip_set_profiling.argtypes = [ci]
-    lib.rdst_hip_profile_run.argtypes = [ci, ctypes.POINTER(ctypes.c_float), u32, ctypes.POINTER(u32)]
-    lib.rdst_hip_profile_run_stages.argtypes = [ci, ctypes.POINTER(u32), u32, ctypes.POINTER(u32)]
-    lib.rdst_hip_set_hybrid.argtypes = [ci, u64]
-    lib.rdst_hip_last_route.argtypes = [vp, ctypes.POINTER(u32)]
-    lib.rdst_hip_debug_raise_device_error.argtypes = [u32, vp]
-    lib.rdst_hip_debug_last_sample.argtypes = [vp, ctypes.POINTER(u32)]
-    lib.rdst_hip_stream_copy.argtypes = [vp, vp, u64, vp]
-    lib.rdst_hip_stream_read.argtypes = [vp, u64, vp]
-    lib.rdst_hip_stream_fill.argtypes = [vp, u64, vp]
-    lib.rdst_hip_last_error.restype = ctypes.c_char_p
-    for name in SYMBOLS:
-        if name not in ("rdst_hip_workspace_bytes", "rdst_hip_sort_bytes_scratch_bytes", "rdst_hip_sort_records_by_fields_scratch_bytes",
-                        "rdst_hip_sort_segments_device_offsets_scratch_bytes", "rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes",
-                        "rdst_hip_topk_scratch_bytes", "rdst_hip_last_error"):
-            getattr(lib, name).restype = ctypes.c_int
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype = restype
+        if argtypes is not None:
+            fn.argtypes = argtypes
     _lib = lib
     return lib
 

@@ -51,11 +51,6 @@ def _is_torch_tensor(x):
     return type(x).__module__.startswith("torch") and hasattr(x, "data_ptr")
 
 
-def _stream_handle(tensor):
-    import torch
-    return ctypes.c_void_p(torch.cuda.current_stream(tensor.device).cuda_stream)
-
-
 def _wide(key):
     return key in ("u128", "i128")
 
@@ -65,40 +60,116 @@ def _check_wide_shape(shape, itemsize):
         raise ValueError("a 128-bit key container has shape (n, 2) with 8-byte limbs [low, high]")
 
 
+def _check_bytes_rows(shape, dtype_ok):
+    if len(shape) != 2 or not dtype_ok or not 1 <= shape[1] <= _lib.RDST_BYTES_MAX_N:
+        raise ValueError(f"[u8; N] keys: a uint8 container of shape (n, N) with N in 1..{_lib.RDST_BYTES_MAX_N}")
+
+
+# ---- what every tensor wrapper is made of: checked operands -> buffers -> one call ----
+
+def _current_stream(device=None):
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def _stream_handle(tensor):
+    return _current_stream(tensor.device)
+
+
+def _ptr(t, empty_is_null=False):
+    return ctypes.c_void_p(t.data_ptr() if t is not None and (t.numel() or not empty_is_null) else None)
+
+
+def _on_device(name, t):
+    if not t.is_cuda:
+        raise ValueError(f"{name} needs a tensor on a HIP device")
+
+
+def _keys_operand(name, keys, key=None):
+    """the keys of a tensor wrapper, checked: (kind, nbytes, levels, n, per_key)"""
+    _on_device(name, keys)
+    if _wide(key):
+        _check_wide_shape(tuple(keys.shape), keys.element_size())
+    if keys.dim() != (2 if _wide(key) else 1) or not keys.is_contiguous():
+        raise ValueError("keys must be a contiguous 1-D tensor (rdst sorts a slice)")
+    kind, nbytes, levels = key_info(key if key else keys.dtype)
+    n = keys.numel() * keys.element_size() // nbytes
+    return kind, nbytes, levels, n, (keys.numel() // n if n else 1)   # per_key: container elements per key (2 for the 128-bit limbs)
+
+
+def _mismatch(t, like):
+    """a tmp (tmp_values) tensor that cannot stand in for `like`, whatever its length"""
+    return t.dtype != like.dtype or not t.is_contiguous() or t.device != like.device
+
+
+def _scratch(scratch, need, device, whose="keys"):
+    """(scratch, its bytes) for an entry that asks for `need` bytes: the caller's tensor, checked, or a fresh one"""
+    import torch
+    if scratch is None:
+        return torch.empty(max(need, 1), dtype=torch.uint8, device=device), need   # the caching allocator hands out 512-byte aligned blocks
+    if scratch.device != device or not scratch.is_contiguous() or scratch.numel() * scratch.element_size() < need:
+        raise ValueError(f"scratch must be a contiguous tensor on the {whose}' device with at least {need} bytes")
+    return scratch, scratch.numel() * scratch.element_size()
+
+
+def _call(tensor, check, entry, *args):
+    """the tail of a tensor wrapper: `entry(*args, stream)` on the tensor's device and current stream, then, with `check`, the
+    blocking look at the status; the blocking hooks, which wait inside `entry`, pass check=False"""
+    import torch
+    lib = _lib.load()
+    with torch.cuda.device(tensor.device):
+        s = _stream_handle(tensor)
+        _lib.check(getattr(lib, entry)(*args, s))
+        if check:
+            _lib.check(lib.rdst_hip_device_status(s))
+
+
+_WHOLE = object()   # the `length` of the plain wrappers: no device-resident length, all keys are sorted
+_LENGTH_DTYPES = {"int32": 4, "uint32": 4, "int64": 8, "uint64": 8}
+
+
+def _device_length(length, keys):
+    """the (pointer, len_bytes) arguments of a device-resident length, checked without looking at its value; none for _WHOLE"""
+    if length is _WHOLE:
+        return ()
+    name = str(getattr(length, "dtype", None)).replace("torch.", "")
+    if not _is_torch_tensor(length) or name not in _LENGTH_DTYPES or length.numel() != 1 or not length.is_contiguous():
+        raise ValueError("length must be a contiguous one-element tensor of dtype int32, int64, uint32 or uint64")
+    if length.device != keys.device:
+        raise ValueError("length must live on the keys' device")
+    return _ptr(length), _LENGTH_DTYPES[name]
+
+
+def _sort_keys(name, keys, length, tmp, check, key):
+    """sort_device_tensor (length: _WHOLE) and sort_device_devlen_tensor"""
+    import torch
+    kind, nbytes, levels, n, _per_key = _keys_operand(name, keys, key)
+    devlen = _device_length(length, keys)
+    if n <= 1:
+        return
+    if tmp is None:
+        tmp = torch.empty_like(keys)
+    elif _mismatch(tmp, keys) or tmp.numel() < keys.numel():
+        raise ValueError("tmp must be a contiguous tensor of the same dtype/device with at least len elements")
+    _call(keys, check, "rdst_hip_sort_device_devlen" if devlen else "rdst_hip_sort_device", _ptr(keys), _ptr(tmp), n, *devlen, nbytes, kind, levels)
+
+
 def sort_device_tensor(keys, tmp=None, check=True, key=None):
     """``rdst_hip_sort_device`` on a 1-D contiguous HIP tensor (``key="u128"/"i128"``: shape (n, 2)).  ``tmp``: optional scratch
     tensor of the same shape/dtype (allocated when omitted).  With ``check`` the call blocks
     and raises if a kernel reported failure; without it the sort stays asynchronous on the
     tensor's current stream (call :func:`device_status` later)."""
-    import torch
-    if not keys.is_cuda:
-        raise ValueError("sort_device_tensor needs a tensor on a HIP device")
-    if _wide(key):
-        _check_wide_shape(tuple(keys.shape), keys.element_size())
-    elif keys.dim() != 1:
-        raise ValueError("keys must be a contiguous 1-D tensor (rdst sorts a slice)")
-    if not keys.is_contiguous():
-        raise ValueError("keys must be a contiguous 1-D tensor (rdst sorts a slice)")
-    kind, nbytes, levels = key_info(key if key else keys.dtype)
-    n = keys.numel() * keys.element_size() // nbytes
-    if n <= 1:
-        return
-    if tmp is None:
-        tmp = torch.empty_like(keys)
-    elif tmp.dtype != keys.dtype or tmp.numel() < keys.numel() or not tmp.is_contiguous() or tmp.device != keys.device:
-        raise ValueError("tmp must be a contiguous tensor of the same dtype/device with at least len elements")
-    lib = _lib.load()
-    with torch.cuda.device(keys.device):
-        s = _stream_handle(keys)
-        _lib.check(lib.rdst_hip_sort_device(ctypes.c_void_p(keys.data_ptr()), ctypes.c_void_p(tmp.data_ptr()),
-                                            n, nbytes, kind, levels, s))
-        if check:
-            _lib.check(lib.rdst_hip_device_status(s))
+    _sort_keys("sort_device_tensor", keys, _WHOLE, tmp, check, key)
 
 
-def _check_bytes_rows(shape, dtype_ok):
-    if len(shape) != 2 or not dtype_ok or not 1 <= shape[1] <= _lib.RDST_BYTES_MAX_N:
-        raise ValueError(f"[u8; N] keys: a uint8 container of shape (n, N) with N in 1..{_lib.RDST_BYTES_MAX_N}")
+def sort_device_devlen_tensor(keys, length, tmp=None, check=True, key=None):
+    """``rdst_hip_sort_device_devlen``: :func:`sort_device_tensor` over the first ``m`` keys, where ``m`` is the value of
+    ``length`` — a one-element contiguous tensor on the keys' device (int32, int64, uint32 or uint64, read as unsigned) that is
+    read on the stream, never by the host: the kernel that produces it may still be running.  The capacity is the number of
+    keys (``key="u128"/"i128"``: rows); keys from ``m`` on are not touched.  ``m`` past the capacity changes nothing and
+    raises in :func:`device_status` (error bit 32).  The call only enqueues work on the tensor's current stream;
+    ``check=False`` makes no blocking call at all."""
+    _sort_keys("sort_device_devlen_tensor", keys, length, tmp, check, key)
 
 
 def sort_bytes_device_tensor(rows, scratch=None, check=True):
@@ -120,32 +191,19 @@ def sort_bytes_device_nowait_tensor(rows, scratch=None, check=True):
 
 def _sort_bytes_rows(name, entry, rows, scratch, check):
     import torch
-    if not rows.is_cuda:
-        raise ValueError(f"{name} needs a tensor on a HIP device")
+    _on_device(name, rows)
     _check_bytes_rows(tuple(rows.shape), rows.dtype == torch.uint8)
     if not rows.is_contiguous():
         raise ValueError("rows must be a contiguous (n, N) tensor")
     n, n_bytes = int(rows.shape[0]), int(rows.shape[1])
     if n <= 1:
         return
-    lib = _lib.load()
-    need = int(lib.rdst_hip_sort_bytes_scratch_bytes(n, n_bytes))
-    if scratch is None:
-        scratch = torch.empty(need, dtype=torch.uint8, device=rows.device)  # the caching allocator hands out 512-byte aligned blocks
-    elif scratch.device != rows.device or not scratch.is_contiguous() or scratch.numel() * scratch.element_size() < need:
-        raise ValueError(f"scratch must be a contiguous tensor on the rows' device with at least {need} bytes")
-    with torch.cuda.device(rows.device):
-        s = _stream_handle(rows)
-        _lib.check(getattr(lib, entry)(ctypes.c_void_p(rows.data_ptr()), n, n_bytes, ctypes.c_void_p(scratch.data_ptr()),
-                                       scratch.numel() * scratch.element_size(), s))
-        if check:
-            _lib.check(lib.rdst_hip_device_status(s))
+    scratch, sbytes = _scratch(scratch, int(_lib.load().rdst_hip_sort_bytes_scratch_bytes(n, n_bytes)), rows.device, "rows")
+    _call(rows, check, entry, _ptr(rows), n, n_bytes, _ptr(scratch), sbytes)
 
 
-def sort_pairs_device_tensor(keys, values, tmp_keys=None, tmp_values=None, check=True):
-    """``rdst_hip_sort_pairs_device``: sort the 1-D HIP tensor ``keys`` (4- or 8-byte built-in key type) in place
-    and permute ``values`` (4- or 8-byte elements, same length) with it.  Stable: equal keys keep their
-    input order (rdst promises none, src/radix_sort.rs:21-45)."""
+def _sort_pairs(keys, values, length, tmp_keys, tmp_values, check):
+    """sort_pairs_device_tensor (length: _WHOLE) and sort_pairs_device_devlen_tensor"""
     import torch
     if not (keys.is_cuda and values.is_cuda) or keys.device != values.device:
         raise ValueError("keys and values must live on the same HIP device")
@@ -155,102 +213,31 @@ def sort_pairs_device_tensor(keys, values, tmp_keys=None, tmp_values=None, check
         raise ValueError("keys and values must be contiguous")
     kind, nbytes, levels = key_info(keys.dtype)
     vbytes = values.element_size()
+    devlen = _device_length(length, keys)
     n = keys.numel()
     if n <= 1:
         return
     tmp_keys = torch.empty_like(keys) if tmp_keys is None else tmp_keys
     tmp_values = torch.empty_like(values) if tmp_values is None else tmp_values
     for t, ref in ((tmp_keys, keys), (tmp_values, values)):
-        if t.dtype != ref.dtype or t.numel() < n or not t.is_contiguous() or t.device != ref.device:
+        if _mismatch(t, ref) or t.numel() < n:
             raise ValueError("tmp tensors must match their originals in dtype, device and length")
-    lib = _lib.load()
-    with torch.cuda.device(keys.device):
-        s = _stream_handle(keys)
-        _lib.check(lib.rdst_hip_sort_pairs_device(ctypes.c_void_p(keys.data_ptr()), ctypes.c_void_p(values.data_ptr()),
-                                                  ctypes.c_void_p(tmp_keys.data_ptr()), ctypes.c_void_p(tmp_values.data_ptr()),
-                                                  n, nbytes, kind, levels, vbytes, s))
-        if check:
-            _lib.check(lib.rdst_hip_device_status(s))
+    _call(keys, check, "rdst_hip_sort_pairs_device_devlen" if devlen else "rdst_hip_sort_pairs_device", _ptr(keys), _ptr(values), _ptr(tmp_keys),
+          _ptr(tmp_values), n, *devlen, nbytes, kind, levels, vbytes)
 
 
-_LENGTH_DTYPES = {"int32": 4, "uint32": 4, "int64": 8, "uint64": 8}
-
-
-def _device_length(length, keys):
-    """len_bytes of a device-resident length, checked without looking at its value"""
-    name = str(getattr(length, "dtype", None)).replace("torch.", "")
-    if not _is_torch_tensor(length) or name not in _LENGTH_DTYPES or length.numel() != 1 or not length.is_contiguous():
-        raise ValueError("length must be a contiguous one-element tensor of dtype int32, int64, uint32 or uint64")
-    if length.device != keys.device:
-        raise ValueError("length must live on the keys' device")
-    return _LENGTH_DTYPES[name]
-
-
-def sort_device_devlen_tensor(keys, length, tmp=None, check=True, key=None):
-    """``rdst_hip_sort_device_devlen``: :func:`sort_device_tensor` over the first ``m`` keys, where ``m`` is the value of
-    ``length`` — a one-element contiguous tensor on the keys' device (int32, int64, uint32 or uint64, read as unsigned) that is
-    read on the stream, never by the host: the kernel that produces it may still be running.  The capacity is the number of
-    keys (``key="u128"/"i128"``: rows); keys from ``m`` on are not touched.  ``m`` past the capacity changes nothing and
-    raises in :func:`device_status` (error bit 32).  The call only enqueues work on the tensor's current stream;
-    ``check=False`` makes no blocking call at all."""
-    import torch
-    if not keys.is_cuda:
-        raise ValueError("sort_device_devlen_tensor needs a tensor on a HIP device")
-    if _wide(key):
-        _check_wide_shape(tuple(keys.shape), keys.element_size())
-    elif keys.dim() != 1:
-        raise ValueError("keys must be a contiguous 1-D tensor (rdst sorts a slice)")
-    if not keys.is_contiguous():
-        raise ValueError("keys must be a contiguous 1-D tensor (rdst sorts a slice)")
-    kind, nbytes, levels = key_info(key if key else keys.dtype)
-    len_bytes = _device_length(length, keys)
-    capacity = keys.numel() * keys.element_size() // nbytes
-    if capacity <= 1:
-        return
-    if tmp is None:
-        tmp = torch.empty_like(keys)
-    elif tmp.dtype != keys.dtype or tmp.numel() < keys.numel() or not tmp.is_contiguous() or tmp.device != keys.device:
-        raise ValueError("tmp must be a contiguous tensor of the same dtype/device with at least len elements")
-    lib = _lib.load()
-    with torch.cuda.device(keys.device):
-        s = _stream_handle(keys)
-        _lib.check(lib.rdst_hip_sort_device_devlen(ctypes.c_void_p(keys.data_ptr()), ctypes.c_void_p(tmp.data_ptr()), capacity,
-                                                   ctypes.c_void_p(length.data_ptr()), len_bytes, nbytes, kind, levels, s))
-        if check:
-            _lib.check(lib.rdst_hip_device_status(s))
+def sort_pairs_device_tensor(keys, values, tmp_keys=None, tmp_values=None, check=True):
+    """``rdst_hip_sort_pairs_device``: sort the 1-D HIP tensor ``keys`` (4- or 8-byte built-in key type) in place
+    and permute ``values`` (4- or 8-byte elements, same length) with it.  Stable: equal keys keep their
+    input order (rdst promises none, src/radix_sort.rs:21-45)."""
+    _sort_pairs(keys, values, _WHOLE, tmp_keys, tmp_values, check)
 
 
 def sort_pairs_device_devlen_tensor(keys, values, length, tmp_keys=None, tmp_values=None, check=True):
     """``rdst_hip_sort_pairs_device_devlen``: :func:`sort_pairs_device_tensor` over the first ``m`` pairs, ``m`` being the
     value of the device-resident ``length`` (see :func:`sort_device_devlen_tensor`); the capacity is ``keys.numel()``.
     Stable; keys and values from ``m`` on are not touched."""
-    import torch
-    if not (keys.is_cuda and values.is_cuda) or keys.device != values.device:
-        raise ValueError("keys and values must live on the same HIP device")
-    if keys.dim() != 1 or values.dim() != 1 or keys.numel() != values.numel():
-        raise ValueError("keys and values must be 1-D tensors of the same length")
-    if not (keys.is_contiguous() and values.is_contiguous()):
-        raise ValueError("keys and values must be contiguous")
-    kind, nbytes, levels = key_info(keys.dtype)
-    vbytes = values.element_size()
-    len_bytes = _device_length(length, keys)
-    capacity = keys.numel()
-    if capacity <= 1:
-        return
-    tmp_keys = torch.empty_like(keys) if tmp_keys is None else tmp_keys
-    tmp_values = torch.empty_like(values) if tmp_values is None else tmp_values
-    for t, ref in ((tmp_keys, keys), (tmp_values, values)):
-        if t.dtype != ref.dtype or t.numel() < capacity or not t.is_contiguous() or t.device != ref.device:
-            raise ValueError("tmp tensors must match their originals in dtype, device and length")
-    lib = _lib.load()
-    with torch.cuda.device(keys.device):
-        s = _stream_handle(keys)
-        _lib.check(lib.rdst_hip_sort_pairs_device_devlen(ctypes.c_void_p(keys.data_ptr()), ctypes.c_void_p(values.data_ptr()),
-                                                         ctypes.c_void_p(tmp_keys.data_ptr()), ctypes.c_void_p(tmp_values.data_ptr()),
-                                                         capacity, ctypes.c_void_p(length.data_ptr()), len_bytes, nbytes, kind, levels,
-                                                         vbytes, s))
-        if check:
-            _lib.check(lib.rdst_hip_device_status(s))
+    _sort_pairs(keys, values, length, tmp_keys, tmp_values, check)
 
 
 def topk_limits(dtype, index_bytes=0):
@@ -276,7 +263,7 @@ def topk_state(scratch):
     import torch
     out = (ctypes.c_uint64 * 4)()
     with torch.cuda.device(scratch.device):
-        _lib.check(_lib.load().rdst_hip_debug_topk_state(ctypes.c_void_p(scratch.data_ptr()), _stream_handle(scratch), out))
+        _lib.check(_lib.load().rdst_hip_debug_topk_state(_ptr(scratch), _stream_handle(scratch), out))   # (the stream is not its last argument)
     return {"levels": int(out[0]), "c_below": int(out[1]), "candidates": int(out[2]), "special": int(out[3])}
 
 
@@ -290,16 +277,7 @@ def topk_device_tensor(keys, k, largest=False, index=None, scratch=None, cand_ca
     gives the same result.  Returns ``(out_keys, out_index or None)``.  The call only enqueues work on the tensor's current
     stream; ``check=False`` makes no blocking call at all (kernel failures then surface in :func:`device_status`)."""
     import torch
-    if not keys.is_cuda:
-        raise ValueError("topk_device_tensor needs a tensor on a HIP device")
-    if _wide(key):
-        _check_wide_shape(tuple(keys.shape), keys.element_size())
-    elif keys.dim() != 1:
-        raise ValueError("keys must be a contiguous 1-D tensor (rdst sorts a slice)")
-    if not keys.is_contiguous():
-        raise ValueError("keys must be a contiguous 1-D tensor (rdst sorts a slice)")
-    kind, nbytes, levels = key_info(key if key else keys.dtype)
-    n = keys.numel() * keys.element_size() // nbytes
+    kind, nbytes, levels, n, _per_key = _keys_operand("topk_device_tensor", keys, key)
     k = int(k)
     if not 0 <= k <= n:
         raise ValueError("k must lie in 0..len")
@@ -310,17 +288,10 @@ def topk_device_tensor(keys, k, largest=False, index=None, scratch=None, cand_ca
     out_index = None if index is None else torch.empty(k, dtype=index, device=keys.device)
     if k == 0:
         return out_keys, out_index
-    lib = _lib.load()
-    need = int(lib.rdst_hip_topk_scratch_bytes(n, k, nbytes, index_bytes, int(cand_capacity)))
-    with torch.cuda.device(keys.device):
-        scratch, sbytes = _segments_scratch(scratch, need, keys.device)
-        s = _stream_handle(keys)
-        _lib.check(lib.rdst_hip_topk_device(ctypes.c_void_p(keys.data_ptr()), n, k, ctypes.c_void_p(out_keys.data_ptr()),
-                                            ctypes.c_void_p(out_index.data_ptr()) if out_index is not None else None, index_bytes,
-                                            ctypes.c_void_p(scratch.data_ptr()), sbytes, int(cand_capacity), nbytes, kind, levels,
-                                            _lib.RDST_TOPK_LARGEST if largest else 0, s))
-        if check:
-            _lib.check(lib.rdst_hip_device_status(s))
+    need = int(_lib.load().rdst_hip_topk_scratch_bytes(n, k, nbytes, index_bytes, int(cand_capacity)))
+    scratch, sbytes = _scratch(scratch, need, keys.device)
+    _call(keys, check, "rdst_hip_topk_device", _ptr(keys), n, k, _ptr(out_keys), _ptr(out_index), index_bytes, _ptr(scratch), sbytes,
+          int(cand_capacity), nbytes, kind, levels, _lib.RDST_TOPK_LARGEST if largest else 0)
     return out_keys, out_index
 
 
@@ -364,42 +335,12 @@ def segments_plan(offsets, n, dtype, val_bytes=0):
 
 def _segments_operands(name, keys, values, key):
     """the keys and values of a segmented tensor wrapper, checked: (kind, nbytes, levels, n, per_key, vbytes)"""
-    if not keys.is_cuda:
-        raise ValueError(f"{name} needs a tensor on a HIP device")
-    if _wide(key):
-        _check_wide_shape(tuple(keys.shape), keys.element_size())
-    elif keys.dim() != 1:
-        raise ValueError("keys must be a contiguous 1-D tensor")
-    if not keys.is_contiguous():
-        raise ValueError("keys must be a contiguous 1-D tensor")
-    kind, nbytes, levels = key_info(key if key else keys.dtype)
-    n = keys.numel() * keys.element_size() // nbytes
-    vbytes = 0
-    if values is not None:
-        if not values.is_cuda or values.device != keys.device or values.dim() != 1 or values.numel() != n or not values.is_contiguous():
-            raise ValueError("values must be a contiguous 1-D tensor of the keys' length on the keys' device")
-        vbytes = values.element_size()
-    per_key = keys.numel() // n if n else 1      # container elements per key (2 for the 128-bit limbs)
-    return kind, nbytes, levels, n, per_key, vbytes
-
-
-def _mismatch(t, like):
-    """a tmp (tmp_values) tensor that cannot stand in for `like`, whatever its length"""
-    return t.dtype != like.dtype or not t.is_contiguous() or t.device != like.device
-
-
-def _ptr(t, empty_is_null=False):
-    return ctypes.c_void_p(t.data_ptr() if t is not None and (t.numel() or not empty_is_null) else None)
-
-
-def _segments_call(keys, check, entry, *args):
-    """the tail of a segmented tensor wrapper: `entry(*args, stream)` on the keys' device and current stream, then the status"""
-    import torch
-    with torch.cuda.device(keys.device):
-        s = _stream_handle(keys)
-        _lib.check(entry(*args, s))
-        if check:
-            _lib.check(_lib.load().rdst_hip_device_status(s))
+    kind, nbytes, levels, n, per_key = _keys_operand(name, keys, key)
+    if values is None:
+        return kind, nbytes, levels, n, per_key, 0
+    if values.device != keys.device or values.dim() != 1 or values.numel() != n or not values.is_contiguous():
+        raise ValueError("values must be a contiguous 1-D tensor of the keys' length on the keys' device")
+    return kind, nbytes, levels, n, per_key, values.element_size()
 
 
 def sort_segments_device_tensor(keys, offsets, tmp=None, values=None, tmp_values=None, check=True, key=None):
@@ -441,10 +382,10 @@ def sort_segments_device_tensor(keys, offsets, tmp=None, values=None, tmp_values
     elif tmp is not None:
         tmp_elems = tmp.numel() // per_key
     if values is None:
-        _segments_call(keys, check, lib.rdst_hip_sort_segments_device, _ptr(keys), _ptr(tmp), tmp_elems, n, offp, n_segments, nbytes, kind, levels)
+        _call(keys, check, "rdst_hip_sort_segments_device", _ptr(keys), _ptr(tmp), tmp_elems, n, offp, n_segments, nbytes, kind, levels)
     else:
-        _segments_call(keys, check, lib.rdst_hip_sort_segments_pairs_device, _ptr(keys), _ptr(values), _ptr(tmp), _ptr(tmp_values), tmp_elems, n, offp,
-                       n_segments, nbytes, kind, levels, vbytes)
+        _call(keys, check, "rdst_hip_sort_segments_pairs_device", _ptr(keys), _ptr(values), _ptr(tmp), _ptr(tmp_values), tmp_elems, n, offp,
+              n_segments, nbytes, kind, levels, vbytes)
 
 
 def segments_device_offsets_scratch_bytes(n_segments):
@@ -467,34 +408,20 @@ def _device_offsets(offsets, keys, n):
     return offsets.numel() - 1, offsets.element_size()
 
 
-def _segments_scratch(scratch, need, device):
-    """(scratch, its bytes) for an entry that asks for `need` bytes: the caller's tensor, checked, or a fresh one"""
-    import torch
-    if scratch is None:
-        return torch.empty(max(need, 1), dtype=torch.uint8, device=device), need   # the caching allocator hands out 512-byte aligned blocks
-    if not scratch.is_cuda or scratch.device != device or not scratch.is_contiguous() or scratch.numel() * scratch.element_size() < need:
-        raise ValueError(f"scratch must be a contiguous tensor on the keys' device with at least {need} bytes")
-    return scratch, scratch.numel() * scratch.element_size()
-
-
 def segments_plan_device(offsets, n, dtype, val_bytes=0, scratch=None):
     """``rdst_hip_debug_segments_plan_device`` (test hook, blocking): the work list the DEVICE plan makes of a device-resident
     ``offsets`` tensor (int32 / int64) over ``n`` elements — ``(items, counts, tmp_elems, flags)``, the first three as
     :func:`segments_plan` returns them; ``flags``: 1 = offsets decrease somewhere, 2 = the last offset lies past ``n`` (the
     other three then mean nothing)."""
-    import torch
     _kind, nbytes, _levels = key_info(dtype)
     n_segments, obytes = _device_offsets(offsets, offsets, 0)
-    lib = _lib.load()
     items = (_lib.SegmentItemC * max(1, n_segments))()
     counts = (ctypes.c_uint64 * 3)()
     tmp_elems = ctypes.c_uint64(0)
     flags = ctypes.c_uint32(0)
-    with torch.cuda.device(offsets.device):
-        scratch, sbytes = _segments_scratch(scratch, segments_device_offsets_scratch_bytes(n_segments), offsets.device)
-        _lib.check(lib.rdst_hip_debug_segments_plan_device(ctypes.c_void_p(offsets.data_ptr()), obytes, n_segments, int(n), nbytes, int(val_bytes),
-                                                           ctypes.c_void_p(scratch.data_ptr()), sbytes, items, n_segments, counts,
-                                                           ctypes.byref(tmp_elems), ctypes.byref(flags), _stream_handle(offsets)))
+    scratch, sbytes = _scratch(scratch, segments_device_offsets_scratch_bytes(n_segments), offsets.device)
+    _call(offsets, False, "rdst_hip_debug_segments_plan_device", _ptr(offsets), obytes, n_segments, int(n), nbytes, int(val_bytes), _ptr(scratch),
+          sbytes, items, n_segments, counts, ctypes.byref(tmp_elems), ctypes.byref(flags))
     total = int(counts[0] + counts[1] + counts[2]) if not flags.value else 0
     return ([(int(it.start), int(it.len), int(it.seg)) for it in items[:total]], tuple(int(c) for c in counts), int(tmp_elems.value),
             int(flags.value))
@@ -529,16 +456,15 @@ def sort_segments_device_offsets_tensor(keys, offsets, tmp=None, values=None, tm
             tmp_elems = min(tmp_elems, tmp_values.numel())
     elif tmp_values is not None:
         raise ValueError("tmp_values without tmp")
-    lib = _lib.load()
-    scratch, sbytes = _segments_scratch(scratch, segments_device_offsets_scratch_bytes(n_segments), keys.device)
+    scratch, sbytes = _scratch(scratch, segments_device_offsets_scratch_bytes(n_segments), keys.device)
     if not tmp_elems:
         tmp = tmp_values = None
     if values is None:
-        _segments_call(keys, check, lib.rdst_hip_sort_segments_device_offsets, _ptr(keys), _ptr(tmp), tmp_elems, n, _ptr(offsets), obytes, n_segments,
-                       nbytes, kind, levels, _ptr(scratch), sbytes)
+        _call(keys, check, "rdst_hip_sort_segments_device_offsets", _ptr(keys), _ptr(tmp), tmp_elems, n, _ptr(offsets), obytes, n_segments,
+              nbytes, kind, levels, _ptr(scratch), sbytes)
     else:
-        _segments_call(keys, check, lib.rdst_hip_sort_segments_pairs_device_offsets, _ptr(keys), _ptr(values), _ptr(tmp), _ptr(tmp_values), tmp_elems, n,
-                       _ptr(offsets), obytes, n_segments, nbytes, kind, levels, vbytes, _ptr(scratch), sbytes)
+        _call(keys, check, "rdst_hip_sort_segments_pairs_device_offsets", _ptr(keys), _ptr(values), _ptr(tmp), _ptr(tmp_values), tmp_elems, n,
+              _ptr(offsets), obytes, n_segments, nbytes, kind, levels, vbytes, _ptr(scratch), sbytes)
 
 
 def segments_nowait_scratch_bytes(n_segments, n, dtype, val_bytes=0):
@@ -575,19 +501,18 @@ def sort_segments_device_offsets_nowait_tensor(keys, offsets, tmp=None, values=N
             tmp_values = torch.empty_like(values)
         elif _mismatch(tmp_values, values) or tmp_values.numel() < n:
             raise ValueError("tmp_values must be a contiguous tensor of the values' dtype and device with at least as many elements")
-    lib = _lib.load()
-    need = int(lib.rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes(n_segments, n, nbytes, vbytes))
-    scratch, sbytes = _segments_scratch(scratch, need, keys.device)
+    need = int(_lib.load().rdst_hip_sort_segments_device_offsets_nowait_scratch_bytes(n_segments, n, nbytes, vbytes))
+    scratch, sbytes = _scratch(scratch, need, keys.device)
 
     def ptr(t):
         return _ptr(t, empty_is_null=True)
 
     if values is None:
-        _segments_call(keys, check, lib.rdst_hip_sort_segments_device_offsets_nowait, ptr(keys), ptr(tmp), n, ptr(offsets), obytes, n_segments, nbytes, kind,
-                       levels, ptr(scratch), sbytes)
+        _call(keys, check, "rdst_hip_sort_segments_device_offsets_nowait", ptr(keys), ptr(tmp), n, ptr(offsets), obytes, n_segments, nbytes, kind,
+              levels, ptr(scratch), sbytes)
     else:
-        _segments_call(keys, check, lib.rdst_hip_sort_segments_pairs_device_offsets_nowait, ptr(keys), ptr(values), ptr(tmp), ptr(tmp_values), n, ptr(offsets),
-                       obytes, n_segments, nbytes, kind, levels, vbytes, ptr(scratch), sbytes)
+        _call(keys, check, "rdst_hip_sort_segments_pairs_device_offsets_nowait", ptr(keys), ptr(values), ptr(tmp), ptr(tmp_values), n, ptr(offsets),
+              obytes, n_segments, nbytes, kind, levels, vbytes, ptr(scratch), sbytes)
 
 
 def sort_records_by_key(records, key_field):
@@ -623,10 +548,7 @@ def sort_device_tensor_lowmem(keys, scratch=None):
         scratch = torch.empty(max(65536, -(-n // 64)), dtype=keys.dtype, device=keys.device)
     elif scratch.dtype != keys.dtype or scratch.device != keys.device or not scratch.is_contiguous():
         raise ValueError("scratch must be a contiguous tensor of the same dtype and device")
-    lib = _lib.load()
-    with torch.cuda.device(keys.device):
-        _lib.check(lib.rdst_hip_sort_device_lowmem(ctypes.c_void_p(keys.data_ptr()), n, nbytes, kind, levels,
-                                                   ctypes.c_void_p(scratch.data_ptr()), scratch.numel(), _stream_handle(keys)))
+    _call(keys, False, "rdst_hip_sort_device_lowmem", _ptr(keys), n, nbytes, kind, levels, _ptr(scratch), scratch.numel())
 
 
 def partition_device(keys, level, digit, scratch=None):
@@ -640,20 +562,27 @@ def partition_device(keys, level, digit, scratch=None):
     if scratch is None:
         scratch = torch.empty(max(65536, -(-n // 64)), dtype=keys.dtype, device=keys.device)
     split = ctypes.c_uint64(0)
-    lib = _lib.load()
-    with torch.cuda.device(keys.device):
-        _lib.check(lib.rdst_hip_partition_device(ctypes.c_void_p(keys.data_ptr()), n, nbytes, kind, int(level), int(digit),
-                                                 ctypes.c_void_p(scratch.data_ptr()), scratch.numel(), ctypes.byref(split),
-                                                 _stream_handle(keys)))
+    _call(keys, False, "rdst_hip_partition_device", _ptr(keys), n, nbytes, kind, int(level), int(digit), _ptr(scratch), scratch.numel(),
+          ctypes.byref(split))
     return int(split.value)
+
+
+def _ask_current_stream(device, entry, *out):
+    """`entry(stream, *out)` for the current stream of `device` (None: the current device)"""
+    import torch
+    with torch.cuda.device(device):
+        _lib.check(getattr(_lib.load(), entry)(_current_stream(), *out))
 
 
 def device_status(device=None):
     """Block on the current stream and raise if a kernel reported failure."""
-    import torch
-    lib = _lib.load()
-    with torch.cuda.device(device):
-        _lib.check(lib.rdst_hip_device_status(ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)))
+    _ask_current_stream(device, "rdst_hip_device_status")
+
+
+def _host_call(entry, arr, n, device, *args):
+    """the tail of a host-slice wrapper: `entry(arr's memory, n, *args, opts)` (H2D, device sort, D2H; blocking)"""
+    opts = _lib.HipOptsC(int(device), 0, 0)
+    _lib.check(getattr(_lib.load(), entry)(ctypes.c_void_p(arr.ctypes.data), n, *args, ctypes.byref(opts)))
 
 
 def sort_host_array(arr, device=-1, key=None):
@@ -664,23 +593,16 @@ def sort_host_array(arr, device=-1, key=None):
         raise ValueError("need a writeable C-contiguous 1-D numpy array (rdst sorts a mutable slice)")
     if key == "bytes":
         _check_bytes_rows(arr.shape, arr.dtype == np.uint8)
-        if arr.shape[0] <= 1:
-            return
-        n_bytes = int(arr.shape[1])
-        opts = _lib.HipOptsC(int(device), 0, 0)
-        _lib.check(_lib.load().rdst_hip_sort(ctypes.c_void_p(arr.ctypes.data), arr.shape[0], n_bytes, _lib.RDST_KEY_BYTES_BE, n_bytes,
-                                             ctypes.byref(opts)))
-        return
-    if _wide(key):
-        _check_wide_shape(arr.shape, arr.dtype.itemsize)
-    elif arr.ndim != 1:
-        raise ValueError("need a writeable C-contiguous 1-D numpy array (rdst sorts a mutable slice)")
-    kind, nbytes, levels = key_info(key if key else arr.dtype.name)
+        kind, nbytes, levels = _lib.RDST_KEY_BYTES_BE, int(arr.shape[1]), int(arr.shape[1])
+    else:
+        if _wide(key):
+            _check_wide_shape(arr.shape, arr.dtype.itemsize)
+        elif arr.ndim != 1:
+            raise ValueError("need a writeable C-contiguous 1-D numpy array (rdst sorts a mutable slice)")
+        kind, nbytes, levels = key_info(key if key else arr.dtype.name)
     if arr.nbytes // nbytes <= 1:
         return
-    lib = _lib.load()
-    opts = _lib.HipOptsC(int(device), 0, 0)
-    _lib.check(lib.rdst_hip_sort(ctypes.c_void_p(arr.ctypes.data), arr.nbytes // nbytes, nbytes, kind, levels, ctypes.byref(opts)))
+    _host_call("rdst_hip_sort", arr, arr.nbytes // nbytes, device, nbytes, kind, levels)
 
 
 class KeyField:
@@ -738,29 +660,28 @@ def sort_records_device_nowait_tensor(records, fields, scratch=None, check=True)
 
 def _sort_records_rows(name, entry, records, fields, scratch, check):
     import torch
-    if not records.is_cuda:
-        raise ValueError(f"{name} needs a tensor on a HIP device")
+    _on_device(name, records)
     if records.dim() != 2 or records.dtype != torch.uint8 or not records.is_contiguous():
         raise ValueError("records must be a contiguous (n, R) uint8 tensor, one row per record")
     n, rec_bytes = int(records.shape[0]), int(records.shape[1])
     table, nf = _field_table(fields)
-    lib = _lib.load()
-    need = int(lib.rdst_hip_sort_records_by_fields_scratch_bytes(n, rec_bytes, table, nf))
-    if scratch is None:
-        scratch = torch.empty(max(need, 1), dtype=torch.uint8, device=records.device)  # the caching allocator hands out 512-byte aligned blocks
-    elif scratch.device != records.device or not scratch.is_contiguous() or scratch.numel() * scratch.element_size() < need:
-        raise ValueError(f"scratch must be a contiguous tensor on the records' device with at least {need} bytes")
-    with torch.cuda.device(records.device):
-        s = _stream_handle(records)
-        _lib.check(getattr(lib, entry)(ctypes.c_void_p(records.data_ptr()), n, rec_bytes, table, nf,
-                                       ctypes.c_void_p(scratch.data_ptr()), scratch.numel() * scratch.element_size(), s))
-        if check and n > 1:
-            _lib.check(lib.rdst_hip_device_status(s))
+    need = int(_lib.load().rdst_hip_sort_records_by_fields_scratch_bytes(n, rec_bytes, table, nf))
+    scratch, sbytes = _scratch(scratch, need, records.device, "records")
+    # unlike the [u8; N] rows, zero or one record still reach the library: it is the library that checks the description
+    # (and enqueues nothing then, so there is no status to wait for)
+    _call(records, check and n > 1, entry, _ptr(records), n, rec_bytes, table, nf, _ptr(scratch), sbytes)
 
 
 def _is_byte_string(ftype):
     return (ftype.subdtype is not None and ftype.subdtype[0] == np.uint8 and len(ftype.subdtype[1]) == 1) or \
         (ftype.kind in "SV" and ftype.fields is None and ftype.subdtype is None)
+
+
+def _field_key(ftype):
+    """(kind, bytes) of one field of a numpy structured dtype: a byte string or a built-in key type"""
+    if _is_byte_string(ftype):
+        return _lib.RDST_KEY_BYTES_BE, ftype.itemsize
+    return key_info(ftype.name)[:2]
 
 
 def key_fields_of(dtype, names):
@@ -773,12 +694,9 @@ def key_fields_of(dtype, names):
         if direction not in ("asc", "desc"):
             raise ValueError(f"field direction is 'asc' or 'desc', not {direction!r}")
         ftype, offset = dtype.fields[name][:2]
-        if _is_byte_string(ftype):
-            kind, nbytes = _lib.RDST_KEY_BYTES_BE, ftype.itemsize
-        else:
-            if ftype.byteorder == ">":
-                raise TypeError(f"field {name!r} is big-endian; built-in key fields are read little-endian")
-            kind, nbytes, _levels = key_info(ftype.name)
+        if ftype.byteorder == ">":   # (never a byte string's; sort_host_records' single-field form does not look)
+            raise TypeError(f"field {name!r} is big-endian; built-in key fields are read little-endian")
+        kind, nbytes = _field_key(ftype)
         out.append(KeyField(int(offset), nbytes, kind, direction == "desc"))
     return out
 
@@ -797,24 +715,15 @@ def sort_host_records(arr, field, device=-1):
         field = list(field)
         fields = field if field and all(isinstance(f, KeyField) for f in field) else key_fields_of(arr.dtype, field)
         table, nf = _field_table(fields)
-        opts = _lib.HipOptsC(int(device), 0, 0)
-        _lib.check(_lib.load().rdst_hip_sort_records_by_fields(ctypes.c_void_p(arr.ctypes.data), arr.shape[0], arr.dtype.itemsize, table, nf,
-                                                               ctypes.byref(opts)))
+        _host_call("rdst_hip_sort_records_by_fields", arr, arr.shape[0], device, arr.dtype.itemsize, table, nf)
         return
     ftype, offset = arr.dtype.fields[field][:2]
-    byte_string = _is_byte_string(ftype)
-    if byte_string:
-        kind, nbytes = _lib.RDST_KEY_BYTES_BE, ftype.itemsize
-        if not 1 <= nbytes <= _lib.RDST_BYTES_MAX_N:
-            raise ValueError(f"[u8; N] key fields: N in 1..{_lib.RDST_BYTES_MAX_N}")
-    else:
-        kind, nbytes, _levels = key_info(ftype.name)
+    kind, nbytes = _field_key(ftype)
+    if kind == _lib.RDST_KEY_BYTES_BE and not 1 <= nbytes <= _lib.RDST_BYTES_MAX_N:
+        raise ValueError(f"[u8; N] key fields: N in 1..{_lib.RDST_BYTES_MAX_N}")
     if arr.shape[0] <= 1:
         return
-    lib = _lib.load()
-    opts = _lib.HipOptsC(int(device), 0, 0)
-    _lib.check(lib.rdst_hip_sort_records(ctypes.c_void_p(arr.ctypes.data), arr.shape[0], arr.dtype.itemsize, int(offset), nbytes, kind,
-                                         ctypes.byref(opts)))
+    _host_call("rdst_hip_sort_records", arr, arr.shape[0], device, arr.dtype.itemsize, int(offset), nbytes, kind)
 
 
 class RadixSortBuilder:
@@ -953,26 +862,18 @@ def level_counts(keys, level):
     """Parity hook: (counts[256], already_sorted, first_digit, last_digit) of one level
     (get_counts_with_ends, src/sort_utils.rs:109-180) over a HIP tensor."""
     kind, nbytes, _ = key_info(keys.dtype)
-    lib = _lib.load()
     counts = (ctypes.c_uint64 * 256)()
     srt, first, last = ctypes.c_uint8(1), ctypes.c_uint8(0), ctypes.c_uint8(0)
-    import torch
-    with torch.cuda.device(keys.device):
-        _lib.check(lib.rdst_hip_level_counts(ctypes.c_void_p(keys.data_ptr()), keys.numel(), nbytes, kind, level,
-                                             counts, ctypes.byref(srt), ctypes.byref(first), ctypes.byref(last),
-                                             _stream_handle(keys)))
+    _call(keys, False, "rdst_hip_level_counts", _ptr(keys), keys.numel(), nbytes, kind, level, counts, ctypes.byref(srt), ctypes.byref(first),
+          ctypes.byref(last))
     return list(counts), bool(srt.value), first.value, last.value
 
 
 def all_level_counts(keys):
     """Parity hook for the fused histogram kernel: numpy uint64 array [levels, 256]."""
     kind, nbytes, levels = key_info(keys.dtype)
-    lib = _lib.load()
     out = np.zeros((levels, 256), dtype=np.uint64)
-    import torch
-    with torch.cuda.device(keys.device):
-        _lib.check(lib.rdst_hip_all_level_counts(ctypes.c_void_p(keys.data_ptr()), keys.numel(), nbytes, kind, levels,
-                                                 out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), _stream_handle(keys)))
+    _call(keys, False, "rdst_hip_all_level_counts", _ptr(keys), keys.numel(), nbytes, kind, levels, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
     return out
 
 
@@ -981,14 +882,10 @@ def scatter_level(src, level, dst=None):
     src/sorts/out_of_place_sort.rs:52-108).  Returns (dst tensor, counts[256])."""
     import torch
     kind, nbytes, _ = key_info(src.dtype)
-    lib = _lib.load()
     if dst is None:
         dst = torch.empty_like(src)
     counts = np.zeros(256, dtype=np.uint64)
-    with torch.cuda.device(src.device):
-        _lib.check(lib.rdst_hip_scatter_level(ctypes.c_void_p(src.data_ptr()), ctypes.c_void_p(dst.data_ptr()),
-                                              src.numel(), nbytes, kind, level,
-                                              counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), _stream_handle(src)))
+    _call(src, False, "rdst_hip_scatter_level", _ptr(src), _ptr(dst), src.numel(), nbytes, kind, level, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)))
     return dst, counts
 
 
@@ -1097,11 +994,8 @@ def release_workspace(device=None) -> None:
 
 def last_route(device=None) -> str:
     """'lsd', 'hybrid' or 'atomic': the route the most recent sort on the current stream's device took."""
-    import torch
-    lib = _lib.load()
     r = ctypes.c_uint32(0)
-    with torch.cuda.device(device):
-        _lib.check(lib.rdst_hip_last_route(ctypes.c_void_p(torch.cuda.current_stream().cuda_stream), ctypes.byref(r)))
+    _ask_current_stream(device, "rdst_hip_last_route", ctypes.byref(r))
     return {1: "hybrid", 2: "atomic"}.get(r.value, "lsd")
 
 
@@ -1111,11 +1005,8 @@ SAMPLE_WORDS = ("win_shift", "win_top", "gross_skew", "top_skew", "low_dups", "p
 def last_sample(device=None) -> dict:
     """What the key sample of the most recent sort on the current stream's device decided (rdst_hip_debug_last_sample, a test
     hook): the six plan words of SAMPLE_WORDS by name; all zero when the sort took no sample."""
-    import torch
-    lib = _lib.load()
     out = (ctypes.c_uint32 * 6)()
-    with torch.cuda.device(device):
-        _lib.check(lib.rdst_hip_debug_last_sample(ctypes.c_void_p(torch.cuda.current_stream().cuda_stream), out))
+    _ask_current_stream(device, "rdst_hip_debug_last_sample", out)
     return {name: int(out[i]) for i, name in enumerate(SAMPLE_WORDS)}
 
 
