@@ -324,6 +324,36 @@ void topk_device(const T* dev_keys, std::size_t len, std::size_t k, T* dev_out_k
                                        largest ? RDST_TOPK_LARGEST : 0u, stream));
 }
 
+// Partial sort of every segment [offsets[s], offsets[s + 1]) of one DEVICE-resident slice (rdst_hip_topk_segments_device):
+// row s of the outputs, dev_out_keys + s * k (and dev_out_index + s * k), receives in its first min(k, n_s) slots what
+// topk_device gives for that segment, positions counted inside the segment; the slots behind are not written.  offsets: a
+// HOST array of n_segments + 1 non-decreasing element indices, read before the call returns.  dev_scratch: 256-byte aligned,
+// at least topk_segments_scratch_bytes<T>(n_segments, longest segment, k) / <T, Idx>(...) bytes.  Asynchronous as
+// sort_segments_device is.
+template <typename T>
+std::size_t topk_segments_scratch_bytes(std::size_t n_segments, std::size_t longest_segment, std::size_t k) {
+    return rdst_hip_topk_segments_scratch_bytes(n_segments, longest_segment, k, sizeof(T), 0);
+}
+template <typename T, typename Idx>
+std::size_t topk_segments_scratch_bytes(std::size_t n_segments, std::size_t longest_segment, std::size_t k) {
+    return rdst_hip_topk_segments_scratch_bytes(n_segments, longest_segment, k, sizeof(T), sizeof(Idx));
+}
+template <typename T>
+void topk_segments(const T* dev_keys, std::size_t len, const std::uint64_t* offsets, std::size_t n_segments, std::size_t k, T* dev_out_keys,
+                   void* dev_scratch, std::size_t scratch_bytes, bool largest = false, void* stream = nullptr) {
+    detail::check(rdst_hip_topk_segments_device(dev_keys, len, offsets, n_segments, k, dev_out_keys, nullptr, 0, dev_scratch, scratch_bytes, sizeof(T),
+                                                RadixKey<T>::kind, static_cast<std::uint32_t>(RadixKey<T>::LEVELS),
+                                                largest ? RDST_TOPK_LARGEST : 0u, stream));
+}
+template <typename T, typename Idx>
+void topk_segments(const T* dev_keys, std::size_t len, const std::uint64_t* offsets, std::size_t n_segments, std::size_t k, T* dev_out_keys,
+                   Idx* dev_out_index, void* dev_scratch, std::size_t scratch_bytes, bool largest = false, void* stream = nullptr) {
+    static_assert(std::is_unsigned<Idx>::value && (sizeof(Idx) == 4 || sizeof(Idx) == 8), "positions are 4- or 8-byte unsigned integers");
+    detail::check(rdst_hip_topk_segments_device(dev_keys, len, offsets, n_segments, k, dev_out_keys, dev_out_index, sizeof(Idx), dev_scratch,
+                                                scratch_bytes, sizeof(T), RadixKey<T>::kind, static_cast<std::uint32_t>(RadixKey<T>::LEVELS),
+                                                largest ? RDST_TOPK_LARGEST : 0u, stream));
+}
+
 // DEVICE-resident [u8; N] rows (src/radix_key_impl.rs:78-85) and DEVICE-resident structs ordered by a described key
 // (src/radix_key.rs; examples/impl_radix_key.rs:32-56), in place and with no host involvement
 // (rdst_hip_sort_bytes_device_nowait, rdst_hip_sort_records_by_fields_device_nowait): N, or the sum of the fields' widths,

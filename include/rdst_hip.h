@@ -308,7 +308,74 @@ int rdst_segments_plan(const uint64_t* offsets, uint64_t n_segments, uint64_t le
                        rdst_segment_item* items_out, uint64_t capacity, uint64_t class_counts_out[3],
                        uint64_t* tmp_elems_out);
 
-/* The same two sorts with the table of borders in DEVICE memory (src/sorter.rs:131-138, as above): a CSR row pointer, the
+/* ---- partial sort of every segment in one call ------------------------------------------------------
+ * The k first keys of every row of a score matrix, of every query's distances, of every CSR row: rdst_hip_topk_device per
+ * segment, in one call.  offsets: HOST table of n_segments + 1 non-decreasing element indices as
+ * rdst_hip_sort_segments_device takes it (offsets[n_segments] <= len, n_segments < 2^32), read before the call returns;
+ * len < 2^32; segment starts need the element's alignment only.
+ *   - Row s of the outputs is dev_out_keys + s * k and dev_out_index + s * k (elements).  With n_s = offsets[s+1] -
+ *     offsets[s] and k_s = min(k, n_s), its first k_s slots hold, bit for bit, what rdst_hip_topk_device writes for the slice
+ *     dev_keys + offsets[s] of length n_s with k_s and the same kind, flags and index width: ascending mapped key (with
+ *     RDST_TOPK_LARGEST: ascending complemented mapped key), positions local to the segment, equal keys in ascending
+ *     position, the lowest positions winning a tie at the k-th key, -0.0 / +0.0 and NaN payloads distinct.
+ *   - Slots k_s .. k of a row are NOT written (the caller knows the lengths), empty segments write nothing, the input is
+ *     never written.  Of the scratch only [0, rdst_hip_topk_segments_scratch_bytes(n_segments, longest segment, k, elem_bytes,
+ *     index_bytes)) is written; it needs no clearing, and stream order makes it reusable by the next call.
+ *   - Keys only: every width and kind of rdst_hip_topk_device; with an index (4 or 8 bytes): 4- and 8-byte keys.  With a NULL
+ *     dev_out_index, index_bytes is not looked at.  RDST_KEY_BYTES_BE: RDST_ERR_UNSUPPORTED.
+ *   - There is no limit on k and no data-dependent failure.  Segments are served by length and k
+ *     (rdst_hip_topk_segments_limits; bm = block_max for this key width and a 4-byte position beside the key):
+ *       1 .. wave_max                       one wave per segment, four segments per workgroup — one launch for all;
+ *       .. bm                               one workgroup per segment, longest first — one launch for all;
+ *       .. stream_max, and k <= k_stream_max (= bm)
+ *                                           one workgroup per segment, longest first — one launch for all: a radix select
+ *                                           streamed from global memory, then the workgroup's LDS sort of at most bm keys;
+ *       everything else ("far": longer than stream_max, or longer than bm with k > bm)
+ *                                           rdst_hip_topk_device's own route, one segment after another on `stream`.
+ *   - ASYNCHRONOUS as rdst_hip_sort_segments_device is: the work list travels through the pinned staging buffer the library
+ *     keeps per device, and a call WAITS (on an event, not on the stream) only while the list of the previous segmented call
+ *     on that device has not reached the device yet.  There is no other copy to the host and no other wait at any k and any
+ *     segment length: the far class runs on the hooks rdst_hip_topk_device runs on, which never wait (the one exception every
+ *     entry shares: a library workspace that has to grow).  Kernel failures surface in rdst_hip_device_status.
+ *   - Profiling: the three batched launches end stages RDST_STAGE_SEGMENTS | (class << 8), class 0 = wave, 1 = block, 2 =
+ *     stream; far segments report rdst_hip_topk_device's stages.
+ *   - Arguments, checked in this order before any device work: the key arguments as rdst_hip_topk_device checks them (its
+ *     codes and messages; BYTES_BE -> RDST_ERR_UNSUPPORTED); len >= 2^32 -> RDST_ERR_UNSUPPORTED; unknown flag bits ->
+ *     RDST_ERR_ARG; k == 0 or n_segments == 0 -> RDST_OK, nothing else is looked at; the table: NULL offsets, n_segments >=
+ *     2^32, decreasing offsets, a last offset past len -> RDST_ERR_ARG; NULL dev_out_keys -> RDST_ERR_ARG; dev_out_keys
+ *     misaligned to the element -> RDST_ERR_ALIGN; with an index: index_bytes not 4 or 8 -> RDST_ERR_ARG, key width not 4 or 8
+ *     -> RDST_ERR_UNSUPPORTED, misaligned index pointer -> RDST_ERR_ALIGN; NULL scratch -> RDST_ERR_ARG; scratch not 256-byte
+ *     aligned -> RDST_ERR_ALIGN; scratch_bytes below rdst_hip_topk_segments_scratch_bytes(...) for the table's longest segment
+ *     -> RDST_ERR_ARG. */
+int rdst_hip_topk_segments_device(const void* dev_keys, uint64_t len,
+                                  const uint64_t* offsets, uint64_t n_segments, uint64_t k,
+                                  void* dev_out_keys, void* dev_out_index, uint32_t index_bytes,
+                                  void* dev_scratch, uint64_t scratch_bytes,
+                                  uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels,
+                                  uint32_t flags, void* stream);
+/* The scratch of the call above.  Pure, monotone in every argument: the item table, 16 bytes per segment rounded up to 256,
+ * and — if a segment of `longest_segment` keys would be of the far class for this k — behind it
+ * rdst_hip_topk_scratch_bytes(longest_segment, min(k, longest_segment), elem_bytes, index_bytes, 0).  It moves with
+ * rdst_hip_set_topk_segments_stream_max.  0 for no segment, 2^32 segments or keys and more, and unsupported widths. */
+uint64_t rdst_hip_topk_segments_scratch_bytes(uint64_t n_segments, uint64_t longest_segment, uint64_t k,
+                                              uint32_t elem_bytes, uint32_t index_bytes);
+/* out = { wave_max, block_max, stream_max, k_stream_max } for this key width (index_bytes 0 = keys only).  Pure but for the
+ * setter below.  Unsupported widths: rdst_hip_topk_limits' codes. */
+int rdst_hip_topk_segments_limits(uint32_t elem_bytes, uint32_t index_bytes, uint32_t out[4]);
+/* Host only, like rdst_segments_plan: the work list the entry runs.  One item per segment of at least ONE key: wave class
+ * first, in segment order; then block class, longest first, ties in segment order; then stream class, the same; then far
+ * class, in segment order.  class_counts_out: the four counts; *longest_far_out: the longest far segment, or 0.  A
+ * `capacity` below their sum: RDST_ERR_ARG, with the counts and *longest_far_out still written.  k == 0: no items.  The
+ * table's errors are rdst_segments_plan's. */
+int rdst_topk_segments_plan(const uint64_t* offsets, uint64_t n_segments, uint64_t len, uint64_t k,
+                            uint32_t elem_bytes, uint32_t index_bytes,
+                            rdst_segment_item* items_out, uint64_t capacity,
+                            uint64_t class_counts_out[4], uint64_t* longest_far_out);
+/* Test hook, like rdst_hip_set_small_sort: the longest segment of the stream class; 0 = the default (2^17 keys).  A value
+ * below block_max leaves the stream class empty. */
+int rdst_hip_set_topk_segments_stream_max(uint32_t stream_max);
+
+/* The two segmented sorts (rdst_hip_sort_segments_device, ..._pairs_device) with the table of borders in DEVICE memory (src/sorter.rs:131-138, as above): a CSR row pointer, the
  * cumulative sum of a ragged batch's lengths, the bucket borders rdst_hip_split_top_level_device leaves behind — no copy of
  * the table to the host, no host plan.  dev_offsets: n_segments + 1 unsigned integers of offset_bytes (4 or 8) bytes,
  * aligned to that size, read only, and read in stream order (the kernel that writes the table may still be running when

@@ -1,4 +1,5 @@
-// rdst_device.h — device helpers shared by the library's HIP translation units (rdst_kernels.hip, rdst_segments.hip, rdst_topk.hip): the
+// rdst_device.h — device helpers shared by the library's HIP translation units (rdst_kernels.hip, rdst_segments.hip, rdst_topk.hip,
+// rdst_topk_segments.hip): the
 // order-preserving key map, digit extraction and the wave-level digit ranking.  Every TU gets its own copy (anonymous
 // namespace, all of it inlined).
 #ifndef RDST_DEVICE_H
@@ -67,6 +68,41 @@ template <typename K>
 __device__ __forceinline__ uint32_t digit_word(K mapped, int shift) {  // 32-bit half that holds the digit
     if constexpr (sizeof(K) > 4) return (uint32_t)(mapped >> (shift & ~31));
     else return (uint32_t)mapped;
+}
+
+// The inverse of map_key for ANY pair of masks (the complemented ones of RDST_TOPK_LARGEST too): the preimage whose sign
+// bit picks the mask it was mapped with.
+template <typename K>
+__device__ __forceinline__ K unmap_any(K m, K neg, K pos) {
+    const K a = (K)(m ^ neg);
+    return (K)(a >> (sizeof(K) * 8 - 1)) ? a : (K)(m ^ pos);
+}
+
+// The bucket pick of a radix select, by one workgroup of 1024 threads over 4096 counters: thread t holds the counters
+// 4 t .. 4 t + 3 in c.  The ONE thread whose counters hold the `remaining`-th key (1 <= remaining <= the sum of all counters)
+// returns true, with *before = the keys in the buckets before the picked one and *j = the picked bucket's place in c.
+// `wave_sum`: 16 words of LDS.  Every thread of the workgroup calls it (one barrier inside).
+__device__ __forceinline__ bool pick_bucket(const uint32_t (&c)[4], uint32_t remaining, uint32_t* wave_sum, uint32_t* before, int* j) {
+    const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+    const uint32_t sum = c[0] + c[1] + c[2] + c[3];
+    uint32_t incl = sum;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(incl, o);
+        if (lane >= (uint32_t)o) incl += y;
+    }
+    if (lane == 63) wave_sum[wave] = incl;
+    __syncthreads();
+    uint32_t earlier = 0;
+    for (uint32_t w = 0; w < wave; ++w) earlier += wave_sum[w];
+    incl += earlier;
+    uint32_t run = incl - sum;
+    if (!(run < remaining && remaining <= incl)) return false;
+    int at = 0;
+    while (at < 3 && run + c[at] < remaining) run += c[at++];
+    *before = run;
+    *j = at;
+    return true;
 }
 
 }  // namespace

@@ -140,7 +140,7 @@ int sort_bytes_widened(void* dev_rows, uint64_t len, uint32_t nb, void* scratch,
 // The same for host-only translation units (rdst_segments.cpp), which do not see HIP's types.
 int note_error(int code, const char* what);
 
-// ---- hooks for rdst_segments.hip and rdst_topk.hip -------------------------------------------------------------------
+// ---- hooks for rdst_segments.hip, rdst_topk.hip and rdst_topk_segments.hip -------------------------------------------------------------------
 // The library's mutex; every hook below this line is called with it held.
 std::mutex& library_mutex();
 // The argument checks shared by the device entry points (width, kind, levels, pointer, alignment, length); no lock needed.
@@ -169,6 +169,13 @@ size_t slice_workspace_bytes(uint64_t n, uint32_t key_bytes, rdst_key_kind kind,
 // used it (workspace_release).
 int workspace_take(size_t bytes, hipStream_t s, void** ws_out, int* device_out);
 int workspace_handback(hipStream_t s);
+// rdst_segments.hip: `count` work items to `dev_dst` on `s` through device `device`'s pinned staging buffer; waits (on the
+// event) only while the previous list that went through it is still on its way.
+int stage_segment_items(int device, const rdst_segment_item* items, size_t count, void* dev_dst, hipStream_t s);
+// rdst_topk.hip: rdst_hip_topk_device after its checks, with the layout of rdst_hip_topk_scratch_bytes(len, k, elem_bytes,
+// index_bytes, 0) in `scratch`; `cus`: the device's compute units.  No copy to the host, no wait.
+int topk_slice_locked(const void* keys, uint64_t len, uint64_t k, void* out_keys, void* out_index, uint32_t index_bytes, void* scratch,
+                      uint32_t elem_bytes, rdst_key_kind kind, bool largest, int cus, hipStream_t s);
 // Profiling (rdst_hip_set_profiling): open a run of its own / close the stage that ends here.  No-ops when profiling is off.
 int profile_open_run(hipStream_t s);
 int profile_stage_end(hipStream_t s, uint32_t stage);

@@ -13,6 +13,9 @@
 // The limits follow from what the kernels of rdst_segments.hip keep per lane and per workgroup; rdst_segments_layout.h
 // states them, and the scratch layouts, once for both files.
 //
+// The segmented partial sort (rdst_hip_topk_segments_device, rdst_topk_segments.hip) has its limits, its border setter and its
+// plan here too: four classes, and a segment of one key is work.
+//
 // Host only: no HIP here (bound by tests/test_segments_plan.py without a device, and compiled into a stand-alone
 // program under the address sanitizer by the same test).
 #include <stdint.h>
@@ -99,5 +102,77 @@ extern "C" int rdst_segments_plan(const uint64_t* offsets, uint64_t n_segments, 
     }
     rdst_segment_item* block = items_out + counts[0];
     std::stable_sort(block, block + counts[1], [](const rdst_segment_item& a, const rdst_segment_item& b) { return a.len > b.len; });
+    return RDST_OK;
+}
+
+// ---- the segmented partial sort: limits and plan (the kernels and the entry: rdst_topk_segments.hip) ----------------------
+
+namespace {
+uint32_t g_topk_stream_max = 0;  // 0: the default
+// keys only: every width; with an index: 4- and 8-byte keys and a 4- or 8-byte index (rdst_hip_topk_limits' codes)
+int topk_segments_widths(uint32_t elem_bytes, uint32_t index_bytes) {
+    if (!L::key_width_ok(elem_bytes)) return note_error(RDST_ERR_UNSUPPORTED, "device path is built for 1-, 2-, 4-, 8- and 16-byte keys");
+    if (index_bytes != 0 && index_bytes != 4 && index_bytes != 8) return note_error(RDST_ERR_ARG, "topk: index_bytes must be 4 or 8");
+    if (index_bytes != 0 && !L::pair_width_ok(elem_bytes)) return note_error(RDST_ERR_UNSUPPORTED, "topk: an index output takes 4- or 8-byte keys");
+    return RDST_OK;
+}
+}  // namespace
+
+extern "C" int rdst_hip_set_topk_segments_stream_max(uint32_t stream_max) {
+    g_topk_stream_max = stream_max;
+    return RDST_OK;
+}
+
+extern "C" int rdst_hip_topk_segments_limits(uint32_t elem_bytes, uint32_t index_bytes, uint32_t out[4]) {
+    if (!out) return note_error(RDST_ERR_ARG, "topk_segments_limits: null output");
+    if (int rc = topk_segments_widths(elem_bytes, index_bytes)) return rc;
+    const uint32_t bm = L::block_max(elem_bytes, index_bytes ? 4 : 0);  // the position travels as a u32 beside the key
+    out[0] = L::wave_max(elem_bytes);
+    out[1] = bm;
+    out[2] = std::max(bm, g_topk_stream_max ? g_topk_stream_max : L::TOPK_STREAM_MAX_DEFAULT);  // (a border below bm: no stream class)
+    out[3] = bm;
+    return RDST_OK;
+}
+
+extern "C" int rdst_topk_segments_plan(const uint64_t* offsets, uint64_t n_segments, uint64_t len, uint64_t k, uint32_t elem_bytes,
+                                       uint32_t index_bytes, rdst_segment_item* items_out, uint64_t capacity, uint64_t class_counts_out[4],
+                                       uint64_t* longest_far_out) {
+    uint32_t lim[4];
+    if (int rc = rdst_hip_topk_segments_limits(elem_bytes, index_bytes, lim)) return rc;
+    if (!class_counts_out || !longest_far_out) return note_error(RDST_ERR_ARG, "topk_segments_plan: null output");
+    class_counts_out[0] = class_counts_out[1] = class_counts_out[2] = class_counts_out[3] = 0;
+    *longest_far_out = 0;
+    if (n_segments == 0 || k == 0) return RDST_OK;
+    if (!offsets) return note_error(RDST_ERR_ARG, "segments: null offsets");
+    if (n_segments >= (1ull << 32)) return note_error(RDST_ERR_ARG, "segments: n_segments must be below 2^32");
+    for (uint64_t s = 0; s < n_segments; ++s)
+        if (offsets[s + 1] < offsets[s]) return note_error(RDST_ERR_ARG, "segments: offsets must be non-decreasing");
+    if (offsets[n_segments] > len) return note_error(RDST_ERR_ARG, "segments: the last offset lies past len");
+    const uint64_t wave_max = lim[0], block_max = lim[1], stream_max = lim[2], k_stream_max = lim[3];
+    const auto class_of = [&](uint64_t n) { return n <= wave_max ? 0 : (n <= block_max ? 1 : (n <= stream_max && k <= k_stream_max ? 2 : 3)); };
+    uint64_t counts[4] = {0, 0, 0, 0}, longest = 0;
+    for (uint64_t s = 0; s < n_segments; ++s) {
+        const uint64_t n = offsets[s + 1] - offsets[s];
+        if (n == 0) continue;
+        const int c = class_of(n);
+        ++counts[c];
+        if (c == 3 && n > longest) longest = n;
+    }
+    uint64_t total = 0;
+    for (int c = 0; c < 4; ++c) total += class_counts_out[c] = counts[c];
+    *longest_far_out = longest;
+    if (total > capacity) return note_error(RDST_ERR_ARG, "topk_segments_plan: capacity too small for the work list");
+    if (total == 0) return RDST_OK;
+    if (!items_out) return note_error(RDST_ERR_ARG, "topk_segments_plan: null item table");
+    uint64_t at[4] = {0, counts[0], counts[0] + counts[1], counts[0] + counts[1] + counts[2]};
+    for (uint64_t s = 0; s < n_segments; ++s) {
+        const uint64_t n = offsets[s + 1] - offsets[s];
+        if (n == 0) continue;
+        items_out[at[class_of(n)]++] = {offsets[s], (uint32_t)std::min<uint64_t>(n, 0xFFFFFFFFull), (uint32_t)s};
+    }
+    const auto longer = [](const rdst_segment_item& a, const rdst_segment_item& b) { return a.len > b.len; };
+    rdst_segment_item* block = items_out + counts[0];
+    std::stable_sort(block, block + counts[1], longer);
+    std::stable_sort(block + counts[1], block + counts[1] + counts[2], longer);
     return RDST_OK;
 }

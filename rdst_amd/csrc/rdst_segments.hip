@@ -1127,6 +1127,11 @@ int sort_segments_nowait(const SegCall& c, bool pair_entry, const void* dev_offs
 
 }  // namespace
 
+int rdst_internal::stage_segment_items(int device, const rdst_segment_item* items, size_t count, void* dev_dst, hipStream_t s) {
+    if (device < 0 || device >= (int)(sizeof g_staging / sizeof g_staging[0])) return set_error(RDST_ERR_ARG, "segments: device index beyond the staging buffers");
+    return stage_items(g_staging[device], items, count, dev_dst, s);
+}
+
 extern "C" int rdst_hip_sort_segments_device_offsets(void* dev_keys, void* dev_tmp, uint64_t tmp_elems, uint64_t len, const void* dev_offsets,
                                                      uint32_t offset_bytes, uint64_t n_segments, uint32_t elem_bytes, rdst_key_kind kind,
                                                      uint32_t levels, void* dev_scratch, uint64_t scratch_bytes, void* stream) {

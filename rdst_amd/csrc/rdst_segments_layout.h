@@ -29,6 +29,11 @@ constexpr uint32_t block_max(size_t key_bytes, size_t val_bytes) {              
     return (uint32_t)BLOCK_THREADS * (uint32_t)block_kpt(key_bytes, val_bytes);
 }
 
+// The segmented partial sort (rdst_topk_segments.hip): the longest segment its one-workgroup radix select streams from global
+// memory.  Measured with one segment per call (DESIGN.md §2i has the sweep): at 2^17 keys the one workgroup still beats the
+// whole-array route's per-call floor, at 2^18 the route's every-CU reads win, for 4- and 8-byte keys alike.
+constexpr uint32_t TOPK_STREAM_MAX_DEFAULT = 1u << 17;
+
 // ---- scratch (byte offsets from its 256-byte aligned base; every array is rounded up to 256 bytes) ----------------------
 constexpr uint64_t MAX_SEGMENTS = 1ull << 30;  // of a table in device memory
 constexpr uint64_t up256(uint64_t bytes) { return (bytes + 255) / 256 * 256; }

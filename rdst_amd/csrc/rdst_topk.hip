@@ -222,30 +222,17 @@ __global__ __launch_bounds__(PICK_THREADS) void topk_pick_kernel(TopkHeader* __r
                                                                  int shift, uint32_t nbits, uint32_t pos_level, uint32_t level, uint32_t last) {
     __shared__ uint32_t wave_sum[PICK_THREADS / 64];
     if (hdr->ready) return;
-    const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
+    const uint32_t tid = threadIdx.x;
     const uint32_t remaining = k - hdr->c_below;
-    uint32_t c[4], sum = 0;
+    uint32_t c[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         c[j] = counters[4 * tid + j];
         counters[4 * tid + j] = 0;
-        sum += c[j];
     }
-    uint32_t incl = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const uint32_t y = __shfl_up(incl, o);
-        if (lane >= (uint32_t)o) incl += y;
-    }
-    if (lane == 63) wave_sum[wave] = incl;
-    __syncthreads();  // (also: every thread has read c_below before the one below writes it)
-    uint32_t before = 0;
-    for (uint32_t w = 0; w < wave; ++w) before += wave_sum[w];
-    incl += before;
-    uint32_t run = incl - sum;
-    if (!(run < remaining && remaining <= incl)) return;  // exactly one thread goes on
-    int j = 0;
-    while (j < 3 && run + c[j] < remaining) run += c[j++];
+    uint32_t run;
+    int j;
+    if (!pick_bucket(c, remaining, wave_sum, &run, &j)) return;  // exactly one thread goes on (every thread has read c_below by now)
     const uint32_t bucket = 4 * tid + (uint32_t)j, m = c[j];
     hdr->c_below += run;
     hdr->m = m;
@@ -353,14 +340,6 @@ __global__ __launch_bounds__(256) void topk_append_kernel(const TopkHeader* __re
         if (fill) sel[below + i] = t;
         else if (i < have) sel[below + i] = cand[i];
     }
-}
-
-// The inverse of map_key for ANY pair of masks (the complemented ones of RDST_TOPK_LARGEST too): the preimage whose sign
-// bit picks the mask it was mapped with.
-template <typename K>
-__device__ __forceinline__ K unmap_any(K m, K neg, K pos) {
-    const K a = (K)(m ^ neg);
-    return (K)(a >> (sizeof(K) * 8 - 1)) ? a : (K)(m ^ pos);
 }
 
 template <typename K, typename C, typename I>
@@ -475,6 +454,27 @@ int dispatch_topk(const TopkCall& c) {
 }
 
 }  // namespace
+
+// The call after its checks, for a caller that holds the library's mutex (rdst_topk_segments.hip: one far-class segment):
+// the layout is that of rdst_hip_topk_scratch_bytes(len, k, elem_bytes, index_bytes, 0).
+int rdst_internal::topk_slice_locked(const void* keys, uint64_t len, uint64_t k, void* out_keys, void* out_index, uint32_t index_bytes, void* scratch,
+                                     uint32_t elem_bytes, rdst_key_kind kind, bool largest, int cus, hipStream_t s) {
+    TopkCall c{};
+    c.L = topk_layout(len, k, elem_bytes, index_bytes, 0);
+    c.keys = keys;
+    c.len = len;
+    c.k = k;
+    c.out_keys = out_keys;
+    c.out_index = out_index;
+    c.index_bytes = index_bytes;
+    c.scratch = static_cast<char*>(scratch);
+    c.elem_bytes = elem_bytes;
+    c.kind = kind;
+    c.largest = largest;
+    c.cus = cus;
+    c.s = s;
+    return dispatch_topk(c);
+}
 
 extern "C" {
 

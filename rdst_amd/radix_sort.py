@@ -240,6 +240,13 @@ def sort_pairs_device_devlen_tensor(keys, values, length, tmp_keys=None, tmp_val
     _sort_pairs(keys, values, length, tmp_keys, tmp_values, check)
 
 
+def _index_bytes(index):
+    import torch
+    if index not in (None, torch.int32, torch.int64):
+        raise ValueError("index must be None, torch.int32 or torch.int64")
+    return 0 if index is None else (4 if index == torch.int32 else 8)
+
+
 def topk_limits(dtype, index_bytes=0):
     """``rdst_hip_topk_limits``: (digit_bits, default cand_capacity, most levels a call can take) of the partial sort for keys
     of ``dtype`` (a numpy / torch dtype or its name, ``"u128"`` / ``"i128"``); ``index_bytes``: 0 = keys only, 4 or 8."""
@@ -281,9 +288,7 @@ def topk_device_tensor(keys, k, largest=False, index=None, scratch=None, cand_ca
     k = int(k)
     if not 0 <= k <= n:
         raise ValueError("k must lie in 0..len")
-    if index not in (None, torch.int32, torch.int64):
-        raise ValueError("index must be None, torch.int32 or torch.int64")
-    index_bytes = 0 if index is None else (4 if index == torch.int32 else 8)
+    index_bytes = _index_bytes(index)
     out_keys = torch.empty((k, 2) if _wide(key) else (k,), dtype=keys.dtype, device=keys.device)
     out_index = None if index is None else torch.empty(k, dtype=index, device=keys.device)
     if k == 0:
@@ -386,6 +391,95 @@ def sort_segments_device_tensor(keys, offsets, tmp=None, values=None, tmp_values
     else:
         _call(keys, check, "rdst_hip_sort_segments_pairs_device", _ptr(keys), _ptr(values), _ptr(tmp), _ptr(tmp_values), tmp_elems, n, offp,
               n_segments, nbytes, kind, levels, vbytes)
+
+
+def topk_segments_limits(dtype, index_bytes=0):
+    """``rdst_hip_topk_segments_limits``: (wave_max, block_max, stream_max, k_stream_max) of the segmented partial sort for
+    keys of ``dtype`` (a dtype or its name, ``"u128"`` / ``"i128"``); ``index_bytes``: 0 = keys only, 4 or 8.  Segments up to
+    wave_max take one wave, up to block_max one workgroup, up to stream_max — for k up to k_stream_max — one workgroup that
+    streams them; everything else takes :func:`topk_device_tensor`'s route, one segment after another."""
+    _kind, nbytes, _levels = key_info(dtype)
+    out = (ctypes.c_uint32 * 4)()
+    _lib.check(_lib.load().rdst_hip_topk_segments_limits(nbytes, int(index_bytes), out))
+    return tuple(int(v) for v in out)
+
+
+def topk_segments_scratch_bytes(n_segments, longest_segment, k, dtype, index_bytes=0):
+    """``rdst_hip_topk_segments_scratch_bytes``: bytes of scratch :func:`topk_segments_device_tensor` needs for
+    ``n_segments`` segments, the longest of ``longest_segment`` keys of ``dtype`` (0 for widths the entry is not built for)."""
+    _kind, nbytes, _levels = key_info(dtype)
+    return int(_lib.load().rdst_hip_topk_segments_scratch_bytes(int(n_segments), int(longest_segment), int(k), nbytes, int(index_bytes)))
+
+
+def topk_segments_plan(offsets, n, k, dtype, index_bytes=0):
+    """``rdst_topk_segments_plan`` (host only): the work list of a segmented partial sort over ``n`` elements — ``(items,
+    counts, longest_far)`` with ``items`` a list of (start, len, segment) in the order the entry runs them, ``counts`` the
+    numbers of wave-, block-, stream- and far-class items and ``longest_far`` the longest far segment (0: none)."""
+    off = _host_offsets(offsets)
+    _kind, nbytes, _levels = key_info(dtype)
+    items = (_lib.SegmentItemC * max(1, off.size - 1))()
+    counts = (ctypes.c_uint64 * 4)()
+    longest = ctypes.c_uint64(0)
+    _lib.check(_lib.load().rdst_topk_segments_plan(off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), off.size - 1, int(n), int(k), nbytes,
+                                                   int(index_bytes), items, off.size - 1, counts, ctypes.byref(longest)))
+    total = int(sum(counts))
+    return [(int(it.start), int(it.len), int(it.seg)) for it in items[:total]], tuple(int(c) for c in counts), int(longest.value)
+
+
+def set_topk_segments_stream_max(stream_max=0):
+    """``rdst_hip_set_topk_segments_stream_max`` (test hook): the longest segment the stream class takes; 0 = the default."""
+    _lib.check(_lib.load().rdst_hip_set_topk_segments_stream_max(int(stream_max)))
+
+
+def topk_segments_device_tensor(keys, offsets, k, largest=False, index=None, scratch=None, check=True, key=None, out=None):
+    """``rdst_hip_topk_segments_device``: :func:`topk_device_tensor` for every segment ``keys[offsets[s]:offsets[s + 1]]`` of
+    a contiguous 1-D HIP tensor, in one call (``key="u128"/"i128"``: shape (n, 2), offsets count keys).  ``offsets``: a
+    sequence, a numpy array or a torch tensor of n_segments + 1 non-decreasing element indices, read on the HOST (a device
+    tensor is copied to the host once, here).  Returns ``(out_keys, out_index or None)`` of shape (n_segments, k): row ``s``
+    holds, in its first ``min(k, n_s)`` slots, the keys of segment ``s`` that come first in the sort's order — ``largest``:
+    last, in descending order — and, with ``index`` (``torch.int32`` / ``torch.int64``; 4- and 8-byte keys), their positions
+    inside the segment, equal keys in ascending position.  The slots from ``min(k, n_s)`` on are NOT written: pass ``out=
+    (out_keys, out_index)`` to choose what they hold.  ``keys`` is not modified.  ``scratch``: optional uint8 HIP tensor of
+    at least :func:`topk_segments_scratch_bytes` bytes, 256-byte aligned (allocated when omitted).  The call only enqueues
+    work on the tensor's current stream; ``check=False`` makes no blocking call at all."""
+    import torch
+    kind, nbytes, levels, n, per_key = _keys_operand("topk_segments_device_tensor", keys, key)
+    index_bytes = _index_bytes(index)
+    k = int(k)
+    if k < 0:
+        raise ValueError("k must not be negative")
+    off = _host_offsets(offsets)
+    n_segments = off.size - 1
+    if out is None:
+        out_keys = torch.empty((n_segments, k, 2) if _wide(key) else (n_segments, k), dtype=keys.dtype, device=keys.device)
+        out_index = None if index is None else torch.empty((n_segments, k), dtype=index, device=keys.device)
+    else:
+        out_keys, out_index = out
+        if _mismatch(out_keys, keys) or out_keys.numel() != n_segments * k * per_key:
+            raise ValueError("out keys: a contiguous tensor of the keys' dtype and device with n_segments * k keys")
+        if (out_index is None) != (index is None) or (out_index is not None and (
+                out_index.dtype != index or out_index.device != keys.device or not out_index.is_contiguous() or out_index.numel() != n_segments * k)):
+            raise ValueError("out index: a contiguous tensor of dtype `index` on the keys' device with n_segments * k elements")
+    if k == 0 or n_segments == 0:
+        return out_keys, out_index
+    longest = int((off[1:] - off[:-1]).max()) if bool((off[1:] >= off[:-1]).all()) else 0   # (a decreasing table: the library says so)
+    need = int(_lib.load().rdst_hip_topk_segments_scratch_bytes(n_segments, longest, k, nbytes, index_bytes))
+    scratch, sbytes = _scratch(scratch, need, keys.device)
+    _call(keys, check, "rdst_hip_topk_segments_device", _ptr(keys), n, off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), n_segments, k,
+          _ptr(out_keys), _ptr(out_index), index_bytes, _ptr(scratch), sbytes, nbytes, kind, levels, _lib.RDST_TOPK_LARGEST if largest else 0)
+    return out_keys, out_index
+
+
+def topk_rows_tensor(keys2d, k, largest=False, index=None, scratch=None, check=True, out=None):
+    """:func:`topk_segments_device_tensor` for the rows of a contiguous 2-D HIP tensor (a score or logits matrix): the ``k``
+    first (``largest``: last) keys of every row and, with ``index``, their columns.  ``k`` may exceed the row length: the
+    slots past it are not written."""
+    _on_device("topk_rows_tensor", keys2d)
+    if keys2d.dim() != 2 or not keys2d.is_contiguous():
+        raise ValueError("topk_rows_tensor needs a contiguous 2-D tensor")
+    rows, cols = int(keys2d.shape[0]), int(keys2d.shape[1])
+    offsets = np.arange(rows + 1, dtype=np.uint64) * np.uint64(cols)
+    return topk_segments_device_tensor(keys2d.reshape(-1), offsets, k, largest=largest, index=index, scratch=scratch, check=check, out=out)
 
 
 def segments_device_offsets_scratch_bytes(n_segments):
