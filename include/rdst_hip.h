@@ -461,6 +461,77 @@ int rdst_hip_debug_segments_plan_device(const void* dev_offsets, uint32_t offset
                                         rdst_segment_item* items_out, uint64_t capacity, uint64_t class_counts_out[3],
                                         uint64_t* tmp_elems_out, uint32_t* flags_out, void* stream);
 
+/* rdst_hip_topk_segments_device with the table of borders in DEVICE memory: a CSR row pointer, the cumulative sum of a ragged
+ * batch's lengths, the bucket borders rdst_hip_split_top_level_device leaves behind — no copy of the table to the host, no
+ * host plan.  dev_offsets follows the rules of rdst_hip_sort_segments_device_offsets: n_segments + 1 unsigned integers of
+ * offset_bytes (4 or 8) bytes, aligned to that size, read only, and read in stream order (the kernel that writes the table may
+ * still be running when the call returns); n_segments <= 2^30; len < 2^32 as for every partial sort.  The result is exactly
+ * rdst_hip_topk_segments_device's: row s of the outputs starts at element s * k; its first min(k, n_s) slots hold, bit for
+ * bit, what rdst_hip_topk_device gives for segment s, positions local to the segment; the slots behind, empty segments and
+ * the input are not written.  Keys only: every width and kind; with an index (4 or 8 bytes): 4- and 8-byte keys;
+ * RDST_TOPK_LARGEST as there.
+ *
+ * dev_scratch: 256-byte aligned, at least rdst_hip_topk_segments_device_offsets_scratch_bytes(n_segments, far_capacity, k,
+ * elem_bytes, index_bytes) bytes.  The plan lives there: a class key and the segment index per segment, one stable (u32, u32)
+ * pair sort of them by the library's own pair route (so rdst_hip_last_route, the profile runs and rdst_hip_debug_last_sample
+ * see that sort too), and the work list — rdst_topk_segments_plan's, item for item.  It needs no clearing; stream order makes
+ * it reusable by the next call on the same stream.
+ *
+ * far_capacity chooses between two modes, as tmp_elems does for rdst_hip_sort_segments_device_offsets:
+ *   far_capacity == 0: FULLY ASYNCHRONOUS.  The call enqueues the plan and three launches (grids bounded by what the host
+ *       knows — n_segments and len —, counts read from the scratch; surplus waves and workgroups return at once) and returns:
+ *       no copy to or from the host, no wait on an event or on the stream, no staging buffer.  The one exception is the one
+ *       every entry shares: a library workspace that has to grow, here for the plan's pair sort.  In this mode THE STREAM CLASS
+ *       HAS NO UPPER LENGTH: with k <= k_stream_max (rdst_hip_topk_segments_limits) every segment beyond block_max is served
+ *       by one workgroup's streamed radix select, longest first, whatever rdst_hip_set_topk_segments_stream_max says.  For
+ *       such a k the call has no data-dependent failure and never needs the host — and the host knows k before it calls.
+ *       One workgroup on a very long segment is a performance cliff (a segment of 2^24 keys is read by 1 of 256 compute
+ *       units), never a wrong answer; far_capacity > 0 is the answer to it.  With k > k_stream_max a segment beyond block_max
+ *       cannot be served, and neither that nor a table the device finds invalid (decreasing, last offset past len) can be
+ *       answered by the return code: NO output element is written, the bit of value 16 (0x10) of the sticky device error word
+ *       is set, and rdst_hip_device_status returns RDST_ERR_DEVICE once.
+ *   far_capacity > 0: EVERY TABLE, ONE WAIT.  The classes are exactly rdst_hip_topk_segments_device's (they follow
+ *       rdst_hip_topk_segments_limits and rdst_hip_set_topk_segments_stream_max).  The call WAITS once for `stream` after the
+ *       plan and reads the four counts, the longest far segment and the flags; with far segments it reads their items too
+ *       (one further wait).  It launches the three batched classes and runs the far segments one after another by
+ *       rdst_hip_topk_device's route, in the scratch behind the plan.  Because the host sees the flags, an invalid table or a
+ *       longest far segment above far_capacity is RDST_ERR_ARG with nothing written and nothing left in the error word.  A
+ *       caller without a better bound passes len.
+ * Profiling: the batched launches end rdst_hip_topk_segments_device's stages, RDST_STAGE_SEGMENTS | (class << 8).
+ * Arguments, checked in this order before any device work:
+ *   1. the key arguments, len and flags as rdst_hip_topk_segments_device checks them (its codes and messages);
+ *   2. k == 0 or n_segments == 0 -> RDST_OK, nothing else is looked at;
+ *   3. the table as rdst_hip_sort_segments_device_offsets checks it: n_segments > 2^30 -> RDST_ERR_UNSUPPORTED; offset_bytes
+ *      not 4 or 8, NULL dev_offsets -> RDST_ERR_ARG; dev_offsets misaligned to offset_bytes -> RDST_ERR_ALIGN;
+ *   4. the outputs as rdst_hip_topk_segments_device checks them: NULL dev_out_keys -> RDST_ERR_ARG; misaligned ->
+ *      RDST_ERR_ALIGN; with an index: index_bytes not 4 or 8 -> RDST_ERR_ARG, key width not 4 or 8 -> RDST_ERR_UNSUPPORTED,
+ *      misaligned index pointer -> RDST_ERR_ALIGN (with a NULL dev_out_index, index_bytes is not looked at);
+ *   5. the scratch: NULL -> RDST_ERR_ARG; not 256-byte aligned -> RDST_ERR_ALIGN; far_capacity >= 2^32 or scratch_bytes below
+ *      rdst_hip_topk_segments_device_offsets_scratch_bytes(...) -> RDST_ERR_ARG. */
+int rdst_hip_topk_segments_device_offsets(const void* dev_keys, uint64_t len,
+                                          const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments, uint64_t k,
+                                          void* dev_out_keys, void* dev_out_index, uint32_t index_bytes,
+                                          void* dev_scratch, uint64_t scratch_bytes, uint64_t far_capacity,
+                                          uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels,
+                                          uint32_t flags, void* stream);
+/* The scratch of the call above.  Pure, monotone in every argument: the plan's layout
+ * (rdst_hip_sort_segments_device_offsets_scratch_bytes(n_segments): 32 bytes per segment and a 256-byte header) and, with
+ * far_capacity > 0, behind it rdst_hip_topk_scratch_bytes(far_capacity, min(k, far_capacity), elem_bytes, index_bytes, 0).
+ * 0 for n_segments == 0 or > 2^30, far_capacity >= 2^32 and unsupported widths. */
+uint64_t rdst_hip_topk_segments_device_offsets_scratch_bytes(uint64_t n_segments, uint64_t far_capacity, uint64_t k,
+                                                             uint32_t elem_bytes, uint32_t index_bytes);
+/* Test hook, BLOCKING, like rdst_hip_debug_segments_plan_device: runs the device plan of the call above for this k and these
+ * widths and copies out the work list it produced, in rdst_topk_segments_plan's output form.  unbounded_stream != 0: the
+ * classes of the asynchronous mode (no upper length of the stream class); 0: the wait mode's.  *flags_out: 1 = offsets
+ * decrease somewhere, 2 = the last offset lies past len (then RDST_OK with the flags as the answer; counts and items mean
+ * nothing); the error word is left alone.  dev_scratch: the plan's part of the scratch above.  k == 0: no items.  A
+ * `capacity` below the four counts' sum: RDST_ERR_ARG with the counts, *longest_far_out and *flags_out written. */
+int rdst_hip_debug_topk_segments_plan_device(const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments, uint64_t len,
+                                             uint64_t k, uint32_t elem_bytes, uint32_t index_bytes, uint32_t unbounded_stream,
+                                             void* dev_scratch, uint64_t scratch_bytes,
+                                             rdst_segment_item* items_out, uint64_t capacity, uint64_t class_counts_out[4],
+                                             uint64_t* longest_far_out, uint32_t* flags_out, void* stream);
+
 /* [u8; N] rows (N = n_bytes in 1..RDST_BYTES_MAX_N), device-resident, sorted IN PLACE in lexicographic order
  * (src/radix_key_impl.rs:78-85).  No alignment requirement on dev_rows.  dev_scratch: at least
  * rdst_hip_sort_bytes_scratch_bytes(len, n_bytes) bytes, 256-byte aligned.  len <= 1: no-op.

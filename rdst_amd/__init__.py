@@ -46,6 +46,9 @@ from .radix_sort import (  # noqa: F401
     topk_limits,
     topk_state,
     topk_segments_device_tensor,
+    topk_segments_device_offsets_tensor,
+    topk_segments_device_offsets_scratch_bytes,
+    topk_segments_plan_device,
     topk_rows_tensor,
     topk_segments_scratch_bytes,
     topk_segments_limits,
@@ -72,5 +75,5 @@ __all__ = [
     "sort_device_devlen_tensor", "sort_pairs_device_devlen_tensor",
     "topk_device_tensor", "topk_scratch_bytes", "topk_limits", "topk_state",
     "topk_segments_device_tensor", "topk_rows_tensor", "topk_segments_scratch_bytes", "topk_segments_limits", "topk_segments_plan",
-    "set_topk_segments_stream_max",
+    "set_topk_segments_stream_max", "topk_segments_device_offsets_tensor", "topk_segments_device_offsets_scratch_bytes", "topk_segments_plan_device",
 ]

@@ -176,6 +176,25 @@ int stage_segment_items(int device, const rdst_segment_item* items, size_t count
 // index_bytes, 0) in `scratch`; `cus`: the device's compute units.  No copy to the host, no wait.
 int topk_slice_locked(const void* keys, uint64_t len, uint64_t k, void* out_keys, void* out_index, uint32_t index_bytes, void* scratch,
                       uint32_t elem_bytes, rdst_key_kind kind, bool largest, int cus, hipStream_t s);
+// rdst_topk_segments.hip: the three batched launches of the segmented partial sort over an item table in device memory,
+// for rdst_topk_segments_offsets.hip.  One call as the launches see it:
+struct TopkSegmentsCall {
+    const void* keys;
+    uint64_t k;
+    void *out_keys, *out_index;
+    uint32_t index_bytes, elem_bytes;
+    rdst_key_kind kind;
+    bool largest;
+    hipStream_t s;
+};
+// `hdr` == nullptr: counts[0 .. 2] are the wave, block and stream class's item counts and the classes follow one another in
+// `items`.  With `hdr` (the plan header, rdst_segments_layout.h: TopkPlanHeader): the counted kernels, which read their item
+// range from it; counts[0 .. 2] bound the counts, for the grids alone.  Ends the stages RDST_STAGE_SEGMENTS | (class << 8).
+// No copy to the host, no wait.
+int topk_segments_launch_locked(const TopkSegmentsCall& c, const rdst_segment_item* items, const uint32_t* hdr, const uint64_t counts[3]);
+// rdst_segments.hip: what every entry with a table of borders in device memory checks of it before any device work
+// (n_segments, offset_bytes, the pointer and its alignment, 4-byte offsets against len); no lock needed.
+int check_offsets_table(const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments, uint64_t len);
 // Profiling (rdst_hip_set_profiling): open a run of its own / close the stage that ends here.  No-ops when profiling is off.
 int profile_open_run(hipStream_t s);
 int profile_stage_end(hipStream_t s, uint32_t stage);

@@ -1132,6 +1132,10 @@ int rdst_internal::stage_segment_items(int device, const rdst_segment_item* item
     return stage_items(g_staging[device], items, count, dev_dst, s);
 }
 
+int rdst_internal::check_offsets_table(const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments, uint64_t len) {
+    return ::check_offsets_table(dev_offsets, offset_bytes, n_segments, len);
+}
+
 extern "C" int rdst_hip_sort_segments_device_offsets(void* dev_keys, void* dev_tmp, uint64_t tmp_elems, uint64_t len, const void* dev_offsets,
                                                      uint32_t offset_bytes, uint64_t n_segments, uint32_t elem_bytes, rdst_key_kind kind,
                                                      uint32_t levels, void* dev_scratch, uint64_t scratch_bytes, void* stream) {

@@ -7,6 +7,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include <initializer_list>
+
 #include "rdst_hip.h"
 
 namespace rdst_segments_layout {
@@ -49,6 +51,60 @@ constexpr PlanLayout plan_layout(uint64_t n_segments) {
     const uint64_t arr = up256(n_segments * sizeof(uint32_t)), at = PLAN_HEADER_BYTES;
     return {at, at + arr, at + 2 * arr, at + 3 * arr, at + 4 * arr, at + 4 * arr + up256(n_segments * sizeof(rdst_segment_item))};
 }
+
+// ---- the segmented partial sort with device-resident offsets (rdst_topk_segments_offsets.hip) ------------------------------
+// Its plan keeps plan_layout's arrays.  The header words (u32) its kernels and the counted top-k kernels
+// (rdst_topk_segments.hip) index:
+enum TopkPlanHeader : int {
+    HDR_TOPK_N_WAVE = 0,       // items of the wave class
+    HDR_TOPK_N_BLOCK = 1,      // items of the block class (they follow the wave class in the item table)
+    HDR_TOPK_N_STREAM = 2,     // items of the stream class (they follow the block class)
+    HDR_TOPK_N_FAR = 3,        // items of the far class (they follow the stream class, in segment order)
+    HDR_TOPK_FLAGS = 4,        // TOPK_PLAN_* bits: what the plan found wrong
+    HDR_TOPK_LONGEST_FAR = 6,  // u64 in the words 6 and 7: the longest far segment
+    HDR_TOPK_RUN_WAVE = 8,     // the counts the counted kernels run: the three N_ words, or 0, 0, 0 when nothing may be written
+    HDR_TOPK_RUN_BLOCK = 9,
+    HDR_TOPK_RUN_STREAM = 10,
+    HDR_TOPK_WORDS = 64,
+};
+static_assert(HDR_TOPK_WORDS * sizeof(uint32_t) == PLAN_HEADER_BYTES, "the header the kernels index is the header of the layout");
+constexpr uint32_t TOPK_PLAN_DECREASING = 1;  // offsets[s + 1] < offsets[s] somewhere
+constexpr uint32_t TOPK_PLAN_PAST_LEN = 2;    // offsets[n_segments] > len
+constexpr uint32_t TOPK_PLAN_FAR = 4;         // asynchronous mode only: a far segment, which only the host can enqueue
+
+// The class key of a segment of n keys (n < 2^32): the plan sorts (key, segment) pairs by the library's stable 4-level pair
+// sort, and the sorted pairs are the work list.  `stream_limit`: the longest segment of the stream class (block_max: none).
+//   0                                       wave class: stays in segment order
+//   1 + (block_max - n)                     block class, wave_max < n <= block_max: 1 .. block_max - wave_max, longest first
+//   TOPK_KEY_STREAM_LAST - (n - block_max - 1)
+//                                           stream class, block_max < n <= 2^32 - 1: block_max - 1 .. TOPK_KEY_STREAM_LAST,
+//                                           longest first (the sort is stable: ties in segment order)
+//   TOPK_KEY_FAR                            far class: in segment order
+//   TOPK_KEY_NONE                           no key: no item
+constexpr uint32_t TOPK_KEY_STREAM_LAST = 0xFFFFFFFDu, TOPK_KEY_FAR = 0xFFFFFFFEu, TOPK_KEY_NONE = 0xFFFFFFFFu;
+constexpr uint32_t topk_class(uint64_t n, uint32_t wave_max, uint32_t block_max, uint32_t stream_limit) {  // 0 .. 3, or 4: no item
+    return n == 0 ? 4u : (n <= wave_max ? 0u : (n <= block_max ? 1u : (n <= stream_limit ? 2u : 3u)));
+}
+constexpr uint32_t topk_class_key(uint64_t n, uint32_t wave_max, uint32_t block_max, uint32_t stream_limit) {
+    const uint32_t c = topk_class(n, wave_max, block_max, stream_limit);
+    return c == 0 ? 0u
+                  : (c == 1 ? 1u + (block_max - (uint32_t)n)
+                            : (c == 2 ? TOPK_KEY_STREAM_LAST - ((uint32_t)n - block_max - 1u) : (c == 3 ? TOPK_KEY_FAR : TOPK_KEY_NONE)));
+}
+// wave < block < stream < far < none for every width: the block keys end at block_max - wave_max, the stream keys start at
+// block_max - 1 (n = 2^32 - 1)
+constexpr bool topk_class_keys_disjoint() {
+    for (uint32_t kb : {1u, 2u, 4u, 8u, 16u})
+        for (uint32_t vb : {0u, 4u}) {
+            const uint32_t wm = wave_max(kb), bm = block_max(kb, vb);
+            if (!(wm >= 2 && wm < bm)) return false;
+            if (!(topk_class_key(wm + 1, wm, bm, 0xFFFFFFFFu) == bm - wm && topk_class_key(bm, wm, bm, 0xFFFFFFFFu) == 1)) return false;
+            if (!(topk_class_key(0xFFFFFFFFull, wm, bm, 0xFFFFFFFFu) == bm - 1 && bm - wm < bm - 1)) return false;
+            if (!(topk_class_key((uint64_t)bm + 1, wm, bm, 0xFFFFFFFFu) == TOPK_KEY_STREAM_LAST && TOPK_KEY_STREAM_LAST < TOPK_KEY_FAR)) return false;
+        }
+    return TOPK_KEY_FAR < TOPK_KEY_NONE;
+}
+static_assert(topk_class_keys_disjoint(), "the class keys of the four classes lie in disjoint, ascending ranges");
 
 // The nowait entries: the plan's layout, then what the tiled route keeps for the long class.  What the host knows bounds
 // that class: a long segment holds more than block_max keys, so there are at most n_long_bound = min(n_segments,

@@ -22,6 +22,10 @@
 //   far                          everything else, one segment after another through rdst_hip_topk_device's own route
 //                                (rdst_internal::topk_slice_locked), in the part of the scratch behind the item table.
 //
+// Each of the three kernels is one body (topk_segment_*_body) under two entries: the kernel the host entry launches with the
+// counts it knows, and a ..._counted_kernel that reads its item range from the plan header in device memory
+// (rdst_hip_topk_segments_device_offsets, rdst_topk_segments_offsets.hip, through rdst_internal::topk_segments_launch_locked).
+//
 // Slots past a segment's end hold the largest mapped key; they start behind every real key and stay there (rdst_segments.hip).
 // With RDST_TOPK_LARGEST both xor masks are complemented, as run_topk does; the kernels always map.
 #include <hip/hip_runtime.h>
@@ -89,8 +93,8 @@ __device__ __forceinline__ void store_rank(const Rows<K>& o, uint32_t seg, uint3
 // ---- wave class --------------------------------------------------------------------------------------------------------------
 
 template <typename K, bool IDX>
-__global__ __launch_bounds__(SEG_WAVES * 64) void topk_segment_wave_kernel(const K* __restrict__ keys, const rdst_segment_item* __restrict__ items,
-                                                                            uint32_t n_items, const Rows<K> o) {
+__device__ __forceinline__ void topk_segment_wave_body(const K* __restrict__ keys, const rdst_segment_item* __restrict__ items, uint32_t n_items,
+                                                       const Rows<K> o) {
     constexpr int LEVELS = (int)sizeof(K);
     constexpr int KPT = L::wave_kpt(sizeof(K));
     constexpr int CAP = 64 * KPT;
@@ -179,6 +183,12 @@ __global__ __launch_bounds__(SEG_WAVES * 64) void topk_segment_wave_kernel(const
         const uint32_t rank = (uint32_t)i * 64u + (uint32_t)lane;
         if (i < rounds && rank < k_s) store_rank<K, IDX>(o, it.seg, rank, mk[i], mv[i]);
     }
+}
+
+template <typename K, bool IDX>
+__global__ __launch_bounds__(SEG_WAVES * 64) void topk_segment_wave_kernel(const K* __restrict__ keys, const rdst_segment_item* __restrict__ items,
+                                                                            uint32_t n_items, const Rows<K> o) {
+    topk_segment_wave_body<K, IDX>(keys, items, n_items, o);
 }
 
 // ---- block class: the level loop, shared with the stream class ------------------------------------------------------------------
@@ -274,13 +284,11 @@ __device__ __forceinline__ void store_first(const K (&mk)[KPT], const uint32_t (
 }
 
 template <typename K, bool IDX>
-__global__ __launch_bounds__(BLOCK_THREADS) void topk_segment_block_kernel(const K* __restrict__ keys, const rdst_segment_item* __restrict__ items,
-                                                                           const Rows<K> o) {
+__device__ __forceinline__ void topk_segment_block_body(const K* __restrict__ keys, const rdst_segment_item it, const Rows<K> o) {
     constexpr int KPT = BlockLds<K, IDX>::KPT;
     constexpr uint32_t TILE = BlockLds<K, IDX>::TILE;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const BlockLds<K, IDX> lds(smem);
-    const rdst_segment_item it = items[blockIdx.x];  // the grid is exactly this class's items
     const uint32_t n = it.len < TILE ? it.len : TILE;  // (the plan never hands this class a longer one)
     const uint32_t k_s = o.k < n ? (uint32_t)o.k : n;
     const K* seg = keys + it.start;
@@ -298,6 +306,12 @@ __global__ __launch_bounds__(BLOCK_THREADS) void topk_segment_block_kernel(const
     }
     block_order<K, IDX, KPT>(mk, mv, rounds, lds);
     store_first<K, IDX, KPT>(mk, mv, rounds, k_s, it.seg, o);
+}
+
+template <typename K, bool IDX>
+__global__ __launch_bounds__(BLOCK_THREADS) void topk_segment_block_kernel(const K* __restrict__ keys, const rdst_segment_item* __restrict__ items,
+                                                                           const Rows<K> o) {
+    topk_segment_block_body<K, IDX>(keys, items[blockIdx.x], o);  // the grid is exactly this class's items
 }
 
 // ---- stream class ------------------------------------------------------------------------------------------------------------
@@ -393,8 +407,7 @@ __device__ __forceinline__ void collect_trip(const K (&m)[G][E], const bool (&ok
 }
 
 template <typename K, bool IDX>
-__global__ __launch_bounds__(BLOCK_THREADS) void topk_segment_stream_kernel(const K* __restrict__ keys, const rdst_segment_item* __restrict__ items,
-                                                                            const Rows<K> o) {
+__device__ __forceinline__ void topk_segment_stream_body(const K* __restrict__ keys, const rdst_segment_item it, const Rows<K> o) {
     constexpr int KPT = BlockLds<K, IDX>::KPT;
     constexpr uint32_t TILE = BlockLds<K, IDX>::TILE;
     constexpr uint32_t VEC = KeyVec<K>::N;
@@ -408,7 +421,6 @@ __global__ __launch_bounds__(BLOCK_THREADS) void topk_segment_stream_kernel(cons
     const BlockLds<K, IDX> lds(smem);
     uint32_t* cnt = lds.wave_hist;
     const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const rdst_segment_item it = items[blockIdx.x];  // the grid is exactly this class's items
     const uint32_t n = it.len;
     const K* seg = keys + it.start;
     uint32_t k = o.k < n ? (uint32_t)o.k : n;
@@ -545,23 +557,47 @@ __global__ __launch_bounds__(BLOCK_THREADS) void topk_segment_stream_kernel(cons
     store_first<K, IDX, KPT>(rk, rv, rounds, k < filled ? k : filled, it.seg, o);
 }
 
+template <typename K, bool IDX>
+__global__ __launch_bounds__(BLOCK_THREADS) void topk_segment_stream_kernel(const K* __restrict__ keys, const rdst_segment_item* __restrict__ items,
+                                                                            const Rows<K> o) {
+    topk_segment_stream_body<K, IDX>(keys, items[blockIdx.x], o);  // the grid is exactly this class's items
+}
+
+// ---- the same three bodies with their item range read from the plan header in device memory (device-resident offsets) ----------
+//
+// rdst_topk_segments_offsets.hip writes the header (rdst_segments_layout.h: TopkPlanHeader) and the item table.  The grids are
+// bounds the host can state without the counts; waves and workgroups past the count return before any barrier.
+template <typename K, bool IDX>
+__global__ __launch_bounds__(SEG_WAVES * 64) void topk_segment_wave_counted_kernel(const K* __restrict__ keys, const rdst_segment_item* __restrict__ items,
+                                                                                    const uint32_t* __restrict__ hdr, const Rows<K> o) {
+    topk_segment_wave_body<K, IDX>(keys, items, hdr[L::HDR_TOPK_RUN_WAVE], o);
+}
+
+template <typename K, bool IDX>
+__global__ __launch_bounds__(BLOCK_THREADS) void topk_segment_block_counted_kernel(const K* __restrict__ keys, const rdst_segment_item* __restrict__ items,
+                                                                                   const uint32_t* __restrict__ hdr, const Rows<K> o) {
+    if (blockIdx.x >= hdr[L::HDR_TOPK_RUN_BLOCK]) return;  // block-uniform
+    topk_segment_block_body<K, IDX>(keys, items[hdr[L::HDR_TOPK_N_WAVE] + blockIdx.x], o);
+}
+
+template <typename K, bool IDX>
+__global__ __launch_bounds__(BLOCK_THREADS) void topk_segment_stream_counted_kernel(const K* __restrict__ keys, const rdst_segment_item* __restrict__ items,
+                                                                                    const uint32_t* __restrict__ hdr, const Rows<K> o) {
+    if (blockIdx.x >= hdr[L::HDR_TOPK_RUN_STREAM]) return;  // block-uniform
+    topk_segment_stream_body<K, IDX>(keys, items[hdr[L::HDR_TOPK_N_WAVE] + hdr[L::HDR_TOPK_N_BLOCK] + blockIdx.x], o);
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------------
 
-struct SegTopkCall {
-    const void* keys;
-    uint64_t k;
-    void *out_keys, *out_index;
-    uint32_t index_bytes, elem_bytes;
-    rdst_key_kind kind;
-    bool largest;
-    hipStream_t s;
-};
+using SegTopkCall = rdst_internal::TopkSegmentsCall;
 
 bool misaligned(const void* p, uint64_t to) { return reinterpret_cast<uintptr_t>(p) % to != 0; }
 
 // The three batched launches over the item table in device memory: wave class first, then block class, then stream class.
+// `hdr` == nullptr: the host knows the counts, counts[0 .. 2], and the classes follow one another in `items`.  With `hdr`, the
+// plan header in device memory: the counts stand there, and counts[0 .. 2] are the host's bounds on them, for the grids alone.
 template <typename K, bool IDX>
-int launch_classes_t(const SegTopkCall& c, const rdst_segment_item* items, const uint64_t counts[4]) {
+int launch_classes_t(const SegTopkCall& c, const rdst_segment_item* items, const uint32_t* hdr, const uint64_t counts[3]) {
     constexpr size_t wave_lds = wave_lds_bytes(sizeof(K), IDX), block_lds = block_lds_bytes(sizeof(K), IDX);
     static_assert(wave_lds <= LDS_LIMIT && block_lds + STREAM_STATIC_LDS <= LDS_LIMIT, "a workgroup's LDS stays within 160 KiB");
     unsigned __int128 neg, pos;
@@ -572,42 +608,56 @@ int launch_classes_t(const SegTopkCall& c, const rdst_segment_item* items, const
         o.pos = (K)~o.pos;
     }
     const K* keys = static_cast<const K*>(c.keys);
+    const dim3 wave_grid((uint32_t)((counts[0] + SEG_WAVES - 1) / SEG_WAVES)), block_grid((uint32_t)counts[1]), stream_grid((uint32_t)counts[2]);
     int rc;
     if (counts[0]) {
-        rc = launch("topk_segment_wave_kernel", topk_segment_wave_kernel<K, IDX>, dim3((uint32_t)((counts[0] + SEG_WAVES - 1) / SEG_WAVES)),
-                    dim3(SEG_WAVES * 64), wave_lds, c.s, keys, items, (uint32_t)counts[0], o);
+        rc = hdr ? launch("topk_segment_wave_counted_kernel", topk_segment_wave_counted_kernel<K, IDX>, wave_grid, dim3(SEG_WAVES * 64), wave_lds, c.s, keys,
+                          items, hdr, o)
+                 : launch("topk_segment_wave_kernel", topk_segment_wave_kernel<K, IDX>, wave_grid, dim3(SEG_WAVES * 64), wave_lds, c.s, keys, items,
+                          (uint32_t)counts[0], o);
         if (rc) return rc;
         if ((rc = rdst_internal::profile_stage_end(c.s, RDST_STAGE_SEGMENTS))) return rc;
     }
     if (counts[1]) {
-        rc = launch("topk_segment_block_kernel", topk_segment_block_kernel<K, IDX>, dim3((uint32_t)counts[1]), dim3(BLOCK_THREADS), block_lds, c.s, keys,
-                    items + counts[0], o);
+        rc = hdr ? launch("topk_segment_block_counted_kernel", topk_segment_block_counted_kernel<K, IDX>, block_grid, dim3(BLOCK_THREADS), block_lds, c.s, keys,
+                          items, hdr, o)
+                 : launch("topk_segment_block_kernel", topk_segment_block_kernel<K, IDX>, block_grid, dim3(BLOCK_THREADS), block_lds, c.s, keys,
+                          items + counts[0], o);
         if (rc) return rc;
         if ((rc = rdst_internal::profile_stage_end(c.s, RDST_STAGE_SEGMENTS | (1u << 8)))) return rc;
     }
     if (counts[2]) {
-        rc = launch("topk_segment_stream_kernel", topk_segment_stream_kernel<K, IDX>, dim3((uint32_t)counts[2]), dim3(BLOCK_THREADS), block_lds, c.s, keys,
-                    items + counts[0] + counts[1], o);
+        rc = hdr ? launch("topk_segment_stream_counted_kernel", topk_segment_stream_counted_kernel<K, IDX>, stream_grid, dim3(BLOCK_THREADS), block_lds, c.s,
+                          keys, items, hdr, o)
+                 : launch("topk_segment_stream_kernel", topk_segment_stream_kernel<K, IDX>, stream_grid, dim3(BLOCK_THREADS), block_lds, c.s, keys,
+                          items + counts[0] + counts[1], o);
         if (rc) return rc;
         if ((rc = rdst_internal::profile_stage_end(c.s, RDST_STAGE_SEGMENTS | (2u << 8)))) return rc;
     }
     return RDST_OK;
 }
 
-int launch_classes(const SegTopkCall& c, const rdst_segment_item* items, const uint64_t counts[4]) {
-    if (c.index_bytes != 0) return c.elem_bytes == 4 ? launch_classes_t<uint32_t, true>(c, items, counts) : launch_classes_t<uint64_t, true>(c, items, counts);
+int launch_classes(const SegTopkCall& c, const rdst_segment_item* items, const uint32_t* hdr, const uint64_t counts[3]) {
+    if (c.index_bytes != 0)
+        return c.elem_bytes == 4 ? launch_classes_t<uint32_t, true>(c, items, hdr, counts) : launch_classes_t<uint64_t, true>(c, items, hdr, counts);
     switch (c.elem_bytes) {
-        case 1: return launch_classes_t<uint8_t, false>(c, items, counts);
-        case 2: return launch_classes_t<uint16_t, false>(c, items, counts);
-        case 4: return launch_classes_t<uint32_t, false>(c, items, counts);
-        case 8: return launch_classes_t<uint64_t, false>(c, items, counts);
-        default: return launch_classes_t<u128, false>(c, items, counts);
+        case 1: return launch_classes_t<uint8_t, false>(c, items, hdr, counts);
+        case 2: return launch_classes_t<uint16_t, false>(c, items, hdr, counts);
+        case 4: return launch_classes_t<uint32_t, false>(c, items, hdr, counts);
+        case 8: return launch_classes_t<uint64_t, false>(c, items, hdr, counts);
+        default: return launch_classes_t<u128, false>(c, items, hdr, counts);
     }
 }
 
 uint64_t table_bytes(uint64_t n_segments) { return L::up256(n_segments * sizeof(rdst_segment_item)); }
 
 }  // namespace
+
+int rdst_internal::topk_segments_launch_locked(const TopkSegmentsCall& c, const rdst_segment_item* items, const uint32_t* hdr, const uint64_t counts[3]) {
+    if (counts[0] >= (1ull << 33) || counts[1] >= (1ull << 31) || counts[2] >= (1ull << 31))
+        return set_error(RDST_ERR_ARG, "segments: too many segments of one class for one launch");
+    return launch_classes(c, items, hdr, counts);
+}
 
 extern "C" uint64_t rdst_hip_topk_segments_scratch_bytes(uint64_t n_segments, uint64_t longest_segment, uint64_t k, uint32_t elem_bytes,
                                                          uint32_t index_bytes) {
@@ -661,7 +711,7 @@ extern "C" int rdst_hip_topk_segments_device(const void* dev_keys, uint64_t len,
         RDST_HIP_TRY(hipGetDevice(&dev));
         if ((rc = rdst_internal::profile_open_run(c.s))) return rc;
         if ((rc = rdst_internal::stage_segment_items(dev, items.data(), (size_t)batched, dev_scratch, c.s))) return rc;
-        if ((rc = launch_classes(c, static_cast<const rdst_segment_item*>(dev_scratch), counts))) return rc;
+        if ((rc = launch_classes(c, static_cast<const rdst_segment_item*>(dev_scratch), nullptr, counts))) return rc;
     }
     // far segments one after another, each by the whole-array route (no copy to the host, no wait), in the scratch behind the table
     char* far_scratch = static_cast<char*>(dev_scratch) + table_bytes(n_segments);

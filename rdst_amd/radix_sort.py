@@ -431,6 +431,21 @@ def set_topk_segments_stream_max(stream_max=0):
     _lib.check(_lib.load().rdst_hip_set_topk_segments_stream_max(int(stream_max)))
 
 
+def _topk_rows_out(keys, key, per_key, index, n_segments, k, out):
+    """(out_keys, out_index) of a segmented partial sort: the caller's pair, checked, or fresh (n_segments, k) tensors"""
+    import torch
+    if out is None:
+        out_keys = torch.empty((n_segments, k, 2) if _wide(key) else (n_segments, k), dtype=keys.dtype, device=keys.device)
+        return out_keys, None if index is None else torch.empty((n_segments, k), dtype=index, device=keys.device)
+    out_keys, out_index = out
+    if _mismatch(out_keys, keys) or out_keys.numel() != n_segments * k * per_key:
+        raise ValueError("out keys: a contiguous tensor of the keys' dtype and device with n_segments * k keys")
+    if (out_index is None) != (index is None) or (out_index is not None and (
+            out_index.dtype != index or out_index.device != keys.device or not out_index.is_contiguous() or out_index.numel() != n_segments * k)):
+        raise ValueError("out index: a contiguous tensor of dtype `index` on the keys' device with n_segments * k elements")
+    return out_keys, out_index
+
+
 def topk_segments_device_tensor(keys, offsets, k, largest=False, index=None, scratch=None, check=True, key=None, out=None):
     """``rdst_hip_topk_segments_device``: :func:`topk_device_tensor` for every segment ``keys[offsets[s]:offsets[s + 1]]`` of
     a contiguous 1-D HIP tensor, in one call (``key="u128"/"i128"``: shape (n, 2), offsets count keys).  ``offsets``: a
@@ -450,16 +465,7 @@ def topk_segments_device_tensor(keys, offsets, k, largest=False, index=None, scr
         raise ValueError("k must not be negative")
     off = _host_offsets(offsets)
     n_segments = off.size - 1
-    if out is None:
-        out_keys = torch.empty((n_segments, k, 2) if _wide(key) else (n_segments, k), dtype=keys.dtype, device=keys.device)
-        out_index = None if index is None else torch.empty((n_segments, k), dtype=index, device=keys.device)
-    else:
-        out_keys, out_index = out
-        if _mismatch(out_keys, keys) or out_keys.numel() != n_segments * k * per_key:
-            raise ValueError("out keys: a contiguous tensor of the keys' dtype and device with n_segments * k keys")
-        if (out_index is None) != (index is None) or (out_index is not None and (
-                out_index.dtype != index or out_index.device != keys.device or not out_index.is_contiguous() or out_index.numel() != n_segments * k)):
-            raise ValueError("out index: a contiguous tensor of dtype `index` on the keys' device with n_segments * k elements")
+    out_keys, out_index = _topk_rows_out(keys, key, per_key, index, n_segments, k, out)
     if k == 0 or n_segments == 0:
         return out_keys, out_index
     longest = int((off[1:] - off[:-1]).max()) if bool((off[1:] >= off[:-1]).all()) else 0   # (a decreasing table: the library says so)
@@ -519,6 +525,66 @@ def segments_plan_device(offsets, n, dtype, val_bytes=0, scratch=None):
     total = int(counts[0] + counts[1] + counts[2]) if not flags.value else 0
     return ([(int(it.start), int(it.len), int(it.seg)) for it in items[:total]], tuple(int(c) for c in counts), int(tmp_elems.value),
             int(flags.value))
+
+
+def topk_segments_device_offsets_scratch_bytes(n_segments, far_capacity, k, dtype, index_bytes=0):
+    """``rdst_hip_topk_segments_device_offsets_scratch_bytes``: bytes of scratch :func:`topk_segments_device_offsets_tensor`
+    needs for ``n_segments`` segments of keys of ``dtype``: the plan and, with ``far_capacity`` > 0, behind it the partial
+    sort's scratch for a far segment of ``far_capacity`` keys (0 for no segment, more than 2^30 of them, a ``far_capacity`` of
+    2^32 or more, and widths the entry is not built for)."""
+    _kind, nbytes, _levels = key_info(dtype)
+    return int(_lib.load().rdst_hip_topk_segments_device_offsets_scratch_bytes(int(n_segments), int(far_capacity), int(k), nbytes, int(index_bytes)))
+
+
+def topk_segments_plan_device(offsets, n, k, dtype, index_bytes=0, unbounded_stream=False, scratch=None):
+    """``rdst_hip_debug_topk_segments_plan_device`` (test hook, blocking): the work list the DEVICE plan of
+    :func:`topk_segments_device_offsets_tensor` makes of a device-resident ``offsets`` tensor (int32 / int64) over ``n``
+    elements — ``(items, counts, longest_far, flags)``, the first three as :func:`topk_segments_plan` returns them;
+    ``unbounded_stream``: the classes of the asynchronous mode, whose stream class has no upper length; ``flags``: 1 = offsets
+    decrease somewhere, 2 = the last offset lies past ``n`` (the other three then mean nothing)."""
+    _kind, nbytes, _levels = key_info(dtype)
+    n_segments, obytes = _device_offsets(offsets, offsets, 0)
+    items = (_lib.SegmentItemC * max(1, n_segments))()
+    counts = (ctypes.c_uint64 * 4)()
+    longest = ctypes.c_uint64(0)
+    flags = ctypes.c_uint32(0)
+    scratch, sbytes = _scratch(scratch, segments_device_offsets_scratch_bytes(n_segments), offsets.device)
+    _call(offsets, False, "rdst_hip_debug_topk_segments_plan_device", _ptr(offsets), obytes, n_segments, int(n), int(k), nbytes, int(index_bytes),
+          1 if unbounded_stream else 0, _ptr(scratch), sbytes, items, n_segments, counts, ctypes.byref(longest), ctypes.byref(flags))
+    total = int(sum(counts)) if not flags.value else 0
+    return ([(int(it.start), int(it.len), int(it.seg)) for it in items[:total]], tuple(int(c) for c in counts), int(longest.value),
+            int(flags.value))
+
+
+def topk_segments_device_offsets_tensor(keys, offsets, k, largest=False, index=None, scratch=None, far_capacity=0, check=True, key=None, out=None):
+    """``rdst_hip_topk_segments_device_offsets``: :func:`topk_segments_device_tensor` for a table of borders that lives on the
+    device — a CSR row pointer, a ``cumsum`` of lengths — and never visits the host.  ``offsets``: a contiguous 1-D int32 or
+    int64 tensor on the keys' device with n_segments + 1 entries, read as unsigned and in stream order.  The result, ``index``
+    and ``out`` are :func:`topk_segments_device_tensor`'s.  ``scratch``: optional uint8 tensor of at least
+    :func:`topk_segments_device_offsets_scratch_bytes` bytes, 256-byte aligned (allocated when omitted).
+
+    ``far_capacity=0`` is the fully asynchronous mode: nothing is copied to the host and nothing waited for (``check=False``
+    makes no blocking call at all).  Every segment beyond ``topk_segments_limits(...)[1]`` keys is served by ONE workgroup,
+    whatever its length — correct at any length, slow for very long rows — and ``k`` beyond ``topk_segments_limits(...)[3]``
+    with such a segment, or a table that decreases or ends past the keys, writes nothing and raises from
+    :func:`device_status` (here, with ``check``).  With ``far_capacity`` (the longest segment the call may meet; ``len(keys)``
+    if nothing better is known) the classes are the host entry's; the call waits once for the stream to read the plan's
+    counts, and an invalid table or a segment beyond ``far_capacity`` raises at once."""
+    import torch
+    kind, nbytes, levels, n, per_key = _keys_operand("topk_segments_device_offsets_tensor", keys, key)
+    index_bytes = _index_bytes(index)
+    k, far_capacity = int(k), int(far_capacity)
+    if k < 0 or far_capacity < 0:
+        raise ValueError("k and far_capacity must not be negative")
+    n_segments, obytes = _device_offsets(offsets, keys, n)
+    out_keys, out_index = _topk_rows_out(keys, key, per_key, index, n_segments, k, out)
+    if k == 0 or n_segments == 0:
+        return out_keys, out_index
+    need = int(_lib.load().rdst_hip_topk_segments_device_offsets_scratch_bytes(n_segments, far_capacity, k, nbytes, index_bytes))
+    scratch, sbytes = _scratch(scratch, need, keys.device)
+    _call(keys, check, "rdst_hip_topk_segments_device_offsets", _ptr(keys), n, _ptr(offsets), obytes, n_segments, k, _ptr(out_keys), _ptr(out_index),
+          index_bytes, _ptr(scratch), sbytes, far_capacity, nbytes, kind, levels, _lib.RDST_TOPK_LARGEST if largest else 0)
+    return out_keys, out_index
 
 
 def sort_segments_device_offsets_tensor(keys, offsets, tmp=None, values=None, tmp_values=None, scratch=None, check=True, key=None):

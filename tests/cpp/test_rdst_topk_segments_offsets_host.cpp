@@ -1,0 +1,127 @@
+// Stand-alone check of the host-only half of rdst_hip_topk_segments_device_offsets (built by
+// tests/test_topk_segments_offsets_abi.py with -fsanitize=address,undefined from rdst_topk_segments_offsets.cpp and
+// rdst_segments.cpp): the scratch-size function over edge values — zeros, the sum it documents, monotone in every argument —
+// and the plan's class keys (rdst_segments_layout.h): sorting the keys of a table gives rdst_topk_segments_plan's order.
+#include <stdint.h>
+#include <stdio.h>
+#include <stdlib.h>
+
+#include <algorithm>
+#include <random>
+#include <string>
+#include <vector>
+
+#include "rdst_hip.h"
+#include "../../rdst_amd/csrc/rdst_segments_layout.h"
+
+namespace L = rdst_segments_layout;
+
+static std::string g_error;
+namespace rdst_internal {
+int note_error(int code, const char* what) {  // the library's own lives in rdst_kernels.hip
+    g_error = what;
+    return code;
+}
+}  // namespace rdst_internal
+
+// the library's own lives in rdst_topk.hip; here any pure function that is monotone in len and k will do
+extern "C" uint64_t rdst_hip_topk_scratch_bytes(uint64_t len, uint64_t k, uint32_t elem_bytes, uint32_t index_bytes, uint64_t) {
+    return L::up256(len * elem_bytes) + L::up256(k * (elem_bytes + index_bytes)) + 512;
+}
+
+#define CHECK(cond)                                                         \
+    do {                                                                    \
+        if (!(cond)) {                                                      \
+            printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #cond);        \
+            exit(1);                                                        \
+        }                                                                   \
+    } while (0)
+
+static const uint32_t WIDTHS[9][2] = {{1, 0}, {2, 0}, {4, 0}, {8, 0}, {16, 0}, {4, 4}, {4, 8}, {8, 4}, {8, 8}};
+
+static void check_scratch_bytes() {
+    const auto f = rdst_hip_topk_segments_device_offsets_scratch_bytes;
+    for (uint32_t kb : {0u, 3u, 5u, 32u}) CHECK(f(10, 100, 5, kb, 0) == 0);
+    for (uint32_t kb : {1u, 2u, 16u}) CHECK(f(10, 100, 5, kb, 4) == 0 && f(10, 100, 5, kb, 0) > 0);
+    CHECK(f(10, 100, 5, 4, 3) == 0);
+    CHECK(f(0, 100, 5, 4, 0) == 0 && f((1ull << 30) + 1, 100, 5, 4, 0) == 0 && f(1ull << 30, 0, 5, 4, 0) > 0);
+    CHECK(f(10, 1ull << 32, 5, 4, 0) == 0 && f(10, ~0ull, 5, 4, 0) == 0 && f(10, (1ull << 32) - 1, 5, 4, 0) > 0);
+    const std::vector<uint64_t> segs{1, 2, 63, 64, 65, 1000, 1000000, 1ull << 30};
+    const std::vector<uint64_t> fars{0, 1, 2, 4096, 4097, 1ull << 17, (1ull << 17) + 1, 1ull << 24, (1ull << 32) - 1};
+    const std::vector<uint64_t> ks{0, 1, 64, 16384, 16385, 1ull << 21, 1ull << 40, ~0ull};
+    for (const auto& w : WIDTHS) {
+        for (size_t i = 0; i < segs.size(); ++i) {
+            const uint64_t plan = rdst_hip_sort_segments_device_offsets_scratch_bytes(segs[i]);
+            CHECK(plan == L::plan_layout(segs[i]).total && plan % 256 == 0 && plan >= 256 + 32 * segs[i]);
+            for (size_t j = 0; j < fars.size(); ++j)
+                for (size_t m = 0; m < ks.size(); ++m) {
+                    const uint64_t got = f(segs[i], fars[j], ks[m], w[0], w[1]);
+                    CHECK(got == f(segs[i], fars[j], ks[m], w[0], w[1]));  // pure
+                    CHECK(got == plan + (fars[j] ? rdst_hip_topk_scratch_bytes(fars[j], std::min(ks[m], fars[j]), w[0], w[1], 0) : 0));
+                    if (i) CHECK(f(segs[i - 1], fars[j], ks[m], w[0], w[1]) <= got);  // monotone in all three
+                    if (j) CHECK(f(segs[i], fars[j - 1], ks[m], w[0], w[1]) <= got);
+                    if (m) CHECK(f(segs[i], fars[j], ks[m - 1], w[0], w[1]) <= got);
+                }
+        }
+    }
+}
+
+// (key, segment) pairs sorted by the key, stable — what the device plan's pair sort does — against rdst_topk_segments_plan
+static void check_class_keys(const std::vector<uint64_t>& off, uint64_t k, uint32_t kb, uint32_t ib) {
+    uint32_t lim[4];
+    CHECK(rdst_hip_topk_segments_limits(kb, ib, lim) == RDST_OK);
+    const uint64_t nseg = off.size() - 1;
+    const uint32_t stream_limit = k > lim[3] ? lim[1] : lim[2];
+    std::vector<std::pair<uint32_t, uint32_t>> pairs;
+    for (uint64_t s = 0; s < nseg; ++s) pairs.push_back({L::topk_class_key(off[s + 1] - off[s], lim[0], lim[1], stream_limit), (uint32_t)s});
+    std::stable_sort(pairs.begin(), pairs.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+    std::vector<rdst_segment_item> items(nseg);
+    uint64_t counts[4], longest = 0;
+    CHECK(rdst_topk_segments_plan(off.data(), nseg, off.back(), k, kb, ib, items.data(), nseg, counts, &longest) == RDST_OK);
+    const uint64_t total = counts[0] + counts[1] + counts[2] + counts[3];
+    for (uint64_t i = 0; i < nseg; ++i) {
+        if (i < total) CHECK(pairs[i].first != L::TOPK_KEY_NONE && pairs[i].second == items[i].seg);
+        else CHECK(pairs[i].first == L::TOPK_KEY_NONE);
+    }
+    for (uint64_t i = 0; i < total; ++i) {
+        const uint32_t c = L::topk_class(items[i].len, lim[0], lim[1], stream_limit);
+        CHECK(c == (i < counts[0] ? 0u : (i < counts[0] + counts[1] ? 1u : (i < counts[0] + counts[1] + counts[2] ? 2u : 3u))));
+    }
+}
+
+int main() {
+    check_scratch_bytes();
+    // the encoding at its ends: ascending class ranges, descending length inside the block and the stream class
+    for (const auto& w : WIDTHS) {
+        uint32_t lim[4];
+        CHECK(rdst_hip_topk_segments_limits(w[0], w[1], lim) == RDST_OK);
+        const uint32_t wm = lim[0], bm = lim[1], all = 0xFFFFFFFFu;
+        CHECK(L::topk_class_key(0, wm, bm, all) == L::TOPK_KEY_NONE && L::topk_class_key(1, wm, bm, all) == 0 && L::topk_class_key(wm, wm, bm, all) == 0);
+        CHECK(L::topk_class_key(bm, wm, bm, all) == 1 && L::topk_class_key(wm + 1, wm, bm, all) == bm - wm);
+        CHECK(L::topk_class_key(0xFFFFFFFFull, wm, bm, all) == bm - 1 && L::topk_class_key(0xFFFFFFFEull, wm, bm, all) == bm);
+        CHECK(L::topk_class_key((uint64_t)bm + 1, wm, bm, all) == L::TOPK_KEY_STREAM_LAST && L::topk_class_key((uint64_t)bm + 2, wm, bm, all) == L::TOPK_KEY_STREAM_LAST - 1);
+        CHECK(L::topk_class_key((uint64_t)bm + 1, wm, bm, bm) == L::TOPK_KEY_FAR && L::topk_class_key(1ull << 40, wm, bm, all) == L::TOPK_KEY_FAR);
+        CHECK(L::topk_class_key(lim[2], wm, bm, lim[2]) < L::TOPK_KEY_FAR && L::topk_class_key((uint64_t)lim[2] + 1, wm, bm, lim[2]) == L::TOPK_KEY_FAR);
+    }
+    // tables: hand-made borders and seeded random ones, k on both sides of k_stream_max, stream borders on both sides of block_max
+    std::mt19937_64 rng(7);
+    for (const auto& w : WIDTHS) {
+        uint32_t lim[4];
+        CHECK(rdst_hip_topk_segments_limits(w[0], w[1], lim) == RDST_OK);
+        const uint64_t wm = lim[0], bm = lim[1];
+        for (uint32_t border : {0u, (uint32_t)bm - 1, (uint32_t)(3 * bm), 0xFFFFFFFFu}) {
+            CHECK(rdst_hip_set_topk_segments_stream_max(border) == RDST_OK);
+            CHECK(rdst_hip_topk_segments_limits(w[0], w[1], lim) == RDST_OK);
+            std::vector<uint64_t> lengths{0, 1, 2, wm, wm + 1, bm, bm + 1, bm + 1, 3 * bm, 3 * bm + 1, (uint64_t)lim[2], std::min<uint64_t>((uint64_t)lim[2] + 1, 0xFFFFFFFFull),
+                                          wm, bm, 0, bm - 1, bm - 1};  // (an item's len saturates at 2^32 - 1)
+            for (int i = 0; i < 40; ++i) lengths.push_back(rng() % (i % 4 == 0 ? 4 * bm : 2 * wm));
+            std::shuffle(lengths.begin(), lengths.end(), rng);
+            std::vector<uint64_t> off{3};
+            for (uint64_t n : lengths) off.push_back(off.back() + n);
+            for (uint64_t k : {(uint64_t)1, bm, bm + 1}) check_class_keys(off, k, w[0], w[1]);
+        }
+        CHECK(rdst_hip_set_topk_segments_stream_max(0) == RDST_OK);
+    }
+    printf("ok\n");
+    return 0;
+}

@@ -2,6 +2,7 @@
 same result before it, and — for information only — torch.topk(dim=1).  One JSON line per case and a summary object.
 
     python tools/topk_segments_bench.py [--reps 5] [--only sweep|table] [--scale 1.0] [--out profiles/topk_segments_bench.json]
+    python tools/topk_segments_bench.py --device-offsets [--reps 7] [--scale 1.0] [--out profiles/topk_segments_offsets_bench.json]
 
 sweep   one segment per call, lengths 2^17 .. 2^23, u32 and u64 keys, k = 64: the stream class forced against the far class
         forced, both through rdst_hip_set_topk_segments_stream_max.  The crossing is where the library's default belongs.
@@ -16,6 +17,16 @@ table   rows x row length 65 536 x 64, 4 096 x 4 096, 1 024 x 16 384, 64 x 131 0
         One more run under rdst_hip_set_profiling gives the time of each class's launch, and for the stream class the bytes
         it streams per second and per workgroup (every read of every level counted, from the select restated on the host
         for a sample of rows).
+
+--device-offsets   the table's shapes and one row of 2^24 keys, with the borders in DEVICE memory
+        (rdst_hip_topk_segments_device_offsets); k = 1, 64, 1 024; u32 and u64 keys only, f32 with an int32 index:
+          async      far_capacity = 0: the plan and three counted launches, nothing comes to the host;
+          wait       far_capacity = len: the plan, one wait for the stream, the host entry's classes;
+          today      what a caller with device offsets pays without the entry: the table copied to the host, a synchronise,
+                     rdst_hip_topk_segments_device;
+          host       rdst_hip_topk_segments_device with a table that is on the host already: the plan's bare cost is what
+                     async and wait add to it.
+        All four give the same bits (checked).
 
 The candidates run in one process, alternating, after one untimed warm-up round; the time is HIP events on the stream around
 the calls, median over --reps with all of them kept.  Every result is compared with the sort baseline's."""
@@ -232,6 +243,59 @@ def table(torch, rdst_amd, args):
     return results
 
 
+def device_offsets(torch, rdst_amd, args):
+    results = []
+    tables = list(_tables(args.scale)) + [("1x2^24", np.array([0, 1 << 24], dtype=np.uint64), 1 << 24)]
+    for shape, off, _cols in tables:
+        n, n_seg = int(off[-1]), len(off) - 1
+        longest = int((off[1:] - off[:-1]).max())
+        toff = torch.from_numpy(off.astype(np.int64)).cuda()
+        for kind, indexed in (("u32", False), ("u64", False), ("f32", True)):
+            keys = _keys(torch, kind, n, n_seg % 11 + len(kind))
+            ib = 4 if indexed else 0
+            index = torch.int32 if indexed else None
+            _wm, bm, sm, _ksm = rdst_amd.topk_segments_limits(keys.dtype, ib)
+            for k in (1, 64, 1024):
+                outs = {name: (torch.zeros((n_seg, k), dtype=keys.dtype, device="cuda"), torch.zeros((n_seg, k), dtype=torch.int32, device="cuda") if indexed else None)
+                        for name in ("async", "wait", "today", "host")}
+                s_async = torch.empty(rdst_amd.topk_segments_device_offsets_scratch_bytes(n_seg, 0, k, keys.dtype, ib), dtype=torch.uint8, device="cuda")
+                s_wait = torch.empty(rdst_amd.topk_segments_device_offsets_scratch_bytes(n_seg, n, k, keys.dtype, ib), dtype=torch.uint8, device="cuda")
+                s_host = torch.empty(rdst_amd.topk_segments_scratch_bytes(n_seg, longest, k, keys.dtype, ib), dtype=torch.uint8, device="cuda")
+
+                def run_async():
+                    rdst_amd.topk_segments_device_offsets_tensor(keys, toff, k, index=index, scratch=s_async, check=False, out=outs["async"])
+
+                def run_wait():
+                    rdst_amd.topk_segments_device_offsets_tensor(keys, toff, k, index=index, scratch=s_wait, far_capacity=n, check=False, out=outs["wait"])
+
+                def run_today():
+                    table = toff.cpu().numpy().astype(np.uint64)            # the copy waits for the stream
+                    rdst_amd.topk_segments_device_tensor(keys, table, k, index=index, scratch=s_host, check=False, out=outs["today"])
+
+                def run_host():
+                    rdst_amd.topk_segments_device_tensor(keys, off, k, index=index, scratch=s_host, check=False, out=outs["host"])
+
+                ms = _time_alternating(torch, {"async": run_async, "wait": run_wait, "today": run_today, "host": run_host}, args.reps)
+                rdst_amd.device_status()
+                for name in ("async", "wait", "today"):
+                    assert torch.equal(outs[name][0].view(torch.uint8), outs["host"][0].view(torch.uint8)), f"{name} and the host entry disagree"
+                    assert not indexed or torch.equal(outs[name][1], outs["host"][1]), f"{name}: the positions disagree"
+                med = {name: v[len(v) // 2] for name, v in ms.items()}
+                rec = {"part": "device_offsets", "shape": shape, "segments": n_seg, "n": n, "keys": kind, "index": ib, "k": k,
+                       "class_counts_async": list(rdst_amd.topk_segments_plan_device(toff, n, k, keys.dtype, ib, unbounded_stream=True)[1]),
+                       "class_counts_wait": list(rdst_amd.topk_segments_plan(off, n, k, keys.dtype, ib)[1]),
+                       "async": _stats(ms["async"]), "wait": _stats(ms["wait"]), "today": _stats(ms["today"]), "host": _stats(ms["host"]),
+                       "today_over_async": round(med["today"] / med["async"], 2), "today_over_wait": round(med["today"] / med["wait"], 2),
+                       "async_minus_host_ms": round(med["async"] - med["host"], 4), "wait_minus_host_ms": round(med["wait"] - med["host"], 4),
+                       "results_equal": True}
+                print(json.dumps(rec), flush=True)
+                results.append(rec)
+                del outs, s_async, s_wait, s_host
+            del keys
+            torch.cuda.empty_cache()
+    return results
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
@@ -240,6 +304,7 @@ def main():
     ap.add_argument("--loop-rows", type=int, default=64)
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-torch", action="store_true", help="leave the torch.topk column out")
+    ap.add_argument("--device-offsets", action="store_true", help="the entry with the borders in device memory against copy + synchronise + host entry")
     args = ap.parse_args()
     import torch
     import rdst_amd
@@ -247,6 +312,17 @@ def main():
     args.cus = torch.cuda.get_device_properties(0).multi_processor_count
     summary = {"tool": "tools/topk_segments_bench.py", "device": torch.cuda.get_device_name(0), "reps": args.reps, "compute_units": args.cus,
                "limits_u32": rdst_amd.topk_segments_limits("uint32"), "limits_u64": rdst_amd.topk_segments_limits("uint64")}
+    if args.device_offsets:
+        summary["device_offsets"] = device_offsets(torch, rdst_amd, args)
+        for name in ("async", "wait"):
+            summary[f"{name}_slower_than_today"] = [[r["shape"], r["keys"], r["index"], r["k"], r[f"today_over_{name}"]] for r in summary["device_offsets"]
+                                                    if r[f"today_over_{name}"] < 1.0]
+        print(json.dumps({key: v for key, v in summary.items() if key != "device_offsets"}))
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                json.dump(summary, f, indent=1)
+        return
     if args.out and os.path.exists(args.out):                              # the two parts may be measured in two runs
         with open(args.out) as f:
             old = json.load(f)
