@@ -324,6 +324,36 @@ void topk_device(const T* dev_keys, std::size_t len, std::size_t k, T* dev_out_k
                                        largest ? RDST_TOPK_LARGEST : 0u, stream));
 }
 
+// Order statistics of one DEVICE-resident slice (rdst_hip_select_device): dev_out_keys[i] receives the key that
+// radix_sort_unstable would leave at position ranks[i] — `largest`: at len - 1 - ranks[i] —; dev_keys is only read.  ranks: a
+// HOST array, any order, repeats allowed.  The second form also writes the input position of that element of a stable
+// argsort to dev_out_index[i] (Idx: std::uint32_t or std::uint64_t; 4- and 8-byte keys).  dev_scratch: 256-byte aligned, at
+// least select_scratch_bytes<T>(len, n_ranks) / select_scratch_bytes<T, Idx>(len, n_ranks) bytes, never len-sized.
+// cand_capacity: 0 = the library's default; any value gives the same result.  Nothing is copied to the host and nothing
+// waited for.
+template <typename T>
+std::size_t select_scratch_bytes(std::size_t len, std::size_t n_ranks, std::size_t cand_capacity = 0) {
+    return rdst_hip_select_scratch_bytes(len, n_ranks, sizeof(T), 0, cand_capacity);
+}
+template <typename T, typename Idx>
+std::size_t select_scratch_bytes(std::size_t len, std::size_t n_ranks, std::size_t cand_capacity = 0) {
+    return rdst_hip_select_scratch_bytes(len, n_ranks, sizeof(T), sizeof(Idx), cand_capacity);
+}
+template <typename T>
+void select_device(const T* dev_keys, std::size_t len, const std::uint64_t* ranks, std::size_t n_ranks, T* dev_out_keys, void* dev_scratch,
+                   std::size_t scratch_bytes, bool largest = false, std::size_t cand_capacity = 0, void* stream = nullptr) {
+    detail::check(rdst_hip_select_device(dev_keys, len, ranks, n_ranks, dev_out_keys, nullptr, 0, dev_scratch, scratch_bytes, cand_capacity, sizeof(T),
+                                         RadixKey<T>::kind, static_cast<std::uint32_t>(RadixKey<T>::LEVELS), largest ? RDST_TOPK_LARGEST : 0u, stream));
+}
+template <typename T, typename Idx>
+void select_device(const T* dev_keys, std::size_t len, const std::uint64_t* ranks, std::size_t n_ranks, T* dev_out_keys, Idx* dev_out_index,
+                   void* dev_scratch, std::size_t scratch_bytes, bool largest = false, std::size_t cand_capacity = 0, void* stream = nullptr) {
+    static_assert(std::is_unsigned<Idx>::value && (sizeof(Idx) == 4 || sizeof(Idx) == 8), "positions are 4- or 8-byte unsigned integers");
+    detail::check(rdst_hip_select_device(dev_keys, len, ranks, n_ranks, dev_out_keys, dev_out_index, sizeof(Idx), dev_scratch, scratch_bytes,
+                                         cand_capacity, sizeof(T), RadixKey<T>::kind, static_cast<std::uint32_t>(RadixKey<T>::LEVELS),
+                                         largest ? RDST_TOPK_LARGEST : 0u, stream));
+}
+
 // Partial sort of every segment [offsets[s], offsets[s + 1]) of one DEVICE-resident slice (rdst_hip_topk_segments_device):
 // row s of the outputs, dev_out_keys + s * k (and dev_out_index + s * k), receives in its first min(k, n_s) slots what
 // topk_device gives for that segment, positions counted inside the segment; the slots behind are not written.  offsets: a

@@ -101,8 +101,10 @@ typedef enum {
     RDST_STAGE_SAMPLE = 12,  /* the 8 192-key sample (and, if it flags the keys, K1h + the route decision) before the MSD passes */
     RDST_STAGE_SEGMENTS = 13, /* segmented sort: the item table's copy (host offsets) and the batched wave-class and block-class launches */
     RDST_STAGE_SEGMENTS_TILED = 14, /* segmented sort, nowait entries: the tiled route's launches for the segments beyond block_max */
-    RDST_STAGE_TOPK = 15     /* partial sort: one select level (counting read + bucket pick; its number in bits 8..15), or with
+    RDST_STAGE_TOPK = 15,    /* partial sort: one select level (counting read + bucket pick; its number in bits 8..15), or with
                                 0xFF there the collection pass */
+    RDST_STAGE_SELECT = 16   /* order statistics: one level of one round (counting read + pick; its number in bits 8..15), or with
+                                0xFF there the round's collection pass */
 } rdst_stage;
 
 /* Device routes (rdst_hip_last_route). */
@@ -260,6 +262,66 @@ int rdst_hip_topk_limits(uint32_t elem_bytes, uint32_t index_bytes, uint32_t out
  * out = { levels the device used, keys strictly before the threshold prefix, candidates collected, 1 if the keys-only fill
  * (digits exhausted with more than cand_capacity keys tied) or a position digit was reached }. */
 int rdst_hip_debug_topk_state(const void* dev_scratch, void* stream, uint64_t out[4]);
+
+/* ---- order statistics: the keys at given ranks, unsorted -----------------------------------------
+ * What `select_nth_unstable`, numpy.partition or torch.kthvalue give — a median, deciles, a p99, a cut-off for pruning — for
+ * several ranks at once, without sorting the array, copying it or handing over a tmp of its size.  Call M the mapped key of
+ * the sort; with RDST_TOPK_LARGEST in `flags` (the partial sort's flag) M is its bitwise complement, exactly as there.
+ *   - ranks: a HOST array of n_ranks ranks, each below len, in any order, repeats allowed.  dev_out_keys[i] is, bit for bit,
+ *     the element rdst_hip_sort_device would leave at position ranks[i]; with the flag the element at len - 1 - ranks[i].
+ *     Each result goes to its own slot i.  -0.0 / +0.0 and NaN payloads are distinct keys, as in the sort.
+ *   - dev_out_index: NULL for keys only.  Otherwise (4- and 8-byte keys, index_bytes 4 or 8) slot i receives the input
+ *     position of element ranks[i] of a STABLE argsort by M: equal keys count in ascending position.  With a NULL
+ *     dev_out_index, index_bytes is not looked at.  Deterministic, bit for bit.
+ *   - Keys only: every width and kind of rdst_hip_topk_device (1, 2, 4, 8, 16 bytes; unsigned, signed, f32 / f64).
+ *     RDST_KEY_BYTES_BE: RDST_ERR_UNSUPPORTED.
+ *   - The input is never written.  Of the outputs only the slots [0, n_ranks) are written, of the scratch only
+ *     [0, rdst_hip_select_scratch_bytes(len, n_ranks, elem_bytes, index_bytes, cand_capacity)).  The scratch needs no
+ *     clearing and is reusable in stream order.  It is never len-sized: a header, a group table, counters and two candidate
+ *     arrays of min(cand_capacity or the default, len) elements.
+ *   - ASYNCHRONOUS on `stream` for every input: no copy to or from the host, no stream or event wait, no staging buffer (the
+ *     one exception every entry shares: a library workspace that has to grow).  The ranks travel as kernel arguments: `ranks`
+ *     may be reused as soon as the call returns.  Every launch is enqueued unconditionally and sized from len, n_ranks and
+ *     cand_capacity on the host; there is no data-dependent failure and no error bit: all keys equal, a sorted input, one
+ *     heavy bucket are answered exactly.
+ *   - The mechanism is a multi-rank radix select.  Up to max_ranks ranks (rdst_hip_select_limits) are followed
+ *     IN THE SAME READS of the input: level 0 counts the first digit of every key, a later level the next digit of every key
+ *     that lies on the prefix of some rank (a "group": prefix, count before it, count on it), until the groups together hold
+ *     at most cand_capacity elements; then one more read collects the elements on the groups' prefixes, one sort orders
+ *     them, and each rank picks its element.  What lies before a prefix is only counted, never kept.  When the digits are
+ *     exhausted first — with an index the key's digits and then the position's — every answer is its group's prefix itself
+ *     and nothing is collected.  A longer list is served in rounds of max_ranks ranks, taken in ascending rank order so that
+ *     neighbours share prefixes; every round has its own reads, all rounds use the same scratch.
+ *   - cand_capacity: 0 = the library's default; any value >= 1 is legal and gives the same result.
+ *   - n_ranks has no upper limit, but the host orders the ranks before the first launch: O(n_ranks log n_ranks) time and 16
+ *     bytes of host memory per rank (std::stable_sort), and one round of reads per max_ranks ranks.  If that memory cannot be
+ *     had, the call returns RDST_ERR_ARG after the argument checks and before any device work; nothing is thrown.
+ *   - Arguments, checked in this order before any device work: (1) the key arguments as rdst_hip_sort_device checks them (its
+ *     codes and messages); (2) BYTES_BE -> RDST_ERR_UNSUPPORTED; (3) len >= 2^32 -> RDST_ERR_UNSUPPORTED; (4) unknown flag
+ *     bits -> RDST_ERR_ARG; (5) n_ranks == 0 -> RDST_OK, nothing else is looked at; (6) NULL ranks -> RDST_ERR_ARG; (7) any
+ *     ranks[i] >= len -> RDST_ERR_ARG, the message names the first such i; (8) NULL dev_out_keys -> RDST_ERR_ARG, misaligned
+ *     to the element -> RDST_ERR_ALIGN; (9) with an index: index_bytes not 4 or 8 -> RDST_ERR_ARG, key width not 4 or 8 ->
+ *     RDST_ERR_UNSUPPORTED, misaligned index pointer -> RDST_ERR_ALIGN; (10) NULL scratch -> RDST_ERR_ARG; (11) scratch not
+ *     256-byte aligned -> RDST_ERR_ALIGN; (12) scratch_bytes below rdst_hip_select_scratch_bytes(...) -> RDST_ERR_ARG. */
+int rdst_hip_select_device(const void* dev_keys, uint64_t len,
+                           const uint64_t* ranks, uint64_t n_ranks,
+                           void* dev_out_keys, void* dev_out_index, uint32_t index_bytes,
+                           void* dev_scratch, uint64_t scratch_bytes, uint64_t cand_capacity,
+                           uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels,
+                           uint32_t flags, void* stream);
+/* The scratch of the call above, sized for one round whatever n_ranks is.  Pure, monotone in cand_capacity: a 256-byte
+ * header, the group table (2 304 bytes), 16 384 counters and two arrays of min(cand_capacity or the default, len) elements,
+ * each rounded up to 256 bytes; an element is a key, or with an index a (key, position) composite of twice the key's width.
+ * 0 for unsupported widths. */
+uint64_t rdst_hip_select_scratch_bytes(uint64_t len, uint64_t n_ranks, uint32_t elem_bytes,
+                                       uint32_t index_bytes, uint64_t cand_capacity);
+/* out = { max_ranks, bits of the first digit, bits of the later digits, the default cand_capacity (sized for max_ranks ranks),
+ * the most levels one round can take } for this key width (index_bytes 0 = keys only).  Pure.  Unsupported widths:
+ * rdst_hip_topk_limits' codes. */
+int rdst_hip_select_limits(uint32_t elem_bytes, uint32_t index_bytes, uint32_t out[5]);
+/* Test hook, BLOCKING: what the most recent round of rdst_hip_select_device on this scratch decided.  out = { levels the
+ * round used, groups at the end, candidates collected, 1 if the digits were exhausted }. */
+int rdst_hip_debug_select_state(const void* dev_scratch, void* stream, uint64_t out[4]);
 
 /* ---- many independent slices in one call ---------------------------------------------------------
  * The reference sorts the 256 buckets of a chunk as slices of their own, in parallel (src/sorter.rs:131-138), and a

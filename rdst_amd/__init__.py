@@ -45,6 +45,11 @@ from .radix_sort import (  # noqa: F401
     topk_scratch_bytes,
     topk_limits,
     topk_state,
+    select_device_tensor,
+    select_scratch_bytes,
+    select_limits,
+    select_state,
+    quantile_ranks,
     topk_segments_device_tensor,
     topk_segments_device_offsets_tensor,
     topk_segments_device_offsets_scratch_bytes,
@@ -74,6 +79,7 @@ __all__ = [
     "KeyField", "key_fields_of", "sort_records_device_tensor", "sort_bytes_device_nowait_tensor", "sort_records_device_nowait_tensor",
     "sort_device_devlen_tensor", "sort_pairs_device_devlen_tensor",
     "topk_device_tensor", "topk_scratch_bytes", "topk_limits", "topk_state",
+    "select_device_tensor", "select_scratch_bytes", "select_limits", "select_state", "quantile_ranks",
     "topk_segments_device_tensor", "topk_rows_tensor", "topk_segments_scratch_bytes", "topk_segments_limits", "topk_segments_plan",
     "set_topk_segments_stream_max", "topk_segments_device_offsets_tensor", "topk_segments_device_offsets_scratch_bytes", "topk_segments_plan_device",
 ]

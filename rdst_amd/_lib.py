@@ -20,6 +20,7 @@ RDST_KEY_FIELDS_MAX = 16   # fields in one key description
 RDST_STAGE_SEGMENTS = 13   # rdst_stage: the batched launches of the segmented sort
 RDST_STAGE_SEGMENTS_TILED = 14   # rdst_stage: the tiled route of the nowait entries (segments beyond block_max)
 RDST_STAGE_TOPK = 15       # rdst_stage: one select level of the partial sort (level in bits 8..15; 0xFF: the collection pass)
+RDST_STAGE_SELECT = 16     # rdst_stage: one level of one round of the order statistics (level in bits 8..15; 0xFF: the collection pass)
 RDST_TOPK_LARGEST = 1      # rdst_hip_topk_device flags: the k largest, in descending order
 
 
@@ -71,6 +72,10 @@ def _signatures():
         "rdst_hip_topk_scratch_bytes": (u64, [u64, u64, u32, u32, u64]),
         "rdst_hip_topk_limits": (ci, [u32, u32, u32p]),
         "rdst_hip_debug_topk_state": (ci, [vp, vp, u64p]),
+        "rdst_hip_select_device": (ci, [vp, u64, u64p, u64, vp, vp, u32, vp, u64, u64, u32, ci, u32, u32, vp]),
+        "rdst_hip_select_scratch_bytes": (u64, [u64, u64, u32, u32, u64]),
+        "rdst_hip_select_limits": (ci, [u32, u32, u32p]),
+        "rdst_hip_debug_select_state": (ci, [vp, vp, u64p]),
         "rdst_hip_topk_segments_device": (ci, [vp, u64, u64p, u64, u64, vp, vp, u32, vp, u64, u32, ci, u32, u32, vp]),
         "rdst_hip_topk_segments_scratch_bytes": (u64, [u64, u64, u64, u32, u32]),
         "rdst_hip_topk_segments_limits": (ci, [u32, u32, u32p]),

@@ -8,12 +8,14 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SOURCES = [os.path.join(HERE, "csrc", "rdst_kernels.hip"), os.path.join(HERE, "csrc", "rdst_bytes.hip"),
            os.path.join(HERE, "csrc", "rdst_segments.hip"), os.path.join(HERE, "csrc", "rdst_topk.hip"),
+           os.path.join(HERE, "csrc", "rdst_select.hip"),
            os.path.join(HERE, "csrc", "rdst_topk_segments.hip"), os.path.join(HERE, "csrc", "rdst_topk_segments_offsets.hip"),
            os.path.join(HERE, "csrc", "rdst_topk_segments_offsets.cpp"),
            os.path.join(HERE, "csrc", "rdst_tuner.cpp"),
            os.path.join(HERE, "csrc", "rdst_regions.cpp"), os.path.join(HERE, "csrc", "rdst_segments.cpp")]
 HEADERS = [os.path.join(ROOT, "include", "rdst_hip.h"), os.path.join(HERE, "csrc", "rdst_internal.h"),
-           os.path.join(HERE, "csrc", "rdst_device.h"), os.path.join(HERE, "csrc", "rdst_segments_layout.h")]
+           os.path.join(HERE, "csrc", "rdst_device.h"), os.path.join(HERE, "csrc", "rdst_segments_layout.h"),
+           os.path.join(HERE, "csrc", "rdst_stream.h")]
 OUT = os.path.join(HERE, "librdst_hip.so")
 
 

@@ -35,6 +35,7 @@
 #include "rdst_hip.h"
 #include "rdst_internal.h"
 #include "rdst_device.h"
+#include "rdst_stream.h"
 
 namespace {
 
@@ -73,14 +74,6 @@ constexpr uint64_t align256(uint64_t x) { return (x + 255) / 256 * 256; }
 bool key_width_ok(uint32_t b) { return b == 1 || b == 2 || b == 4 || b == 8 || b == 16; }
 uint32_t digit_bits_for(uint32_t elem_bytes) { return elem_bytes == 1 ? DIGIT_BITS_BYTE : DIGIT_BITS_WIDE; }
 uint32_t levels_over(uint32_t bits, uint32_t digit) { return (bits + digit - 1) / digit; }
-// level l of a field of `bits` bits: its digit is the bits [shift, shift + nbits)
-void level_shape(uint32_t bits, uint32_t digit, uint32_t l, int* shift, uint32_t* nbits) {
-    const uint32_t hi = bits - l * digit;
-    const uint32_t lo = hi > digit ? hi - digit : 0;
-    *shift = (int)lo;
-    *nbits = hi - lo;
-}
-
 struct TopkLayout {
     uint64_t counters, sel, sel_tmp, cand, cand_tmp, total;
     uint64_t cap;  // the capacity the candidate buffers are sized for
@@ -101,84 +94,6 @@ TopkLayout topk_layout(uint64_t len, uint64_t k, uint32_t elem_bytes, uint32_t i
 
 // ---- device side -------------------------------------------------------------------------------------------------------------
 
-template <typename K>
-__device__ __forceinline__ K header_key(const uint64_t w[2]) {
-    if constexpr (sizeof(K) == 16) return (K)w[0] | ((K)w[1] << 64);
-    else return (K)w[0];
-}
-
-template <typename K>
-struct alignas(16) KeyVec {
-    static constexpr int N = 16 / (int)sizeof(K);
-    K e[N];
-};
-
-template <typename K>
-__device__ __forceinline__ KeyVec<K> load_vec(const K* p) {  // p is 16-byte aligned
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    const u32x4 raw = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p));
-    KeyVec<K> v;
-    __builtin_memcpy(&v, &raw, 16);
-    return v;
-}
-
-// How a kernel that streams the input cuts it: a scalar head up to the first 16-byte boundary, whole 16-byte vectors, a scalar
-// tail.  Exact for any len and any element-aligned pointer.
-template <typename K>
-struct StreamCut {
-    uint32_t head, nvec, tail_start, len;
-    __device__ StreamCut(const K* keys, uint32_t n) {
-        constexpr uint32_t VEC = KeyVec<K>::N;
-        const uint32_t mis = (uint32_t)(reinterpret_cast<uintptr_t>(keys) & 15u);
-        uint32_t h = mis ? (16u - mis) / (uint32_t)sizeof(K) : 0u;
-        head = h < n ? h : n;
-        nvec = (n - head) / VEC;
-        tail_start = head + nvec * VEC;
-        len = n;
-    }
-};
-
-// Calls visit(raw_key, position, valid) for every element, with ALL 64 lanes of a wave in every call (visit may ballot):
-// lanes without an element pass valid == false.
-template <typename K, typename F>
-__device__ __forceinline__ void stream_keys(const K* __restrict__ keys, uint32_t len, F&& visit) {
-    constexpr uint32_t VEC = KeyVec<K>::N;
-    const StreamCut<K> cut(keys, len);
-    const uint32_t tid = threadIdx.x, lane = tid & 63u;
-    const uint64_t stride = (uint64_t)gridDim.x * blockDim.x;
-    const K* body = keys + cut.head;
-    // wave-uniform loop bound: a wave goes on while its first lane has a vector
-    for (uint64_t v = (uint64_t)blockIdx.x * blockDim.x + tid; v - lane < cut.nvec; v += stride * HIST_UNROLL) {
-        KeyVec<K> vec[HIST_UNROLL];
-        bool ok[HIST_UNROLL];
-#pragma unroll
-        for (int u = 0; u < HIST_UNROLL; ++u) {
-            const uint64_t vi = v + (uint64_t)u * stride;
-            ok[u] = vi < cut.nvec;
-            if (ok[u]) vec[u] = load_vec<K>(body + vi * VEC);
-            else
-                for (uint32_t j = 0; j < VEC; ++j) vec[u].e[j] = 0;
-        }
-#pragma unroll
-        for (int u = 0; u < HIST_UNROLL; ++u) {
-            const uint64_t vi = v + (uint64_t)u * stride;
-            if (__builtin_amdgcn_ballot_w64(ok[u]) == 0) continue;  // wave-uniform
-#pragma unroll
-            for (uint32_t j = 0; j < VEC; ++j) visit(vec[u].e[j], (uint32_t)(cut.head + vi * VEC + j), ok[u]);
-        }
-    }
-    // head and tail: fewer than 2 * 16 / sizeof(K) <= 32 elements, one wave
-    if (blockIdx.x == 0 && tid < 64) {
-        const uint32_t tail_n = cut.len - cut.tail_start;
-        if (cut.head + tail_n != 0) {
-            const bool valid = lane < cut.head + tail_n;
-            const uint32_t idx = lane < cut.head ? lane : cut.tail_start + (lane - cut.head);
-            const K raw = valid ? keys[idx] : (K)0;
-            visit(raw, idx, valid);
-        }
-    }
-}
-
 __global__ __launch_bounds__(64) void topk_init_kernel(TopkHeader* __restrict__ hdr, uint32_t len, uint32_t cap) {
     if (threadIdx.x != 0) return;  // (the header and the counters were cleared just before)
     hdr->m = len;
@@ -196,19 +111,13 @@ __global__ __launch_bounds__(HIST_THREADS) void topk_hist_kernel(const K* __rest
     const uint32_t ppref = hdr->pos_pref, ppmask = hdr->pos_mask;
     const uint32_t lane = threadIdx.x & 63u;
     __syncthreads();
-    stream_keys<K>(keys, len, [&](K raw, uint32_t idx, bool valid) {
+    stream_keys<K, HIST_UNROLL>(keys, len, [&](K raw, uint32_t idx, bool valid) {
         const K m = map_key<K>(raw, neg, pos);
         const bool hit = valid && (K)(m & pmask) == pref && (idx & ppmask) == ppref;
         const uint64_t bal = __builtin_amdgcn_ballot_w64(hit);
         if (bal == 0) return;  // wave-uniform
         const uint32_t d = (pos_level ? idx >> shift : (uint32_t)(m >> shift)) & dmask;
-        const uint32_t first = (uint32_t)__builtin_ctzll(bal);
-        const uint32_t d0 = (uint32_t)__builtin_amdgcn_readlane((int)d, (int)first);
-        if (__builtin_amdgcn_ballot_w64(hit && d == d0) == bal) {  // every hit of the wave on one counter: one add
-            if (lane == first) atomicAdd(&lds[d0], (uint32_t)__builtin_popcountll(bal));
-        } else if (hit) {
-            atomicAdd(&lds[d], 1u);
-        }
+        wave_count(lds, d, hit, bal, lane);
     });
     __syncthreads();
     for (uint32_t i = threadIdx.x; i < COUNTERS; i += HIST_THREADS) {
@@ -253,34 +162,6 @@ __global__ __launch_bounds__(PICK_THREADS) void topk_pick_kernel(TopkHeader* __r
     if (last || m <= cap) hdr->ready = 1;
 }
 
-// The element that is collected and sorted: the mapped key, or with an index the composite (mapped key, position).
-template <typename K, typename C>
-__device__ __forceinline__ C compose(K m, uint32_t idx) {
-    if constexpr (sizeof(C) == sizeof(K)) return (C)m;
-    else return (C)((C)m << (8 * sizeof(K))) | (C)idx;
-}
-
-// orders this wave's LDS accesses: nothing moves across it, in the compiler or in the wave
-__device__ __forceinline__ void wave_sync() {
-    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-}
-
-// One wave's stage of one class, handed to the output: ONE atomic on the class's cursor claims the range.  `count` is
-// wave-uniform.  Claims on a single address serialise (one per element that is kept cost 13 ms per 10^6 kept elements), hence
-// the stages: a claim per STAGE_BYTES of kept elements and one per wave at the end.
-template <typename C>
-__device__ __forceinline__ void flush_stage(const C* stage, uint32_t count, uint32_t* cursor, C* __restrict__ dst, uint32_t limit, uint32_t lane) {
-    if (count == 0) return;
-    uint32_t base = 0;
-    if (lane == 0) base = atomicAdd(cursor, count);
-    base = (uint32_t)__builtin_amdgcn_readfirstlane((int)base);
-    wave_sync();
-    for (uint32_t i = lane; i < count; i += 64)
-        if (base + i < limit) dst[base + i] = stage[i];
-    wave_sync();
-}
-
 template <typename K, typename C>
 __global__ __launch_bounds__(HIST_THREADS) void topk_collect_kernel(const K* __restrict__ keys, uint32_t len, K neg, K pos, TopkHeader* __restrict__ hdr,
                                                                    C* __restrict__ sel, uint32_t k, C* __restrict__ cand, uint32_t cap) {
@@ -294,7 +175,7 @@ __global__ __launch_bounds__(HIST_THREADS) void topk_collect_kernel(const K* __r
     const K pref = header_key<K>(hdr->pref), pmask = header_key<K>(hdr->pmask);
     const uint32_t ppref = hdr->pos_pref, ppmask = hdr->pos_mask;
     const bool collect_cand = hdr->fill == 0;
-    stream_keys<K>(keys, len, [&](K raw, uint32_t idx, bool valid) {
+    stream_keys<K, HIST_UNROLL>(keys, len, [&](K raw, uint32_t idx, bool valid) {
         const K m = map_key<K>(raw, neg, pos);
         const K km = (K)(m & pmask);
         const uint32_t pm = idx & ppmask;

@@ -300,6 +300,85 @@ def topk_device_tensor(keys, k, largest=False, index=None, scratch=None, cand_ca
     return out_keys, out_index
 
 
+def select_limits(dtype, index_bytes=0):
+    """``rdst_hip_select_limits``: (max_ranks, bits of the first digit, bits of the later digits, default cand_capacity, most
+    levels one round can take) of :func:`select_device_tensor` for keys of ``dtype``; ``index_bytes``: 0 = keys only, 4 or 8."""
+    _kind, nbytes, _levels = key_info(dtype)
+    out = (ctypes.c_uint32 * 5)()
+    _lib.check(_lib.load().rdst_hip_select_limits(nbytes, int(index_bytes), out))
+    return tuple(int(v) for v in out)
+
+
+def select_scratch_bytes(n, n_ranks, dtype, index_bytes=0, cand_capacity=0):
+    """``rdst_hip_select_scratch_bytes``: bytes of scratch :func:`select_device_tensor` needs for ``n`` keys of ``dtype`` (0 for
+    widths the entry is not built for).  Never ``n``-sized, and the same for every ``n_ranks``."""
+    _kind, nbytes, _levels = key_info(dtype)
+    return int(_lib.load().rdst_hip_select_scratch_bytes(int(n), int(n_ranks), nbytes, int(index_bytes), int(cand_capacity)))
+
+
+def select_state(scratch):
+    """``rdst_hip_debug_select_state`` (test hook, blocking): what the most recent round of :func:`select_device_tensor` on
+    ``scratch`` decided — dict with ``levels``, ``groups`` (distinct prefixes at the end), ``candidates`` (collected) and
+    ``exhausted`` (the digits ran out: the answers are the prefixes)."""
+    import torch
+    out = (ctypes.c_uint64 * 4)()
+    with torch.cuda.device(scratch.device):
+        _lib.check(_lib.load().rdst_hip_debug_select_state(_ptr(scratch), _stream_handle(scratch), out))
+    return {"levels": int(out[0]), "groups": int(out[1]), "candidates": int(out[2]), "exhausted": int(out[3])}
+
+
+def quantile_ranks(n, qs, method="lower"):
+    """The ranks (0-based positions of the sorted array of ``n`` elements) that ``numpy.quantile(a, qs, method=...)`` indexes
+    for ``method`` "lower", "higher" or "nearest", as a list of ints for :func:`select_device_tensor`.  Pure, host only."""
+    import numpy as np
+    n = int(n)
+    if n < 1:
+        raise ValueError("quantile_ranks needs n >= 1")
+    q = np.atleast_1d(np.asarray(qs, dtype=np.float64))
+    if q.size and not (np.all(q >= 0) and np.all(q <= 1)):
+        raise ValueError("quantiles must lie in [0, 1]")
+    virtual = (n - 1) * q                                   # numpy's virtual index for these three methods
+    if method == "lower":
+        r = np.floor(virtual)
+    elif method == "higher":
+        r = np.ceil(virtual)
+    elif method == "nearest":
+        r = np.around(virtual)                              # half to even, as numpy does
+    else:
+        raise ValueError('method must be "lower", "higher" or "nearest"')
+    return [int(v) for v in np.clip(r, 0, n - 1).astype(np.int64)]
+
+
+def select_device_tensor(keys, ranks, largest=False, index=None, scratch=None, cand_capacity=0, check=True, key=None):
+    """``rdst_hip_select_device``: the keys of the 1-D contiguous HIP tensor ``keys`` (``key="u128"/"i128"``: shape (n, 2)) that
+    stand at the positions ``ranks`` of the sort's order — ``largest``: of the descending order —, slot ``i`` for ``ranks[i]``,
+    as a new tensor; ``keys`` is not modified and not sorted.  ``ranks``: a HOST sequence of ints below ``n``, any order,
+    repeats allowed (:func:`quantile_ranks` makes one from quantiles); a device tensor is refused, never copied behind the
+    caller's back.  ``index``: ``None`` for keys only, ``torch.int32`` or ``torch.int64`` to get the input position of each
+    element of a stable argsort as well (4- and 8-byte keys).  ``scratch``: optional uint8 HIP tensor of at least
+    :func:`select_scratch_bytes` bytes (allocated when omitted); ``cand_capacity``: 0 = the library's default, any value >= 1
+    gives the same result.  Returns ``(out_keys, out_index or None)``.  The call only enqueues work on the tensor's current
+    stream; ``check=False`` makes no blocking call at all (kernel failures then surface in :func:`device_status`)."""
+    import torch
+    kind, nbytes, levels, n, _per_key = _keys_operand("select_device_tensor", keys, key)
+    if isinstance(ranks, torch.Tensor) and ranks.is_cuda:
+        raise ValueError("select_device_tensor takes its ranks from the host: pass a list or ranks.tolist(), not a device tensor")
+    ranks = [int(r) for r in (ranks.tolist() if hasattr(ranks, "tolist") else ranks)]
+    if any(not 0 <= r < n for r in ranks):
+        raise ValueError("every rank must lie in 0..len-1")
+    index_bytes = _index_bytes(index)
+    nr = len(ranks)
+    out_keys = torch.empty((nr, 2) if _wide(key) else (nr,), dtype=keys.dtype, device=keys.device)
+    out_index = None if index is None else torch.empty(nr, dtype=index, device=keys.device)
+    if nr == 0:
+        return out_keys, out_index
+    need = int(_lib.load().rdst_hip_select_scratch_bytes(n, nr, nbytes, index_bytes, int(cand_capacity)))
+    scratch, sbytes = _scratch(scratch, need, keys.device)
+    _call(keys, check, "rdst_hip_select_device", _ptr(keys), n, (ctypes.c_uint64 * nr)(*ranks), nr, _ptr(out_keys), _ptr(out_index), index_bytes,
+          _ptr(scratch), sbytes, int(cand_capacity), nbytes, kind, levels, _lib.RDST_TOPK_LARGEST if largest else 0)
+    return out_keys, out_index
+
+
 def segments_limits(dtype, val_bytes=0):
     """``rdst_hip_sort_segments_limits``: (wave_max, block_max) of the segmented sort for keys of ``dtype`` (a numpy / torch
     dtype or its name, ``"u128"`` / ``"i128"``) and values of ``val_bytes`` bytes (0: keys only) — the longest segment one
@@ -1083,7 +1162,7 @@ def profile_runs() -> int:
     return int(_lib.load().rdst_hip_profile_runs())
 
 
-STAGE_NAMES = {1: "clear", 2: "histogram", 3: "scan", 4: "pass", 5: "copy_back", 6: "histogram16", 7: "route", 8: "local_sort", 10: "msd_pass_a", 11: "msd_pass_b", 12: "sample", 13: "segments", 14: "segments_tiled", 15: "topk"}
+STAGE_NAMES = {1: "clear", 2: "histogram", 3: "scan", 4: "pass", 5: "copy_back", 6: "histogram16", 7: "route", 8: "local_sort", 10: "msd_pass_a", 11: "msd_pass_b", 12: "sample", 13: "segments", 14: "segments_tiled", 15: "topk", 16: "select"}
 
 
 def profile_run(run: int, levels: int):
@@ -1104,7 +1183,7 @@ def profile_run(run: int, levels: int):
         code, level = kinds[i] & 0xFF, (kinds[i] >> 8) & 0xFF
         name = STAGE_NAMES.get(code, f"stage{code}")
         ms = float(buf[i])
-        out["stages"].append((name, level if name in ("pass", "topk") else None, ms))   # (topk: the select level; 255 = the collection pass)
+        out["stages"].append((name, level if name in ("pass", "topk", "select") else None, ms))   # (topk: the select level; 255 = the collection pass)
         if name == "pass":
             out["passes"].append(ms)
         else:
