@@ -384,7 +384,49 @@ void topk_segments(const T* dev_keys, std::size_t len, const std::uint64_t* offs
                                                 largest ? RDST_TOPK_LARGEST : 0u, stream));
 }
 
-// The same with the table of borders in DEVICE memory (rdst_hip_topk_segments_device_offsets): dev_offsets holds
+// Order statistics of every segment [offsets[s], offsets[s + 1]) of one DEVICE-resident slice
+// (rdst_hip_select_segments_device): slot i of row s of the outputs, dev_out_keys + s * n_ranks (and dev_out_index +
+// s * n_ranks), receives what select_device gives for that segment at the rank ranks[i] stands for in a segment of its length
+// (rank_for_length; rank_at / rank_quantile make a spec), positions counted inside the segment.  A slot whose spec the segment
+// has no element for — an empty segment, an absolute rank at or past its length — is not written.  offsets and ranks: HOST
+// arrays, read before the call returns.  dev_scratch: 256-byte aligned, at least select_segments_scratch_bytes<T>(n_segments,
+// longest segment, n_ranks) / <T, Idx>(...) bytes.  Asynchronous as topk_segments is.
+inline rdst_rank_spec rank_at(std::uint32_t rank) { return rdst_rank_spec{rank, 0u, RDST_RANK_LOWER, 0u}; }
+inline rdst_rank_spec rank_quantile(std::uint32_t num, std::uint32_t den, std::uint32_t mode = RDST_RANK_LOWER) {
+    return rdst_rank_spec{num, den, mode, 0u};
+}
+// the rank `spec` stands for in a segment of n keys; false: none (an empty segment, an absolute rank >= n)
+inline bool rank_for_length(const rdst_rank_spec& spec, std::uint64_t n, std::uint64_t* rank_out) {
+    const int rc = rdst_rank_for_length(&spec, n, rank_out);
+    if (rc < 0) detail::check(rc);
+    return rc == 1;
+}
+template <typename T>
+std::size_t select_segments_scratch_bytes(std::size_t n_segments, std::size_t longest_segment, std::size_t n_ranks) {
+    return rdst_hip_select_segments_scratch_bytes(n_segments, longest_segment, n_ranks, sizeof(T), 0);
+}
+template <typename T, typename Idx>
+std::size_t select_segments_scratch_bytes(std::size_t n_segments, std::size_t longest_segment, std::size_t n_ranks) {
+    return rdst_hip_select_segments_scratch_bytes(n_segments, longest_segment, n_ranks, sizeof(T), sizeof(Idx));
+}
+template <typename T>
+void select_segments(const T* dev_keys, std::size_t len, const std::uint64_t* offsets, std::size_t n_segments, const rdst_rank_spec* ranks,
+                     std::size_t n_ranks, T* dev_out_keys, void* dev_scratch, std::size_t scratch_bytes, bool largest = false, void* stream = nullptr) {
+    detail::check(rdst_hip_select_segments_device(dev_keys, len, offsets, n_segments, ranks, n_ranks, dev_out_keys, nullptr, 0, dev_scratch, scratch_bytes,
+                                                  sizeof(T), RadixKey<T>::kind, static_cast<std::uint32_t>(RadixKey<T>::LEVELS),
+                                                  largest ? RDST_TOPK_LARGEST : 0u, stream));
+}
+template <typename T, typename Idx>
+void select_segments(const T* dev_keys, std::size_t len, const std::uint64_t* offsets, std::size_t n_segments, const rdst_rank_spec* ranks,
+                     std::size_t n_ranks, T* dev_out_keys, Idx* dev_out_index, void* dev_scratch, std::size_t scratch_bytes, bool largest = false,
+                     void* stream = nullptr) {
+    static_assert(std::is_unsigned<Idx>::value && (sizeof(Idx) == 4 || sizeof(Idx) == 8), "positions are 4- or 8-byte unsigned integers");
+    detail::check(rdst_hip_select_segments_device(dev_keys, len, offsets, n_segments, ranks, n_ranks, dev_out_keys, dev_out_index, sizeof(Idx), dev_scratch,
+                                                  scratch_bytes, sizeof(T), RadixKey<T>::kind, static_cast<std::uint32_t>(RadixKey<T>::LEVELS),
+                                                  largest ? RDST_TOPK_LARGEST : 0u, stream));
+}
+
+// topk_segments with the table of borders in DEVICE memory (rdst_hip_topk_segments_device_offsets): dev_offsets holds
 // n_segments + 1 borders of type Off (a 4- or 8-byte unsigned integer), read in stream order.  far_capacity == 0: fully
 // asynchronous — no copy to the host, no wait; every segment beyond block_max is served by ONE workgroup whatever its length (a
 // performance cliff for very long rows, never a wrong answer), and a k beyond k_stream_max with such a segment, or an invalid

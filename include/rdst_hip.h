@@ -437,6 +437,79 @@ int rdst_topk_segments_plan(const uint64_t* offsets, uint64_t n_segments, uint64
  * below block_max leaves the stream class empty. */
 int rdst_hip_set_topk_segments_stream_max(uint32_t stream_max);
 
+/* ---- order statistics of every segment in one call ---------------------------------------------------
+ * The median of every row, the deciles of every CSR row: rdst_hip_select_device per segment, in one call.  Segments differ
+ * in length, so a rank is given as a SPEC that every segment resolves against its own length n_s:
+ *   den == 0: the absolute rank `num`; a segment with n_s <= num has no such element: its slot is NOT written.
+ *   den  > 0: the quantile num / den (num <= den): the virtual index (n_s - 1) * num / den as an exact rational, rounded by
+ *             `mode` as numpy.quantile's methods "lower", "higher" and "nearest" (half to even) round it.  Always a rank
+ *             below n_s.  64-bit integer arithmetic only, no floating point: both factors are below 2^32. */
+#define RDST_RANK_LOWER   0u   /* floor of the virtual index (numpy method="lower")   */
+#define RDST_RANK_HIGHER  1u   /* ceil                                   ("higher")   */
+#define RDST_RANK_NEAREST 2u   /* round half to even                     ("nearest")  */
+typedef struct { uint32_t num, den, mode, reserved; } rdst_rank_spec;
+/* Host only, pure: the rank `spec` stands for in a segment of n keys.  1 = *rank_out is that rank (below n); 0 = none
+ * (n == 0, or an absolute rank >= n; *rank_out is not written); RDST_ERR_ARG = a bad spec (den > 0 && num > den; mode > 2;
+ * reserved != 0; mode != 0 with den == 0), a NULL argument, or a quantile of n > 2^32 keys. */
+int rdst_rank_for_length(const rdst_rank_spec* spec, uint64_t n, uint64_t* rank_out);
+/* offsets: HOST table of n_segments + 1 non-decreasing element indices exactly as rdst_hip_topk_segments_device takes it,
+ * read before the call returns; ranks: HOST array of n_ranks specs, repeats allowed, any order, read before the call returns
+ * too; len < 2^32; segment starts need the element's alignment only.
+ *   - Row s of the outputs is dev_out_keys + s * n_ranks and dev_out_index + s * n_ranks (elements).  Slot i of row s holds,
+ *     bit for bit, what rdst_hip_select_device returns for the slice dev_keys + offsets[s] of length n_s at the rank
+ *     rdst_rank_for_length(&ranks[i], n_s), with the same kind, flags and index width: positions are local to the segment,
+ *     equal keys count in ascending position, -0.0 / +0.0 and NaN payloads are distinct keys; with RDST_TOPK_LARGEST the
+ *     order is that of the complemented mapped key, as in the select.
+ *   - Slots without a rank — every slot of an empty segment, an absolute rank at or past the segment's length — are NOT
+ *     written, the input is never written.  Of the scratch only [0, rdst_hip_select_segments_scratch_bytes(n_segments,
+ *     longest segment, n_ranks, elem_bytes, index_bytes)) is written; it needs no clearing, and stream order makes it
+ *     reusable by the next call.
+ *   - Keys only: every width and kind of rdst_hip_select_device (1, 2, 4, 8, 16 bytes); with an index (4 or 8 bytes): 4- and
+ *     8-byte keys.  With a NULL dev_out_index, index_bytes is not looked at.  RDST_KEY_BYTES_BE: RDST_ERR_UNSUPPORTED.
+ *   - There is no limit on n_ranks and no data-dependent failure.  The work list is rdst_topk_segments_plan's with k = 1, so
+ *     the class of a segment follows from its length alone (rdst_hip_select_segments_limits; bm = block_max for this key
+ *     width, with a 4-byte position beside the key only when an index is asked for):
+ *       1 .. wave_max     one wave per segment, four segments per workgroup: the segment is ordered in registers and LDS
+ *                         and the thread that holds a rank stores it;
+ *       .. bm             one workgroup per segment, longest first: the same with the workgroup's level loop;
+ *       .. stream_max     one workgroup per segment, longest first: the specs are resolved and served in ascending rank
+ *                         order; a rank outside what the LDS stage holds runs a radix select on the mapped key from the
+ *                         root, streamed from global memory, until at most bm keys lie on its prefix (keys before the
+ *                         prefix are only counted), one more read collects those, the level loop orders them, and every
+ *                         rank inside them is answered without another read;
+ *       longer ("far")    rdst_hip_select_device's own route, one segment after another on `stream`, with the ranks the
+ *                         host resolved.
+ *     The specs travel as kernel arguments, max_ranks per round; a longer list is served in rounds over the same items,
+ *     slot i keeping its place in the row.  stream_max is the border rdst_hip_set_topk_segments_stream_max moves.
+ *   - ASYNCHRONOUS exactly as rdst_hip_topk_segments_device is: the work list travels through the pinned staging buffer the
+ *     library keeps per device, and the one possible wait is on that buffer's event.  Kernel failures surface in
+ *     rdst_hip_device_status.
+ *   - Arguments, checked in this order before any device work: the key arguments as rdst_hip_topk_segments_device checks
+ *     them (the sort's codes and messages; BYTES_BE -> RDST_ERR_UNSUPPORTED); len >= 2^32 -> RDST_ERR_UNSUPPORTED; unknown
+ *     flag bits -> RDST_ERR_ARG; n_ranks == 0 or n_segments == 0 -> RDST_OK, nothing else is looked at; the table: NULL
+ *     offsets, n_segments >= 2^32, decreasing offsets, a last offset past len -> RDST_ERR_ARG; NULL ranks, a bad spec ->
+ *     RDST_ERR_ARG, the message names the first bad i; NULL dev_out_keys -> RDST_ERR_ARG, misaligned to the element ->
+ *     RDST_ERR_ALIGN; with an index: index_bytes not 4 or 8 -> RDST_ERR_ARG, key width not 4 or 8 -> RDST_ERR_UNSUPPORTED,
+ *     misaligned index pointer -> RDST_ERR_ALIGN; NULL scratch -> RDST_ERR_ARG; scratch not 256-byte aligned ->
+ *     RDST_ERR_ALIGN; scratch_bytes below rdst_hip_select_segments_scratch_bytes(...) for the table's longest segment ->
+ *     RDST_ERR_ARG. */
+int rdst_hip_select_segments_device(const void* dev_keys, uint64_t len,
+                                    const uint64_t* offsets, uint64_t n_segments,
+                                    const rdst_rank_spec* ranks, uint64_t n_ranks,
+                                    void* dev_out_keys, void* dev_out_index, uint32_t index_bytes,
+                                    void* dev_scratch, uint64_t scratch_bytes,
+                                    uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels,
+                                    uint32_t flags, void* stream);
+/* The scratch of the call above.  Pure but for the border's setter, monotone in every argument: the item table, 16 bytes per
+ * segment rounded up to 256, and — if a segment of `longest_segment` keys would be of the far class — behind it
+ * rdst_hip_select_scratch_bytes(longest_segment, n_ranks, elem_bytes, index_bytes, 0).  0 for no segment, 2^32 segments or
+ * keys and more, and unsupported widths. */
+uint64_t rdst_hip_select_segments_scratch_bytes(uint64_t n_segments, uint64_t longest_segment, uint64_t n_ranks,
+                                                uint32_t elem_bytes, uint32_t index_bytes);
+/* out = { wave_max, block_max, stream_max, max_ranks per round } for this key width (index_bytes 0 = keys only: the larger
+ * keys-only tile).  Pure but for rdst_hip_set_topk_segments_stream_max.  Unsupported widths: rdst_hip_topk_limits' codes. */
+int rdst_hip_select_segments_limits(uint32_t elem_bytes, uint32_t index_bytes, uint32_t out[4]);
+
 /* The two segmented sorts (rdst_hip_sort_segments_device, ..._pairs_device) with the table of borders in DEVICE memory (src/sorter.rs:131-138, as above): a CSR row pointer, the
  * cumulative sum of a ragged batch's lengths, the bucket borders rdst_hip_split_top_level_device leaves behind — no copy of
  * the table to the host, no host plan.  dev_offsets: n_segments + 1 unsigned integers of offset_bytes (4 or 8) bytes,

@@ -22,6 +22,7 @@ RDST_STAGE_SEGMENTS_TILED = 14   # rdst_stage: the tiled route of the nowait ent
 RDST_STAGE_TOPK = 15       # rdst_stage: one select level of the partial sort (level in bits 8..15; 0xFF: the collection pass)
 RDST_STAGE_SELECT = 16     # rdst_stage: one level of one round of the order statistics (level in bits 8..15; 0xFF: the collection pass)
 RDST_TOPK_LARGEST = 1      # rdst_hip_topk_device flags: the k largest, in descending order
+RDST_RANK_LOWER, RDST_RANK_HIGHER, RDST_RANK_NEAREST = 0, 1, 2   # rdst_rank_spec.mode: how a quantile's virtual index is rounded
 
 
 class TuningParamsC(ctypes.Structure):
@@ -48,6 +49,11 @@ class SegmentItemC(ctypes.Structure):
     _fields_ = [("start", ctypes.c_uint64), ("len", ctypes.c_uint32), ("seg", ctypes.c_uint32)]
 
 
+class RankSpecC(ctypes.Structure):
+    """rdst_rank_spec: an absolute rank (den == 0) or the quantile num / den rounded by mode, resolved per segment"""
+    _fields_ = [("num", ctypes.c_uint32), ("den", ctypes.c_uint32), ("mode", ctypes.c_uint32), ("reserved", ctypes.c_uint32)]
+
+
 class RdstHipError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"rdst_hip call failed with status {code}: {msg}")
@@ -57,7 +63,7 @@ class RdstHipError(RuntimeError):
 def _signatures():
     vp, u64, u32, ci = ctypes.c_void_p, ctypes.c_uint64, ctypes.c_uint32, ctypes.c_int
     u64p, u32p, u8p, f32p = ctypes.POINTER(u64), ctypes.POINTER(u32), ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_float)
-    opts, kfp, items = ctypes.POINTER(HipOptsC), ctypes.POINTER(KeyFieldC), ctypes.POINTER(SegmentItemC)
+    opts, kfp, items, specs = ctypes.POINTER(HipOptsC), ctypes.POINTER(KeyFieldC), ctypes.POINTER(SegmentItemC), ctypes.POINTER(RankSpecC)
     return {
         "rdst_hip_sort": (ci, [vp, u64, u32, ci, u32, opts]),
         "rdst_hip_sort_device": (ci, [vp, vp, u64, u32, ci, u32, vp]),
@@ -81,6 +87,10 @@ def _signatures():
         "rdst_hip_topk_segments_limits": (ci, [u32, u32, u32p]),
         "rdst_topk_segments_plan": (ci, [u64p, u64, u64, u64, u32, u32, items, u64, u64p, u64p]),
         "rdst_hip_set_topk_segments_stream_max": (ci, [u32]),
+        "rdst_rank_for_length": (ci, [specs, u64, u64p]),
+        "rdst_hip_select_segments_device": (ci, [vp, u64, u64p, u64, specs, u64, vp, vp, u32, vp, u64, u32, ci, u32, u32, vp]),
+        "rdst_hip_select_segments_scratch_bytes": (u64, [u64, u64, u64, u32, u32]),
+        "rdst_hip_select_segments_limits": (ci, [u32, u32, u32p]),
         "rdst_hip_topk_segments_device_offsets": (ci, [vp, u64, vp, u32, u64, u64, vp, vp, u32, vp, u64, u64, u32, ci, u32, u32, vp]),
         "rdst_hip_topk_segments_device_offsets_scratch_bytes": (u64, [u64, u64, u64, u32, u32]),
         "rdst_hip_debug_topk_segments_plan_device": (ci, [vp, u32, u64, u64, u64, u32, u32, u32, vp, u64, items, u64, u64p, u64p, u32p, vp]),

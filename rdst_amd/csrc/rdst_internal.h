@@ -176,6 +176,15 @@ int stage_segment_items(int device, const rdst_segment_item* items, size_t count
 // index_bytes, 0) in `scratch`; `cus`: the device's compute units.  No copy to the host, no wait.
 int topk_slice_locked(const void* keys, uint64_t len, uint64_t k, void* out_keys, void* out_index, uint32_t index_bytes, void* scratch,
                       uint32_t elem_bytes, rdst_key_kind kind, bool largest, int cus, hipStream_t s);
+// rdst_select.hip: rdst_hip_select_device after its checks, with the layout of rdst_hip_select_scratch_bytes(len, n_ranks,
+// elem_bytes, index_bytes, cand_capacity) in `scratch`.  ranks[i] < len goes to slot slots[i] of the outputs (`slots` ==
+// nullptr: to slot i).  `order`: order_ranks' answer for `ranks`, made before the mutex was taken.  No copy to the host, no wait.
+int select_slice_locked(const void* keys, uint64_t len, const uint64_t* ranks, const uint64_t* slots, const uint64_t* order, uint64_t n_ranks,
+                        void* out_keys, void* out_index, uint32_t index_bytes, void* scratch, uint64_t cand_capacity, uint32_t elem_bytes,
+                        rdst_key_kind kind, bool largest, int cus, hipStream_t s);
+// rdst_select.hip: the indices of `ranks` in ascending rank order, equal ranks in index order, into order_out[0 .. n_ranks).  No
+// lock needed; RDST_ERR_ARG if the sort's host memory cannot be had.
+int order_ranks(const uint64_t* ranks, uint64_t n_ranks, uint64_t* order_out);
 // rdst_topk_segments.hip: the three batched launches of the segmented partial sort over an item table in device memory,
 // for rdst_topk_segments_offsets.hip.  One call as the launches see it:
 struct TopkSegmentsCall {

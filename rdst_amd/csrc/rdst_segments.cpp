@@ -14,7 +14,8 @@
 // states them, and the scratch layouts, once for both files.
 //
 // The segmented partial sort (rdst_hip_topk_segments_device, rdst_topk_segments.hip) has its limits, its border setter and its
-// plan here too: four classes, and a segment of one key is work.
+// plan here too: four classes, and a segment of one key is work.  The segmented select (rdst_hip_select_segments_device,
+// rdst_select_segments.hip) runs that plan with k = 1; its rank rule (rdst_rank_for_length) and its limits are here.
 //
 // Host only: no HIP here (bound by tests/test_segments_plan.py without a device, and compiled into a stand-alone
 // program under the address sanitizer by the same test).
@@ -25,6 +26,7 @@
 #include <vector>
 
 #include "rdst_hip.h"
+#include "rdst_rank_rule.h"
 #include "rdst_segments_layout.h"
 
 namespace rdst_internal {
@@ -174,5 +176,25 @@ extern "C" int rdst_topk_segments_plan(const uint64_t* offsets, uint64_t n_segme
     rdst_segment_item* block = items_out + counts[0];
     std::stable_sort(block, block + counts[1], longer);
     std::stable_sort(block + counts[1], block + counts[1] + counts[2], longer);
+    return RDST_OK;
+}
+
+// ---- the segmented select: the rank rule and the limits (the kernels and the entry: rdst_select_segments.hip) ---------------
+
+extern "C" int rdst_rank_for_length(const rdst_rank_spec* spec, uint64_t n, uint64_t* rank_out) {
+    if (!spec || !rank_out) return note_error(RDST_ERR_ARG, "rank_for_length: null argument");
+    if (!rdst_rank_rule::spec_ok(*spec))
+        return note_error(RDST_ERR_ARG, "rank spec: num <= den for a quantile, mode 0 .. 2 (0 for an absolute rank), reserved 0");
+    if (spec->den != 0 && n > (1ull << 32)) return note_error(RDST_ERR_ARG, "rank_for_length: a quantile takes n <= 2^32");
+    uint64_t rank = 0;
+    if (!rdst_rank_rule::resolve(*spec, n, &rank)) return 0;
+    *rank_out = rank;
+    return 1;
+}
+
+extern "C" int rdst_hip_select_segments_limits(uint32_t elem_bytes, uint32_t index_bytes, uint32_t out[4]) {
+    if (!out) return note_error(RDST_ERR_ARG, "select_segments_limits: null output");
+    if (int rc = rdst_hip_topk_segments_limits(elem_bytes, index_bytes, out)) return rc;  // the classes of the plan with k = 1
+    out[3] = L::SELECT_SEGMENTS_MAX_RANKS;
     return RDST_OK;
 }

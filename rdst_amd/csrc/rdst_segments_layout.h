@@ -36,6 +36,10 @@ constexpr uint32_t block_max(size_t key_bytes, size_t val_bytes) {              
 // whole-array route's per-call floor, at 2^18 the route's every-CU reads win, for 4- and 8-byte keys alike.
 constexpr uint32_t TOPK_STREAM_MAX_DEFAULT = 1u << 17;
 
+// The segmented select (rdst_select_segments.hip): rank specs per round, a kernel argument of 16 bytes each; one lane of a
+// 32-lane step resolves each against the segment's length.
+constexpr uint32_t SELECT_SEGMENTS_MAX_RANKS = 32;
+
 // ---- scratch (byte offsets from its 256-byte aligned base; every array is rounded up to 256 bytes) ----------------------
 constexpr uint64_t MAX_SEGMENTS = 1ull << 30;  // of a table in device memory
 constexpr uint64_t up256(uint64_t bytes) { return (bytes + 255) / 256 * 256; }

@@ -422,6 +422,7 @@ struct SelectCall {
     const void* keys;
     uint64_t len;
     const uint64_t* ranks;
+    const uint64_t* slots;  // the output slot of each rank; nullptr: rank i goes to slot i
     const uint64_t* order;  // the ranks' indices, ascending by rank (equal ranks in slot order)
     uint64_t n_ranks;
     void *out_keys, *out_index;
@@ -476,7 +477,7 @@ int run_select(const SelectCall& c) {
         ra.n = (uint32_t)std::min<uint64_t>(MAX_RANKS, c.n_ranks - start);
         for (uint32_t i = 0; i < ra.n; ++i) {
             ra.rank[i] = (uint32_t)c.ranks[order[start + i]];
-            ra.slot[i] = (uint32_t)order[start + i];
+            ra.slot[i] = (uint32_t)(c.slots ? c.slots[order[start + i]] : order[start + i]);
         }
         RDST_HIP_TRY(hipMemsetAsync(c.scratch, 0, c.L.cand, c.s));  // header, table and counters: the caller never clears the scratch
         if ((rc = launch("select_init_kernel", select_init_kernel, dim3(1), dim3(64), 0, c.s, hdr, table, len, cap))) return rc;
@@ -535,6 +536,41 @@ int dispatch_select(const SelectCall& c, uint32_t index_bytes) {
 
 }  // namespace
 
+// Ascending rank order (equal ranks in slot order), before the mutex is taken; nothing may be thrown through the C ABI.
+int rdst_internal::order_ranks(const uint64_t* ranks, uint64_t n_ranks, uint64_t* order_out) {
+    try {
+        std::iota(order_out, order_out + n_ranks, 0ull);
+        std::stable_sort(order_out, order_out + n_ranks, [&](uint64_t a, uint64_t b) { return ranks[a] < ranks[b]; });
+    } catch (const std::exception&) {
+        return set_error(RDST_ERR_ARG, "select: no host memory to order n_ranks ranks (16 bytes per rank)");
+    }
+    return RDST_OK;
+}
+
+// rdst_hip_select_device after its checks and the ordering of its ranks (rdst_internal.h); rdst_select_segments.hip runs its
+// far class on it.
+int rdst_internal::select_slice_locked(const void* keys, uint64_t len, const uint64_t* ranks, const uint64_t* slots, const uint64_t* order,
+                                       uint64_t n_ranks, void* out_keys, void* out_index, uint32_t index_bytes, void* scratch, uint64_t cand_capacity,
+                                       uint32_t elem_bytes, rdst_key_kind kind, bool largest, int cus, hipStream_t s) {
+    SelectCall c{};
+    c.L = select_layout(len, elem_bytes, index_bytes, cand_capacity);
+    c.keys = keys;
+    c.len = len;
+    c.ranks = ranks;
+    c.slots = slots;
+    c.n_ranks = n_ranks;
+    c.out_keys = out_keys;
+    c.out_index = out_index;
+    c.scratch = static_cast<char*>(scratch);
+    c.elem_bytes = elem_bytes;
+    c.kind = kind;
+    c.largest = largest;
+    c.cus = cus;
+    c.s = s;
+    c.order = order;
+    return dispatch_select(c, index_bytes);
+}
+
 extern "C" {
 
 uint64_t rdst_hip_select_scratch_bytes(uint64_t len, uint64_t n_ranks, uint32_t elem_bytes, uint32_t index_bytes, uint64_t cand_capacity) {
@@ -584,34 +620,21 @@ int rdst_hip_select_device(const void* dev_keys, uint64_t len, const uint64_t* r
     }
     if (dev_scratch == nullptr) return set_error(RDST_ERR_ARG, "select: null scratch");
     if (misaligned(dev_scratch, 256)) return set_error(RDST_ERR_ALIGN, "select: scratch not aligned to 256 bytes");
-    SelectCall c{};
-    c.L = select_layout(len, elem_bytes, index_bytes, cand_capacity);
-    if (scratch_bytes < c.L.total)
+    if (scratch_bytes < select_layout(len, elem_bytes, index_bytes, cand_capacity).total)
         return set_error(RDST_ERR_ARG, "select: scratch_bytes is below rdst_hip_select_scratch_bytes(len, n_ranks, elem_bytes, index_bytes, cand_capacity)");
-    c.keys = dev_keys;
-    c.len = len;
-    c.ranks = ranks;
-    c.n_ranks = n_ranks;
-    c.out_keys = dev_out_keys;
-    c.out_index = dev_out_index;
-    c.scratch = static_cast<char*>(dev_scratch);
-    c.elem_bytes = elem_bytes;
-    c.kind = kind;
-    c.largest = (flags & RDST_TOPK_LARGEST) != 0;
-    c.s = static_cast<hipStream_t>(stream);
     // ascending rank order (equal ranks in slot order), before the mutex is taken; nothing may be thrown through the C ABI
     std::vector<uint64_t> order;
     try {
         order.resize(n_ranks);
-        std::iota(order.begin(), order.end(), 0ull);
-        std::stable_sort(order.begin(), order.end(), [&](uint64_t a, uint64_t b) { return ranks[a] < ranks[b]; });
     } catch (const std::exception&) {
         return set_error(RDST_ERR_ARG, "select: no host memory to order n_ranks ranks (16 bytes per rank)");
     }
-    c.order = order.data();
-    if (int rc = rdst_internal::device_cus(&c.cus)) return rc;  // (takes the mutex itself)
+    if (int rc = rdst_internal::order_ranks(ranks, n_ranks, order.data())) return rc;
+    int cus = 0;
+    if (int rc = rdst_internal::device_cus(&cus)) return rc;  // (takes the mutex itself)
     std::lock_guard<std::mutex> lock(rdst_internal::library_mutex());
-    return dispatch_select(c, index_bytes);
+    return rdst_internal::select_slice_locked(dev_keys, len, ranks, nullptr, order.data(), n_ranks, dev_out_keys, dev_out_index, index_bytes, dev_scratch, cand_capacity,
+                                              elem_bytes, kind, (flags & RDST_TOPK_LARGEST) != 0, cus, static_cast<hipStream_t>(stream));
 }
 
 int rdst_hip_debug_select_state(const void* dev_scratch, void* stream, uint64_t out[4]) {

@@ -567,6 +567,128 @@ def topk_rows_tensor(keys2d, k, largest=False, index=None, scratch=None, check=T
     return topk_segments_device_tensor(keys2d.reshape(-1), offsets, k, largest=largest, index=index, scratch=scratch, check=check, out=out)
 
 
+def select_segments_limits(dtype, index_bytes=0):
+    """``rdst_hip_select_segments_limits``: (wave_max, block_max, stream_max, max_ranks) of the segmented select for keys of
+    ``dtype`` (a dtype or its name, ``"u128"`` / ``"i128"``); ``index_bytes``: 0 = keys only, 4 or 8.  Segments up to wave_max
+    take one wave, up to block_max one workgroup, up to stream_max one workgroup that streams them; longer ones take
+    :func:`select_device_tensor`'s route, one segment after another.  max_ranks: the rank specs of one round."""
+    _kind, nbytes, _levels = key_info(dtype)
+    out = (ctypes.c_uint32 * 4)()
+    _lib.check(_lib.load().rdst_hip_select_segments_limits(nbytes, int(index_bytes), out))
+    return tuple(int(v) for v in out)
+
+
+def select_segments_scratch_bytes(n_segments, longest_segment, n_ranks, dtype, index_bytes=0):
+    """``rdst_hip_select_segments_scratch_bytes``: bytes of scratch :func:`select_segments_device_tensor` needs for
+    ``n_segments`` segments, the longest of ``longest_segment`` keys of ``dtype`` (0 for widths the entry is not built for)."""
+    _kind, nbytes, _levels = key_info(dtype)
+    return int(_lib.load().rdst_hip_select_segments_scratch_bytes(int(n_segments), int(longest_segment), int(n_ranks), nbytes, int(index_bytes)))
+
+
+_RANK_MODES = {"lower": _lib.RDST_RANK_LOWER, "higher": _lib.RDST_RANK_HIGHER, "nearest": _lib.RDST_RANK_NEAREST}
+
+
+def _rank_specs(ranks, quantiles, method):
+    """the (num, den, mode) of every spec of a segmented select, the absolute ranks first, then the quantiles"""
+    from fractions import Fraction
+    if method not in _RANK_MODES:
+        raise ValueError('method must be "lower", "higher" or "nearest"')
+    specs = []
+    for name, operand in (("ranks", ranks), ("quantiles", quantiles)):
+        if _is_torch_tensor(operand) and operand.is_cuda:
+            raise ValueError(f"select_segments_device_tensor takes its {name} from the host: pass a list, not a device tensor")
+    for r in ([] if ranks is None else (ranks.tolist() if hasattr(ranks, "tolist") else ranks)):
+        r = int(r)
+        if not 0 <= r < 1 << 32:
+            raise ValueError("an absolute rank lies in 0..2^32-1")
+        specs.append((r, 0, 0))
+    for q in ([] if quantiles is None else (quantiles.tolist() if hasattr(quantiles, "tolist") else quantiles)):
+        if isinstance(q, Fraction):
+            f = q
+        elif isinstance(q, (tuple, list)):
+            num, den = (int(v) for v in q)
+            if den <= 0:
+                raise ValueError("a quantile (num, den) has den > 0")
+            if not 0 <= num <= den:
+                raise ValueError("quantiles must lie in [0, 1]")
+            if den >= 1 << 32:
+                raise ValueError("a quantile's denominator must be below 2^32")
+            specs.append((num, den, _RANK_MODES[method]))                  # as given: not reduced
+            continue
+        else:
+            f = Fraction(repr(float(q)))                                    # the shortest decimal that names this float: 0.1 is 1/10
+        if not 0 <= f <= 1:
+            raise ValueError("quantiles must lie in [0, 1]")
+        if f.denominator >= 1 << 32:
+            raise ValueError("a quantile's denominator must be below 2^32")
+        specs.append((f.numerator, f.denominator, _RANK_MODES[method]))
+    return specs
+
+
+def rank_for_length(n, rank=None, quantile=None, method="lower"):
+    """``rdst_rank_for_length``: the rank that one spec — the absolute ``rank``, or the ``quantile`` (a ``Fraction``, a
+    ``(num, den)`` pair or a float, taken at its shortest decimal form) rounded by ``method`` — stands for in a segment of
+    ``n`` keys, or ``None`` where the segment has no such element.  Pure, host only, integer arithmetic."""
+    if (rank is None) == (quantile is None):
+        raise ValueError("rank_for_length takes a rank or a quantile")
+    (num, den, mode), = _rank_specs(None if rank is None else [rank], None if quantile is None else [quantile], method)
+    spec = _lib.RankSpecC(num, den, mode, 0)
+    out = ctypes.c_uint64(0)
+    rc = _lib.load().rdst_rank_for_length(ctypes.byref(spec), int(n), ctypes.byref(out))
+    if rc < 0:
+        _lib.check(rc)
+    return int(out.value) if rc == 1 else None
+
+
+def select_segments_device_tensor(keys, offsets, ranks=None, quantiles=None, method="lower", largest=False, index=None, scratch=None, check=True,
+                                  key=None, out=None):
+    """``rdst_hip_select_segments_device``: :func:`select_device_tensor` for every segment ``keys[offsets[s]:offsets[s + 1]]``
+    of a contiguous 1-D HIP tensor, in one call (``key="u128"/"i128"``: shape (n, 2), offsets count keys).  Every segment
+    resolves the specs against its own length ``n_s``: ``ranks`` holds ints, absolute ranks (a segment of ``n_s <= rank`` keys
+    has no such element); ``quantiles`` holds ``fractions.Fraction``, ``(num, den)`` pairs or floats — a float is taken at its
+    shortest decimal form, so 0.1 means 1/10 — and stands for the element ``numpy.quantile(..., method=method)`` indexes, with
+    ``method`` "lower", "higher" or "nearest", in exact integer arithmetic (:func:`rank_for_length`).  Both lists may be given:
+    the ranks come first, then the quantiles.  ``offsets``, ``ranks`` and ``quantiles`` are read on the HOST; device tensors
+    are refused, never copied behind the caller's back.  Returns ``(out_keys, out_index or None)`` of shape (n_segments,
+    n_ranks): slot ``i`` of row ``s`` holds the key of segment ``s`` at the rank of spec ``i`` in the sort's order —
+    ``largest``: the descending order — and, with ``index`` (``torch.int32`` / ``torch.int64``; 4- and 8-byte keys), its
+    position inside the segment as a stable argsort gives it.  Slots without a rank (empty segments, absolute ranks at or past
+    the length) are NOT written: pass a pre-filled ``out=(out_keys, out_index)`` to recognise them.  ``keys`` is not
+    modified.  ``scratch``: optional uint8 HIP tensor of at least :func:`select_segments_scratch_bytes` bytes, 256-byte aligned
+    (allocated when omitted).  The call only enqueues work on the tensor's current stream; ``check=False`` makes no blocking
+    call at all."""
+    kind, nbytes, levels, n, per_key = _keys_operand("select_segments_device_tensor", keys, key)
+    index_bytes = _index_bytes(index)
+    if _is_torch_tensor(offsets) and offsets.is_cuda:
+        raise ValueError("select_segments_device_tensor takes its offsets from the host: pass a list or offsets.tolist(), not a device tensor")
+    specs = _rank_specs(ranks, quantiles, method)
+    nr = len(specs)
+    off = _host_offsets(offsets)
+    n_segments = off.size - 1
+    out_keys, out_index = _topk_rows_out(keys, key, per_key, index, n_segments, nr, out)
+    if nr == 0 or n_segments == 0:
+        return out_keys, out_index
+    longest = int((off[1:] - off[:-1]).max()) if bool((off[1:] >= off[:-1]).all()) else 0   # (a decreasing table: the library says so)
+    need = int(_lib.load().rdst_hip_select_segments_scratch_bytes(n_segments, longest, nr, nbytes, index_bytes))
+    scratch, sbytes = _scratch(scratch, need, keys.device)
+    table = (_lib.RankSpecC * nr)(*(_lib.RankSpecC(num, den, mode, 0) for num, den, mode in specs))
+    _call(keys, check, "rdst_hip_select_segments_device", _ptr(keys), n, off.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), n_segments, table, nr,
+          _ptr(out_keys), _ptr(out_index), index_bytes, _ptr(scratch), sbytes, nbytes, kind, levels, _lib.RDST_TOPK_LARGEST if largest else 0)
+    return out_keys, out_index
+
+
+def select_rows_tensor(keys2d, ranks=None, quantiles=None, method="lower", largest=False, index=None, scratch=None, check=True, out=None):
+    """:func:`select_segments_device_tensor` for the rows of a contiguous 2-D HIP tensor: the median, the deciles, the k-th
+    value of every row and, with ``index``, their columns."""
+    _on_device("select_rows_tensor", keys2d)
+    if keys2d.dim() != 2 or not keys2d.is_contiguous():
+        raise ValueError("select_rows_tensor needs a contiguous 2-D tensor")
+    rows, cols = int(keys2d.shape[0]), int(keys2d.shape[1])
+    offsets = np.arange(rows + 1, dtype=np.uint64) * np.uint64(cols)
+    return select_segments_device_tensor(keys2d.reshape(-1), offsets, ranks=ranks, quantiles=quantiles, method=method, largest=largest, index=index,
+                                         scratch=scratch, check=check, out=out)
+
+
 def segments_device_offsets_scratch_bytes(n_segments):
     """``rdst_hip_sort_segments_device_offsets_scratch_bytes``: bytes of scratch the device-offsets segmented sort needs for
     ``n_segments`` segments (0 for none, or for more than 2^30)."""
