@@ -462,6 +462,42 @@ void topk_segments_device_offsets(const T* dev_keys, std::size_t len, const Off*
                                                         static_cast<std::uint32_t>(RadixKey<T>::LEVELS), largest ? RDST_TOPK_LARGEST : 0u, stream));
 }
 
+// select_segments with the table of borders in DEVICE memory (rdst_hip_select_segments_device_offsets): dev_offsets holds
+// n_segments + 1 borders of type Off (a 4- or 8-byte unsigned integer), read in stream order; ranks stays a HOST array.
+// far_capacity == 0: fully asynchronous — no copy to the host, no wait; every segment beyond block_max is served by ONE
+// workgroup whatever its length (a performance cliff for very long rows, steeper than topk's, never a wrong answer), and only
+// an invalid table can fail: it writes nothing and raises bit 0x10 of the device error word.  far_capacity > 0 (the longest
+// segment the call may meet; len if nothing better is known): the classes of select_segments, one wait for the stream, an
+// invalid table or a longer far segment throws.  dev_scratch: 256-byte aligned, at least
+// select_segments_device_offsets_scratch_bytes<T>(n_segments, far_capacity, n_ranks) / <T, Idx>(...) bytes.
+template <typename T>
+std::size_t select_segments_device_offsets_scratch_bytes(std::size_t n_segments, std::size_t far_capacity, std::size_t n_ranks) {
+    return rdst_hip_select_segments_device_offsets_scratch_bytes(n_segments, far_capacity, n_ranks, sizeof(T), 0);
+}
+template <typename T, typename Idx>
+std::size_t select_segments_device_offsets_scratch_bytes(std::size_t n_segments, std::size_t far_capacity, std::size_t n_ranks) {
+    return rdst_hip_select_segments_device_offsets_scratch_bytes(n_segments, far_capacity, n_ranks, sizeof(T), sizeof(Idx));
+}
+template <typename T, typename Off>
+void select_segments_device_offsets(const T* dev_keys, std::size_t len, const Off* dev_offsets, std::size_t n_segments, const rdst_rank_spec* ranks,
+                                    std::size_t n_ranks, T* dev_out_keys, void* dev_scratch, std::size_t scratch_bytes, std::size_t far_capacity = 0,
+                                    bool largest = false, void* stream = nullptr) {
+    static_assert(std::is_unsigned<Off>::value && (sizeof(Off) == 4 || sizeof(Off) == 8), "borders are 4- or 8-byte unsigned integers");
+    detail::check(rdst_hip_select_segments_device_offsets(dev_keys, len, dev_offsets, sizeof(Off), n_segments, ranks, n_ranks, dev_out_keys, nullptr, 0,
+                                                          dev_scratch, scratch_bytes, far_capacity, sizeof(T), RadixKey<T>::kind,
+                                                          static_cast<std::uint32_t>(RadixKey<T>::LEVELS), largest ? RDST_TOPK_LARGEST : 0u, stream));
+}
+template <typename T, typename Off, typename Idx>
+void select_segments_device_offsets(const T* dev_keys, std::size_t len, const Off* dev_offsets, std::size_t n_segments, const rdst_rank_spec* ranks,
+                                    std::size_t n_ranks, T* dev_out_keys, Idx* dev_out_index, void* dev_scratch, std::size_t scratch_bytes,
+                                    std::size_t far_capacity = 0, bool largest = false, void* stream = nullptr) {
+    static_assert(std::is_unsigned<Off>::value && (sizeof(Off) == 4 || sizeof(Off) == 8), "borders are 4- or 8-byte unsigned integers");
+    static_assert(std::is_unsigned<Idx>::value && (sizeof(Idx) == 4 || sizeof(Idx) == 8), "positions are 4- or 8-byte unsigned integers");
+    detail::check(rdst_hip_select_segments_device_offsets(dev_keys, len, dev_offsets, sizeof(Off), n_segments, ranks, n_ranks, dev_out_keys, dev_out_index,
+                                                          sizeof(Idx), dev_scratch, scratch_bytes, far_capacity, sizeof(T), RadixKey<T>::kind,
+                                                          static_cast<std::uint32_t>(RadixKey<T>::LEVELS), largest ? RDST_TOPK_LARGEST : 0u, stream));
+}
+
 // DEVICE-resident [u8; N] rows (src/radix_key_impl.rs:78-85) and DEVICE-resident structs ordered by a described key
 // (src/radix_key.rs; examples/impl_radix_key.rs:32-56), in place and with no host involvement
 // (rdst_hip_sort_bytes_device_nowait, rdst_hip_sort_records_by_fields_device_nowait): N, or the sum of the fields' widths,

@@ -667,6 +667,70 @@ int rdst_hip_debug_topk_segments_plan_device(const void* dev_offsets, uint32_t o
                                              rdst_segment_item* items_out, uint64_t capacity, uint64_t class_counts_out[4],
                                              uint64_t* longest_far_out, uint32_t* flags_out, void* stream);
 
+/* rdst_hip_select_segments_device with the table of borders in DEVICE memory: a CSR row pointer, the cumulative sum of a
+ * ragged batch's lengths, the bucket borders rdst_hip_split_top_level_device leaves behind — no copy of the table to the host,
+ * no host plan.  dev_offsets follows the rules of rdst_hip_sort_segments_device_offsets: n_segments + 1 unsigned integers of
+ * offset_bytes (4 or 8) bytes, aligned to that size, read only, and read in stream order (the kernel that writes the table may
+ * still be running when the call returns); n_segments <= 2^30; len < 2^32.  ranks stays a HOST array of n_ranks specs, read
+ * before the call returns: the host knows them, and they travel as kernel arguments.  The result is exactly
+ * rdst_hip_select_segments_device's, bit for bit: row s of the outputs starts at element s * n_ranks; slot i holds what
+ * rdst_hip_select_device gives for the slice at the rank rdst_rank_for_length(&ranks[i], n_s), positions local to the segment;
+ * slots without a rank, empty segments and the input are not written.  Keys only: every width and kind; with an index (4 or 8
+ * bytes): 4- and 8-byte keys; RDST_TOPK_LARGEST as there.
+ *
+ * dev_scratch: 256-byte aligned, at least rdst_hip_select_segments_device_offsets_scratch_bytes(n_segments, far_capacity,
+ * n_ranks, elem_bytes, index_bytes) bytes; only that range is written, and it needs no clearing.  The plan lives there, made
+ * on the device as rdst_hip_topk_segments_device_offsets makes its own: the select's work list is rdst_topk_segments_plan's
+ * with k = 1, so rdst_hip_debug_topk_segments_plan_device with k = 1 is the test hook for THIS entry's plan too.  Stream order
+ * makes the scratch reusable by the next call on the same stream.
+ *
+ * far_capacity chooses between two modes, as it does for rdst_hip_topk_segments_device_offsets:
+ *   far_capacity == 0: FULLY ASYNCHRONOUS.  The call enqueues the plan — once per call — and three launches per round of
+ *       max_ranks specs (rdst_hip_select_segments_limits; every round runs over the same items, slot i keeping its place in
+ *       the row; grids bounded by what the host knows — n_segments and len —, counts read from the scratch; surplus waves and
+ *       workgroups return at once) and returns: no copy to or from the host, no wait on an event or on the stream, no staging
+ *       buffer.  The one exception is the one every entry shares: a library workspace that has to grow, here for the plan's
+ *       pair sort.  In this mode THE STREAM CLASS HAS NO UPPER LENGTH: every segment beyond block_max is served by one
+ *       workgroup's streamed radix select, longest first, whatever rdst_hip_set_topk_segments_stream_max says.  One workgroup
+ *       on a very long segment is a performance cliff, never a wrong answer — and a steeper one than the partial sort's: every
+ *       rank that misses what the LDS stage holds counts again from the root, so a segment of 2^24 keys is read by 1 of 256
+ *       compute units several times per distinct rank neighbourhood; far_capacity > 0 is the answer to it.  With k = 1 the plan
+ *       never meets "k > k_stream_max", so this mode has NO DATA-DEPENDENT FAILURE except an invalid table (decreasing, last
+ *       offset past len), which cannot be answered by the return code: NO output element is written, the bit of value 16
+ *       (0x10) of the sticky device error word is set, and rdst_hip_device_status returns RDST_ERR_DEVICE once.
+ *   far_capacity > 0: EVERY TABLE, ONE WAIT.  The classes are exactly rdst_hip_select_segments_device's (they follow
+ *       rdst_hip_select_segments_limits and rdst_hip_set_topk_segments_stream_max).  The call WAITS once for `stream` after the
+ *       plan and reads the four counts, the longest far segment and the flags; with far segments it reads their items and
+ *       unsaturated lengths too (one further wait), resolves and orders their ranks on the host as the host-table entry does,
+ *       and runs them one after another by rdst_hip_select_device's route, in the scratch behind the plan.  Because the host
+ *       sees the flags, an invalid table or a longest far segment above far_capacity is RDST_ERR_ARG with nothing written and
+ *       nothing left in the error word.  A caller without a better bound passes len.
+ * Profiling: the batched launches end rdst_hip_select_segments_device's stages, RDST_STAGE_SEGMENTS | (class << 8).
+ * Arguments, checked in this order before any device work:
+ *   1. the key arguments, len and flags as rdst_hip_select_segments_device checks them (its codes and messages);
+ *   2. n_ranks == 0 or n_segments == 0 -> RDST_OK, nothing else is looked at;
+ *   3. the table as rdst_hip_sort_segments_device_offsets checks it: n_segments > 2^30 -> RDST_ERR_UNSUPPORTED; offset_bytes
+ *      not 4 or 8, NULL dev_offsets -> RDST_ERR_ARG; dev_offsets misaligned to offset_bytes -> RDST_ERR_ALIGN;
+ *   4. NULL ranks, a bad spec -> RDST_ERR_ARG, the message names the first bad i;
+ *   5. the outputs as rdst_hip_select_segments_device checks them: NULL dev_out_keys -> RDST_ERR_ARG; misaligned ->
+ *      RDST_ERR_ALIGN; with an index: index_bytes not 4 or 8 -> RDST_ERR_ARG, key width not 4 or 8 -> RDST_ERR_UNSUPPORTED,
+ *      misaligned index pointer -> RDST_ERR_ALIGN (with a NULL dev_out_index, index_bytes is not looked at);
+ *   6. the scratch: NULL -> RDST_ERR_ARG; not 256-byte aligned -> RDST_ERR_ALIGN; far_capacity >= 2^32 or scratch_bytes below
+ *      rdst_hip_select_segments_device_offsets_scratch_bytes(...) -> RDST_ERR_ARG. */
+int rdst_hip_select_segments_device_offsets(const void* dev_keys, uint64_t len,
+                                            const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments,
+                                            const rdst_rank_spec* ranks, uint64_t n_ranks,
+                                            void* dev_out_keys, void* dev_out_index, uint32_t index_bytes,
+                                            void* dev_scratch, uint64_t scratch_bytes, uint64_t far_capacity,
+                                            uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels,
+                                            uint32_t flags, void* stream);
+/* The scratch of the call above.  Pure, monotone in every argument: the plan's layout
+ * (rdst_hip_sort_segments_device_offsets_scratch_bytes(n_segments): 32 bytes per segment and a 256-byte header) and, with
+ * far_capacity > 0, behind it rdst_hip_select_scratch_bytes(far_capacity, n_ranks, elem_bytes, index_bytes, 0).
+ * 0 for n_segments == 0 or > 2^30, far_capacity >= 2^32 and unsupported widths. */
+uint64_t rdst_hip_select_segments_device_offsets_scratch_bytes(uint64_t n_segments, uint64_t far_capacity, uint64_t n_ranks,
+                                                               uint32_t elem_bytes, uint32_t index_bytes);
+
 /* [u8; N] rows (N = n_bytes in 1..RDST_BYTES_MAX_N), device-resident, sorted IN PLACE in lexicographic order
  * (src/radix_key_impl.rs:78-85).  No alignment requirement on dev_rows.  dev_scratch: at least
  * rdst_hip_sort_bytes_scratch_bytes(len, n_bytes) bytes, 256-byte aligned.  len <= 1: no-op.

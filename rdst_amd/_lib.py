@@ -94,6 +94,8 @@ def _signatures():
         "rdst_hip_topk_segments_device_offsets": (ci, [vp, u64, vp, u32, u64, u64, vp, vp, u32, vp, u64, u64, u32, ci, u32, u32, vp]),
         "rdst_hip_topk_segments_device_offsets_scratch_bytes": (u64, [u64, u64, u64, u32, u32]),
         "rdst_hip_debug_topk_segments_plan_device": (ci, [vp, u32, u64, u64, u64, u32, u32, u32, vp, u64, items, u64, u64p, u64p, u32p, vp]),
+        "rdst_hip_select_segments_device_offsets": (ci, [vp, u64, vp, u32, u64, specs, u64, vp, vp, u32, vp, u64, u64, u32, ci, u32, u32, vp]),
+        "rdst_hip_select_segments_device_offsets_scratch_bytes": (u64, [u64, u64, u64, u32, u32]),
         "rdst_hip_sort_segments_device": (ci, [vp, vp, u64, u64, u64p, u64, u32, ci, u32, vp]),
         "rdst_hip_sort_segments_pairs_device": (ci, [vp, vp, vp, vp, u64, u64, u64p, u64, u32, ci, u32, u32, vp]),
         "rdst_hip_sort_segments_limits": (ci, [u32, u32, u32p]),

@@ -11,7 +11,8 @@ SOURCES = [os.path.join(HERE, "csrc", "rdst_kernels.hip"), os.path.join(HERE, "c
            os.path.join(HERE, "csrc", "rdst_select.hip"),
            os.path.join(HERE, "csrc", "rdst_topk_segments.hip"), os.path.join(HERE, "csrc", "rdst_topk_segments_offsets.hip"),
            os.path.join(HERE, "csrc", "rdst_topk_segments_offsets.cpp"),
-           os.path.join(HERE, "csrc", "rdst_select_segments.hip"),
+           os.path.join(HERE, "csrc", "rdst_select_segments.hip"), os.path.join(HERE, "csrc", "rdst_select_segments_offsets.hip"),
+           os.path.join(HERE, "csrc", "rdst_select_segments_offsets.cpp"),
            os.path.join(HERE, "csrc", "rdst_tuner.cpp"),
            os.path.join(HERE, "csrc", "rdst_regions.cpp"), os.path.join(HERE, "csrc", "rdst_segments.cpp")]
 HEADERS = [os.path.join(ROOT, "include", "rdst_hip.h"), os.path.join(HERE, "csrc", "rdst_internal.h"),

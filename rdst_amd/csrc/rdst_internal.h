@@ -201,6 +201,36 @@ struct TopkSegmentsCall {
 // range from it; counts[0 .. 2] bound the counts, for the grids alone.  Ends the stages RDST_STAGE_SEGMENTS | (class << 8).
 // No copy to the host, no wait.
 int topk_segments_launch_locked(const TopkSegmentsCall& c, const rdst_segment_item* items, const uint32_t* hdr, const uint64_t counts[3]);
+// rdst_topk_segments_offsets.hip: the plan of the segmented partial sort made on the device, for
+// rdst_select_segments_offsets.hip (the select's plan is this one with k = 1).  Where it lies in the caller's scratch
+// (rdst_segments_layout.h: plan_layout, TopkPlanHeader) and what the classes were cut by:
+struct TopkSegmentsPlan {
+    uint32_t* hdr;
+    rdst_segment_item* items;
+    uint64_t* far_lens;  // the unsaturated lengths of the far items, in their order
+    uint32_t wave_max, block_max, stream_limit;
+};
+// Enqueues the plan for this k and these widths into `scratch` (rdst_hip_sort_segments_device_offsets_scratch_bytes(n_segments)
+// bytes of it).  `unbounded_stream`: the classes of the asynchronous mode, whose stream class has no upper length.  `no_far`:
+// a far segment raises TOPK_PLAN_FAR; with a flag up the counted kernels get zero counts and `err` (if given) the table bit.
+// No copy to the host, no wait.
+int topk_segments_plan_locked(const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments, uint64_t len, uint64_t k, uint32_t elem_bytes,
+                              uint32_t index_bytes, bool unbounded_stream, void* scratch, bool no_far, uint32_t* err, hipStream_t s,
+                              TopkSegmentsPlan* out);
+// rdst_select_segments.hip: the batched launches of the segmented select over an item table in device memory, every round of
+// c.n_ranks specs (`ranks`: host array), for both of its entries.  One call as the launches see it:
+struct SelectSegmentsCall {
+    const void* keys;
+    uint64_t n_ranks;
+    void *out_keys, *out_index;
+    uint32_t index_bytes, elem_bytes;
+    rdst_key_kind kind;
+    bool largest;
+    hipStream_t s;
+};
+// `hdr` and counts[0 .. 2] as for topk_segments_launch_locked.  No copy to the host, no wait.
+int select_segments_launch_locked(const SelectSegmentsCall& c, const rdst_segment_item* items, const uint32_t* hdr, const uint64_t counts[3],
+                                  const rdst_rank_spec* ranks);
 // rdst_segments.hip: what every entry with a table of borders in device memory checks of it before any device work
 // (n_segments, offset_bytes, the pointer and its alignment, 4-byte offsets against len); no lock needed.
 int check_offsets_table(const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments, uint64_t len);

@@ -75,6 +75,24 @@ static_assert(HDR_TOPK_WORDS * sizeof(uint32_t) == PLAN_HEADER_BYTES, "the heade
 constexpr uint32_t TOPK_PLAN_DECREASING = 1;  // offsets[s + 1] < offsets[s] somewhere
 constexpr uint32_t TOPK_PLAN_PAST_LEN = 2;    // offsets[n_segments] > len
 constexpr uint32_t TOPK_PLAN_FAR = 4;         // asynchronous mode only: a far segment, which only the host can enqueue
+// The header as a host reads it back: the first TOPK_PLAN_READ_WORDS words, decoded in one place for every entry that waits.
+constexpr int TOPK_PLAN_READ_WORDS = 8;
+struct TopkPlanResult {
+    uint64_t counts[4], longest_far;
+    uint32_t flags;
+};
+constexpr TopkPlanResult topk_plan_result(const uint32_t (&h)[TOPK_PLAN_READ_WORDS]) {
+    static_assert(HDR_TOPK_LONGEST_FAR + 1 < TOPK_PLAN_READ_WORDS && HDR_TOPK_N_FAR < TOPK_PLAN_READ_WORDS, "the words read cover what is decoded");
+    TopkPlanResult r{};
+    for (int c = 0; c < 4; ++c) r.counts[c] = h[HDR_TOPK_N_WAVE + c];
+    r.flags = h[HDR_TOPK_FLAGS];
+    r.longest_far = (uint64_t)h[HDR_TOPK_LONGEST_FAR] | ((uint64_t)h[HDR_TOPK_LONGEST_FAR + 1] << 32);
+    return r;
+}
+// What the host answers for a plan that raised TOPK_PLAN_DECREASING or TOPK_PLAN_PAST_LEN.
+constexpr const char* topk_plan_flags_message(uint32_t flags) {
+    return flags & TOPK_PLAN_DECREASING ? "segments: offsets must be non-decreasing" : "segments: the last offset lies past len";
+}
 
 // The class key of a segment of n keys (n < 2^32): the plan sorts (key, segment) pairs by the library's stable 4-level pair
 // sort, and the sorted pairs are the work list.  `stream_limit`: the longest segment of the stream class (block_max: none).

@@ -27,6 +27,11 @@
 //   far                            everything longer, one segment after another through rdst_hip_select_device's own route
 //                                  (rdst_internal::select_slice_locked) with the ranks the host resolved, in the part of the
 //                                  scratch behind the item table.
+//
+// Each of the three kernels is one body (select_segment_*_body) under two entries: the kernel the host-table entry launches
+// with the counts it knows, and a ..._counted_kernel that reads its item range from the plan header in device memory
+// (rdst_hip_select_segments_device_offsets, rdst_select_segments_offsets.hip).  Both entries go through
+// rdst_internal::select_segments_launch_locked, which serves the rounds.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -66,8 +71,8 @@ __device__ __forceinline__ uint32_t resolved_rank(const RankSpecs& rs, uint32_t 
 // ---- wave class --------------------------------------------------------------------------------------------------------------
 
 template <typename K, bool IDX>
-__global__ __launch_bounds__(SEG_WAVES * 64) void select_segment_wave_kernel(const K* __restrict__ keys, const rdst_segment_item* __restrict__ items,
-                                                                              uint32_t n_items, const Rows<K> o, const RankSpecs rs) {
+__device__ __forceinline__ void select_segment_wave_body(const K* __restrict__ keys, const rdst_segment_item* __restrict__ items, uint32_t n_items,
+                                                         const Rows<K>& o, const RankSpecs& rs) {
     constexpr int KPT = L::wave_kpt(sizeof(K));
     constexpr int CAP = 64 * KPT;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -103,17 +108,21 @@ __global__ __launch_bounds__(SEG_WAVES * 64) void select_segment_wave_kernel(con
     }
 }
 
+template <typename K, bool IDX>
+__global__ __launch_bounds__(SEG_WAVES * 64) void select_segment_wave_kernel(const K* __restrict__ keys, const rdst_segment_item* __restrict__ items,
+                                                                              uint32_t n_items, const Rows<K> o, const RankSpecs rs) {
+    select_segment_wave_body<K, IDX>(keys, items, n_items, o, rs);
+}
+
 // ---- block class -------------------------------------------------------------------------------------------------------------
 
 template <typename K, bool IDX>
-__global__ __launch_bounds__(BLOCK_THREADS) void select_segment_block_kernel(const K* __restrict__ keys, const rdst_segment_item* __restrict__ items,
-                                                                             const Rows<K> o, const RankSpecs rs) {
+__device__ __forceinline__ void select_segment_block_body(const K* __restrict__ keys, const rdst_segment_item it, const Rows<K> o, const RankSpecs rs) {
     constexpr int KPT = BlockLds<K, IDX>::KPT;
     constexpr uint32_t TILE = BlockLds<K, IDX>::TILE;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     __shared__ uint32_t s_rank[MAX_RANKS];
     const BlockLds<K, IDX> lds(smem);
-    const rdst_segment_item it = items[blockIdx.x];  // the grid is exactly this class's items
     const uint32_t n = it.len < TILE ? it.len : TILE;  // (the plan never hands this class a longer one)
     const K* seg = keys + it.start;
     const int rounds = (int)((n + BLOCK_THREADS - 1) / BLOCK_THREADS);
@@ -140,11 +149,18 @@ __global__ __launch_bounds__(BLOCK_THREADS) void select_segment_block_kernel(con
     }
 }
 
+template <typename K, bool IDX>
+__global__ __launch_bounds__(BLOCK_THREADS) void select_segment_block_kernel(const K* __restrict__ keys, const rdst_segment_item* __restrict__ items,
+                                                                             const Rows<K> o, const RankSpecs rs) {
+    select_segment_block_body<K, IDX>(keys, items[blockIdx.x], o, rs);  // the grid is exactly this class's items
+}
+
 // ---- stream class ------------------------------------------------------------------------------------------------------------
 
+// Nothing below assumes n <= stream_max: n, m, c_below, the ordinals and every counter are u32 and n < 2^32;
+// the asynchronous device-offsets entry hands it segments of any length.
 template <typename K, bool IDX>
-__global__ __launch_bounds__(BLOCK_THREADS) void select_segment_stream_kernel(const K* __restrict__ keys, const rdst_segment_item* __restrict__ items,
-                                                                              const Rows<K> o, const RankSpecs rs) {
+__device__ __forceinline__ void select_segment_stream_body(const K* __restrict__ keys, const rdst_segment_item it, const Rows<K> o, const RankSpecs rs) {
     constexpr int KPT = BlockLds<K, IDX>::KPT;
     constexpr uint32_t TILE = BlockLds<K, IDX>::TILE;
     constexpr uint32_t BITS = 8 * sizeof(K), DIGIT = sizeof(K) == 1 ? 8 : 12;  // rdst_topk.hip's digits
@@ -160,7 +176,6 @@ __global__ __launch_bounds__(BLOCK_THREADS) void select_segment_stream_kernel(co
     const BlockLds<K, IDX> lds(smem);
     uint32_t* cnt = lds.wave_hist;
     const uint32_t tid = threadIdx.x;
-    const rdst_segment_item it = items[blockIdx.x];  // the grid is exactly this class's items
     const uint32_t n = it.len;
     const SegmentCut<K> cut(keys + it.start, n);
 
@@ -253,23 +268,51 @@ __global__ __launch_bounds__(BLOCK_THREADS) void select_segment_stream_kernel(co
     }
 }
 
+template <typename K, bool IDX>
+__global__ __launch_bounds__(BLOCK_THREADS) void select_segment_stream_kernel(const K* __restrict__ keys, const rdst_segment_item* __restrict__ items,
+                                                                              const Rows<K> o, const RankSpecs rs) {
+    select_segment_stream_body<K, IDX>(keys, items[blockIdx.x], o, rs);  // the grid is exactly this class's items
+}
+
+// ---- the same three bodies with their item range read from the plan header in device memory (device-resident offsets) ----------
+//
+// rdst_topk_segments_offsets.hip writes the header (rdst_segments_layout.h: TopkPlanHeader) and the item table: the plan of
+// the segmented partial sort with k = 1.  The grids are bounds the host can state without the counts; waves and workgroups
+// past the count return before any barrier.  With a flag up the RUN counts are zero and nothing runs.
+template <typename K, bool IDX>
+__global__ __launch_bounds__(SEG_WAVES * 64) void select_segment_wave_counted_kernel(const K* __restrict__ keys,
+                                                                                      const rdst_segment_item* __restrict__ items,
+                                                                                      const uint32_t* __restrict__ hdr, const Rows<K> o, const RankSpecs rs) {
+    select_segment_wave_body<K, IDX>(keys, items, hdr[L::HDR_TOPK_RUN_WAVE], o, rs);
+}
+
+template <typename K, bool IDX>
+__global__ __launch_bounds__(BLOCK_THREADS) void select_segment_block_counted_kernel(const K* __restrict__ keys,
+                                                                                     const rdst_segment_item* __restrict__ items,
+                                                                                     const uint32_t* __restrict__ hdr, const Rows<K> o, const RankSpecs rs) {
+    if (blockIdx.x >= hdr[L::HDR_TOPK_RUN_BLOCK]) return;  // block-uniform
+    select_segment_block_body<K, IDX>(keys, items[hdr[L::HDR_TOPK_N_WAVE] + blockIdx.x], o, rs);
+}
+
+template <typename K, bool IDX>
+__global__ __launch_bounds__(BLOCK_THREADS) void select_segment_stream_counted_kernel(const K* __restrict__ keys,
+                                                                                      const rdst_segment_item* __restrict__ items,
+                                                                                      const uint32_t* __restrict__ hdr, const Rows<K> o, const RankSpecs rs) {
+    if (blockIdx.x >= hdr[L::HDR_TOPK_RUN_STREAM]) return;  // block-uniform
+    select_segment_stream_body<K, IDX>(keys, items[hdr[L::HDR_TOPK_N_WAVE] + hdr[L::HDR_TOPK_N_BLOCK] + blockIdx.x], o, rs);
+}
+
 // ---- host side ---------------------------------------------------------------------------------------------------------------
 
-struct SegSelectCall {
-    const void* keys;
-    uint64_t n_ranks;
-    void *out_keys, *out_index;
-    uint32_t index_bytes, elem_bytes;
-    rdst_key_kind kind;
-    bool largest;
-    hipStream_t s;
-};
+using SegSelectCall = rdst_internal::SelectSegmentsCall;
 
 bool misaligned(const void* p, uint64_t to) { return reinterpret_cast<uintptr_t>(p) % to != 0; }
 
-// One round over the item table in device memory: wave class first, then block class, then stream class.
+// One round over the item table in device memory: wave class first, then block class, then stream class.  `hdr` == nullptr:
+// the host knows the counts, counts[0 .. 2], and the classes follow one another in `items`.  With `hdr`, the plan header in
+// device memory: the counts stand there, and counts[0 .. 2] are the host's bounds on them, for the grids alone.
 template <typename K, bool IDX>
-int launch_round_t(const SegSelectCall& c, const rdst_segment_item* items, const uint64_t counts[3], const RankSpecs& rs) {
+int launch_round_t(const SegSelectCall& c, const rdst_segment_item* items, const uint32_t* hdr, const uint64_t counts[3], const RankSpecs& rs) {
     constexpr size_t wave_lds = wave_lds_bytes(sizeof(K), IDX), block_lds = block_lds_bytes(sizeof(K), IDX);
     static_assert(wave_lds <= LDS_LIMIT && block_lds + STREAM_STATIC_LDS <= LDS_LIMIT, "a workgroup's LDS stays within 160 KiB");
     unsigned __int128 neg, pos;
@@ -280,43 +323,65 @@ int launch_round_t(const SegSelectCall& c, const rdst_segment_item* items, const
         o.pos = (K)~o.pos;
     }
     const K* keys = static_cast<const K*>(c.keys);
+    const dim3 wave_grid((uint32_t)((counts[0] + SEG_WAVES - 1) / SEG_WAVES)), block_grid((uint32_t)counts[1]), stream_grid((uint32_t)counts[2]);
     int rc;
     if (counts[0]) {
-        if ((rc = launch("select_segment_wave_kernel", select_segment_wave_kernel<K, IDX>, dim3((uint32_t)((counts[0] + SEG_WAVES - 1) / SEG_WAVES)),
-                         dim3(SEG_WAVES * 64), wave_lds, c.s, keys, items, (uint32_t)counts[0], o, rs)))
-            return rc;
+        rc = hdr ? launch("select_segment_wave_counted_kernel", select_segment_wave_counted_kernel<K, IDX>, wave_grid, dim3(SEG_WAVES * 64), wave_lds, c.s,
+                          keys, items, hdr, o, rs)
+                 : launch("select_segment_wave_kernel", select_segment_wave_kernel<K, IDX>, wave_grid, dim3(SEG_WAVES * 64), wave_lds, c.s, keys, items,
+                          (uint32_t)counts[0], o, rs);
+        if (rc) return rc;
         if ((rc = rdst_internal::profile_stage_end(c.s, RDST_STAGE_SEGMENTS))) return rc;
     }
     if (counts[1]) {
-        if ((rc = launch("select_segment_block_kernel", select_segment_block_kernel<K, IDX>, dim3((uint32_t)counts[1]), dim3(BLOCK_THREADS), block_lds, c.s,
-                         keys, items + counts[0], o, rs)))
-            return rc;
+        rc = hdr ? launch("select_segment_block_counted_kernel", select_segment_block_counted_kernel<K, IDX>, block_grid, dim3(BLOCK_THREADS), block_lds,
+                          c.s, keys, items, hdr, o, rs)
+                 : launch("select_segment_block_kernel", select_segment_block_kernel<K, IDX>, block_grid, dim3(BLOCK_THREADS), block_lds, c.s, keys,
+                          items + counts[0], o, rs);
+        if (rc) return rc;
         if ((rc = rdst_internal::profile_stage_end(c.s, RDST_STAGE_SEGMENTS | (1u << 8)))) return rc;
     }
     if (counts[2]) {
-        if ((rc = launch("select_segment_stream_kernel", select_segment_stream_kernel<K, IDX>, dim3((uint32_t)counts[2]), dim3(BLOCK_THREADS), block_lds,
-                         c.s, keys, items + counts[0] + counts[1], o, rs)))
-            return rc;
+        rc = hdr ? launch("select_segment_stream_counted_kernel", select_segment_stream_counted_kernel<K, IDX>, stream_grid, dim3(BLOCK_THREADS), block_lds,
+                          c.s, keys, items, hdr, o, rs)
+                 : launch("select_segment_stream_kernel", select_segment_stream_kernel<K, IDX>, stream_grid, dim3(BLOCK_THREADS), block_lds, c.s, keys,
+                          items + counts[0] + counts[1], o, rs);
+        if (rc) return rc;
         if ((rc = rdst_internal::profile_stage_end(c.s, RDST_STAGE_SEGMENTS | (2u << 8)))) return rc;
     }
     return RDST_OK;
 }
 
-int launch_round(const SegSelectCall& c, const rdst_segment_item* items, const uint64_t counts[3], const RankSpecs& rs) {
+int launch_round(const SegSelectCall& c, const rdst_segment_item* items, const uint32_t* hdr, const uint64_t counts[3], const RankSpecs& rs) {
     if (c.index_bytes != 0)
-        return c.elem_bytes == 4 ? launch_round_t<uint32_t, true>(c, items, counts, rs) : launch_round_t<uint64_t, true>(c, items, counts, rs);
+        return c.elem_bytes == 4 ? launch_round_t<uint32_t, true>(c, items, hdr, counts, rs) : launch_round_t<uint64_t, true>(c, items, hdr, counts, rs);
     switch (c.elem_bytes) {
-        case 1: return launch_round_t<uint8_t, false>(c, items, counts, rs);
-        case 2: return launch_round_t<uint16_t, false>(c, items, counts, rs);
-        case 4: return launch_round_t<uint32_t, false>(c, items, counts, rs);
-        case 8: return launch_round_t<uint64_t, false>(c, items, counts, rs);
-        default: return launch_round_t<u128, false>(c, items, counts, rs);
+        case 1: return launch_round_t<uint8_t, false>(c, items, hdr, counts, rs);
+        case 2: return launch_round_t<uint16_t, false>(c, items, hdr, counts, rs);
+        case 4: return launch_round_t<uint32_t, false>(c, items, hdr, counts, rs);
+        case 8: return launch_round_t<uint64_t, false>(c, items, hdr, counts, rs);
+        default: return launch_round_t<u128, false>(c, items, hdr, counts, rs);
     }
 }
 
 uint64_t table_bytes(uint64_t n_segments) { return L::up256(n_segments * sizeof(rdst_segment_item)); }
 
 }  // namespace
+
+// Every round of c.n_ranks specs, MAX_RANKS a round, over the same items: slot i keeps its place in the row.
+int rdst_internal::select_segments_launch_locked(const SelectSegmentsCall& c, const rdst_segment_item* items, const uint32_t* hdr,
+                                                 const uint64_t counts[3], const rdst_rank_spec* ranks) {
+    if (counts[0] >= (1ull << 33) || counts[1] >= (1ull << 31) || counts[2] >= (1ull << 31))
+        return set_error(RDST_ERR_ARG, "segments: too many segments of one class for one launch");
+    for (uint64_t start = 0; start < c.n_ranks; start += MAX_RANKS) {
+        RankSpecs rs{};
+        rs.n = (uint32_t)std::min<uint64_t>(MAX_RANKS, c.n_ranks - start);
+        rs.slot0 = (uint32_t)start;
+        for (uint32_t i = 0; i < rs.n; ++i) rs.spec[i] = ranks[start + i];
+        if (int rc = launch_round(c, items, hdr, counts, rs)) return rc;
+    }
+    return RDST_OK;
+}
 
 extern "C" uint64_t rdst_hip_select_segments_scratch_bytes(uint64_t n_segments, uint64_t longest_segment, uint64_t n_ranks, uint32_t elem_bytes,
                                                            uint32_t index_bytes) {
@@ -383,8 +448,6 @@ extern "C" int rdst_hip_select_segments_device(const void* dev_keys, uint64_t le
         return set_error(RDST_ERR_ARG, "select: no host memory for the work list (16 bytes per segment) and the far segments' ranks (24 bytes per rank each)");
     }
     if ((rc = rdst_topk_segments_plan(offsets, n_segments, len, 1, elem_bytes, index_bytes, items.data(), total, counts, &longest_far))) return rc;
-    if (counts[0] >= (1ull << 33) || counts[1] >= (1ull << 31) || counts[2] >= (1ull << 31))
-        return set_error(RDST_ERR_ARG, "segments: too many segments of one class for one launch");
     // the far segments' ranks, resolved and ordered here, before the mutex is taken; a spec the segment has no element for is left out
     const uint64_t batched = counts[0] + counts[1] + counts[2];
     for (uint64_t f = 0; f < counts[3]; ++f) {
@@ -407,13 +470,7 @@ extern "C" int rdst_hip_select_segments_device(const void* dev_keys, uint64_t le
         RDST_HIP_TRY(hipGetDevice(&dev));
         if ((rc = rdst_internal::profile_open_run(c.s))) return rc;
         if ((rc = rdst_internal::stage_segment_items(dev, items.data(), (size_t)batched, dev_scratch, c.s))) return rc;
-        for (uint64_t start = 0; start < n_ranks; start += MAX_RANKS) {  // every round covers the same items
-            RankSpecs rs{};
-            rs.n = (uint32_t)std::min<uint64_t>(MAX_RANKS, n_ranks - start);
-            rs.slot0 = (uint32_t)start;
-            for (uint32_t i = 0; i < rs.n; ++i) rs.spec[i] = ranks[start + i];
-            if ((rc = launch_round(c, static_cast<const rdst_segment_item*>(dev_scratch), counts, rs))) return rc;
-        }
+        if ((rc = rdst_internal::select_segments_launch_locked(c, static_cast<const rdst_segment_item*>(dev_scratch), nullptr, counts, ranks))) return rc;
     }
     // far segments one after another, each by the whole-array select (no copy to the host, no wait), in the scratch behind the
     // table

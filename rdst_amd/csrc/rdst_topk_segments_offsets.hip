@@ -176,17 +176,12 @@ int topk_segments_async(const Call& c, uint64_t len, const void* dev_offsets, ui
 }
 
 // The header as the host reads it (the wait mode and the plan hook): one copy and one wait for `s`.
-struct PlanResult {
-    uint64_t counts[4], longest_far;
-    uint32_t flags;
-};
+using PlanResult = L::TopkPlanResult;
 int read_plan(const PlanScratch& P, PlanResult* r, hipStream_t s) {
-    uint32_t h[8] = {};
+    uint32_t h[L::TOPK_PLAN_READ_WORDS] = {};
     RDST_HIP_TRY(hipMemcpyAsync(h, P.hdr, sizeof h, hipMemcpyDeviceToHost, s));
     RDST_HIP_TRY(hipStreamSynchronize(s));
-    for (int c = 0; c < 4; ++c) r->counts[c] = h[L::HDR_TOPK_N_WAVE + c];
-    r->flags = h[L::HDR_TOPK_FLAGS];
-    r->longest_far = (uint64_t)h[L::HDR_TOPK_LONGEST_FAR] | ((uint64_t)h[L::HDR_TOPK_LONGEST_FAR + 1] << 32);
+    *r = L::topk_plan_result(h);
     return RDST_OK;
 }
 
@@ -199,8 +194,7 @@ int read_far(const PlanScratch& P, uint64_t batched, std::vector<rdst_segment_it
 }
 
 int flags_error(uint32_t flags) {
-    if (flags & L::TOPK_PLAN_DECREASING) return set_error(RDST_ERR_ARG, "segments: offsets must be non-decreasing");
-    return set_error(RDST_ERR_ARG, "segments: the last offset lies past len");
+    return set_error(RDST_ERR_ARG, L::topk_plan_flags_message(flags));
 }
 
 // The wait mode after the checks.  Callers hold the library's mutex.
@@ -236,6 +230,17 @@ int topk_segments_wait(const Call& c, uint64_t len, const void* dev_offsets, uin
 }
 
 }  // namespace
+
+// The plan for another entry over the same work list (rdst_internal.h; the segmented select's, k = 1).
+int rdst_internal::topk_segments_plan_locked(const void* dev_offsets, uint32_t offset_bytes, uint64_t n_segments, uint64_t len, uint64_t k,
+                                             uint32_t elem_bytes, uint32_t index_bytes, bool unbounded_stream, void* scratch, bool no_far, uint32_t* err,
+                                             hipStream_t s, TopkSegmentsPlan* out) {
+    Cuts cuts;
+    if (int rc = class_cuts(k, elem_bytes, index_bytes, unbounded_stream, &cuts)) return rc;
+    const PlanScratch P = plan_scratch(scratch, n_segments);
+    *out = {P.hdr, P.items, P.far_lens, cuts.wave_max, cuts.block_max, cuts.stream_limit};
+    return enqueue_plan(dev_offsets, offset_bytes, n_segments, len, cuts, P, no_far ? 1u : 0u, err, s);
+}
 
 extern "C" int rdst_hip_topk_segments_device_offsets(const void* dev_keys, uint64_t len, const void* dev_offsets, uint32_t offset_bytes,
                                                      uint64_t n_segments, uint64_t k, void* dev_out_keys, void* dev_out_index, uint32_t index_bytes,

@@ -695,13 +695,16 @@ def segments_device_offsets_scratch_bytes(n_segments):
     return int(_lib.load().rdst_hip_sort_segments_device_offsets_scratch_bytes(int(n_segments)))
 
 
-def _device_offsets(offsets, keys, n):
-    """(n_segments, offset_bytes) of a device-resident table of borders, checked without looking at its values"""
+def _device_offsets(offsets, keys, n, unsigned_too=False):
+    """(n_segments, offset_bytes) of a device-resident table of borders, checked without looking at its values;
+    ``unsigned_too``: uint32 and uint64 tensors are taken as well"""
     import torch
     if not _is_torch_tensor(offsets) or not offsets.is_cuda or offsets.device != keys.device:
         raise ValueError("offsets must be a tensor on the keys' HIP device")
     if offsets.dim() != 1 or offsets.numel() == 0 or not offsets.is_contiguous():
         raise ValueError("offsets: a contiguous 1-D tensor of n_segments + 1 element indices")
+    if unsigned_too and offsets.dtype in (getattr(torch, "uint32", None), getattr(torch, "uint64", None)):
+        return offsets.numel() - 1, offsets.element_size()
     if offsets.dtype not in (torch.int32, torch.int64):
         raise ValueError("offsets must be int32 or int64 (read as unsigned: a negative value fails the device's check)")
     if offsets.dtype == torch.int32 and n >= 2**31:
@@ -785,6 +788,51 @@ def topk_segments_device_offsets_tensor(keys, offsets, k, largest=False, index=N
     scratch, sbytes = _scratch(scratch, need, keys.device)
     _call(keys, check, "rdst_hip_topk_segments_device_offsets", _ptr(keys), n, _ptr(offsets), obytes, n_segments, k, _ptr(out_keys), _ptr(out_index),
           index_bytes, _ptr(scratch), sbytes, far_capacity, nbytes, kind, levels, _lib.RDST_TOPK_LARGEST if largest else 0)
+    return out_keys, out_index
+
+
+def select_segments_device_offsets_scratch_bytes(n_segments, far_capacity, n_ranks, dtype, index_bytes=0):
+    """``rdst_hip_select_segments_device_offsets_scratch_bytes``: bytes of scratch :func:`select_segments_device_offsets_tensor`
+    needs for ``n_segments`` segments of keys of ``dtype``: the plan and, with ``far_capacity`` > 0, behind it the select's
+    scratch for a far segment of ``far_capacity`` keys (0 for no segment, more than 2^30 of them, a ``far_capacity`` of 2^32 or
+    more, and widths the entry is not built for)."""
+    _kind, nbytes, _levels = key_info(dtype)
+    return int(_lib.load().rdst_hip_select_segments_device_offsets_scratch_bytes(int(n_segments), int(far_capacity), int(n_ranks), nbytes,
+                                                                                  int(index_bytes)))
+
+
+def select_segments_device_offsets_tensor(keys, offsets, ranks=None, quantiles=None, method="lower", largest=False, index=None, scratch=None,
+                                          far_capacity=0, check=True, key=None, out=None):
+    """``rdst_hip_select_segments_device_offsets``: :func:`select_segments_device_tensor` for a table of borders that lives on
+    the device — a CSR row pointer, a ``cumsum`` of lengths — and never visits the host.  ``offsets``: a contiguous 1-D int32,
+    int64, uint32 or uint64 tensor on the keys' device with n_segments + 1 entries, read as unsigned and in stream order.
+    ``ranks``, ``quantiles``, ``method``, the result, ``index`` and ``out`` are :func:`select_segments_device_tensor`'s; the
+    specs stay on the host.  ``scratch``: optional uint8 tensor of at least
+    :func:`select_segments_device_offsets_scratch_bytes` bytes, 256-byte aligned (allocated when omitted).
+
+    ``far_capacity=0`` is the fully asynchronous mode: nothing is copied to the host and nothing waited for (``check=False``
+    makes no blocking call at all).  Every segment beyond ``select_segments_limits(...)[1]`` keys is served by ONE workgroup,
+    whatever its length — correct at any length, slow for very long rows, and slower still with ranks far apart — and only a
+    table that decreases or ends past the keys can fail: it writes nothing and raises from :func:`device_status` (here, with
+    ``check``).  With ``far_capacity`` (the longest segment the call may meet; ``len(keys)`` if nothing better is known) the
+    classes are the host entry's; the call waits once for the stream to read the plan's counts, and an invalid table or a
+    segment beyond ``far_capacity`` raises at once."""
+    kind, nbytes, levels, n, per_key = _keys_operand("select_segments_device_offsets_tensor", keys, key)
+    index_bytes = _index_bytes(index)
+    far_capacity = int(far_capacity)
+    if far_capacity < 0:
+        raise ValueError("far_capacity must not be negative")
+    specs = _rank_specs(ranks, quantiles, method)
+    nr = len(specs)
+    n_segments, obytes = _device_offsets(offsets, keys, n, unsigned_too=True)
+    out_keys, out_index = _topk_rows_out(keys, key, per_key, index, n_segments, nr, out)
+    if nr == 0 or n_segments == 0:
+        return out_keys, out_index
+    need = int(_lib.load().rdst_hip_select_segments_device_offsets_scratch_bytes(n_segments, far_capacity, nr, nbytes, index_bytes))
+    scratch, sbytes = _scratch(scratch, need, keys.device)
+    table = (_lib.RankSpecC * nr)(*(_lib.RankSpecC(num, den, mode, 0) for num, den, mode in specs))
+    _call(keys, check, "rdst_hip_select_segments_device_offsets", _ptr(keys), n, _ptr(offsets), obytes, n_segments, table, nr, _ptr(out_keys),
+          _ptr(out_index), index_bytes, _ptr(scratch), sbytes, far_capacity, nbytes, kind, levels, _lib.RDST_TOPK_LARGEST if largest else 0)
     return out_keys, out_index
 
 

@@ -4,6 +4,7 @@ summary object.
 
     python tools/select_segments_bench.py [--reps 7] [--scale 1.0] [--out profiles/select_segments_bench.json]
     python tools/select_segments_bench.py --stream-max-sweep [--reps 7] [--out profiles/select_segments_bench.json]
+    python tools/select_segments_bench.py --device-offsets [--reps 7] [--out profiles/select_segments_offsets_bench.json]
 
 table   rows x row length 65 536 x 64, 4 096 x 4 096, 1 024 x 16 384, 64 x 131 072, 8 x 2^20 and a ragged table of 300 rows
         with lengths from 1 to 2^18; rank sets: the median, the nine deciles, 32 ranks (quantiles i / 31); u32, f32 and u64
@@ -15,6 +16,9 @@ table   rows x row length 65 536 x 64, 4 096 x 4 096, 1 024 x 16 384, 64 x 131 0
 --stream-max-sweep   one segment per call, lengths 2^15 .. 2^22, u32 and u64 keys, the median and the nine deciles: the stream
         class forced against the far class forced, both through rdst_hip_set_topk_segments_stream_max — the border was
         measured for top-k, and this says where it would belong for selects.
+--device-offsets     rdst_hip_select_segments_device_offsets, both modes, over the same tables and rank sets and one row of
+        2^24 keys, the table of borders a device tensor.  The baseline is what such a caller paid before the entry: the table
+        copied to the host, a synchronise, rdst_hip_select_segments_device.
 
 The candidates run in one process, alternating, after one untimed warm-up round; the time is HIP events on the stream around
 the calls, median over --reps with all of them kept.  Every result is compared with the sort baseline's."""
@@ -188,6 +192,56 @@ def stream_max_sweep(torch, rdst_amd, args):
     return results
 
 
+def device_offsets(torch, rdst_amd, args):
+    results = []
+    tables = list(_tables(args.scale)) + [("1x16777216", np.array([0, 1 << 24], dtype=np.uint64), 1 << 24)]
+    for shape, off, _cols in tables:
+        n, n_seg = int(off[-1]), len(off) - 1
+        longest = int((off[1:] - off[:-1]).max())
+        toff = torch.from_numpy(off.astype(np.int64)).cuda()
+        for kind, indexed in (("u32", False), ("f32", False), ("u64", False), ("f32", True)):
+            keys = _keys(torch, kind, n, n_seg % 11 + len(kind))
+            ib = 4 if indexed else 0
+            index = torch.int32 if indexed else None
+            for set_name, quantiles in RANK_SETS.items():
+                nr = len(quantiles)
+                host_scratch = torch.empty(rdst_amd.select_segments_scratch_bytes(n_seg, longest, nr, keys.dtype, ib), dtype=torch.uint8, device="cuda")
+                scratch = torch.empty(rdst_amd.select_segments_device_offsets_scratch_bytes(n_seg, n, nr, keys.dtype, ib), dtype=torch.uint8, device="cuda")
+                outs = {name: (torch.zeros((n_seg, nr), dtype=keys.dtype, device="cuda"),
+                               torch.zeros((n_seg, nr), dtype=torch.int32, device="cuda") if indexed else None) for name in ("baseline", "async", "wait")}
+
+                def baseline():
+                    host = toff.cpu().numpy().astype(np.uint64)             # the copy and the synchronise
+                    rdst_amd.select_segments_device_tensor(keys, host, quantiles=quantiles, index=index, scratch=host_scratch, check=False,
+                                                           out=outs["baseline"])
+
+                def run_async():
+                    rdst_amd.select_segments_device_offsets_tensor(keys, toff, quantiles=quantiles, index=index, scratch=scratch, check=False,
+                                                                   out=outs["async"])
+
+                def run_wait():
+                    rdst_amd.select_segments_device_offsets_tensor(keys, toff, quantiles=quantiles, index=index, scratch=scratch, far_capacity=n,
+                                                                   check=False, out=outs["wait"])
+
+                ms = _time_alternating(torch, {"baseline": baseline, "async": run_async, "wait": run_wait}, args.reps)
+                rdst_amd.device_status()
+                for name in ("async", "wait"):
+                    assert torch.equal(outs[name][0].view(torch.uint8), outs["baseline"][0].view(torch.uint8)), f"{name} and the host-table entry disagree"
+                    assert not indexed or torch.equal(outs[name][1], outs["baseline"][1]), f"{name}: the positions disagree"
+                med = {name: v[len(v) // 2] for name, v in ms.items()}
+                rec = {"part": "device_offsets", "shape": shape, "segments": n_seg, "n": n, "keys": kind, "index": ib, "ranks": set_name, "n_ranks": nr,
+                       "class_counts_wait": list(rdst_amd.topk_segments_plan(off, n, 1, keys.dtype, ib)[1]),
+                       "baseline_copy_sync_host_entry": _stats(ms["baseline"]), "async": _stats(ms["async"]), "wait": _stats(ms["wait"]),
+                       "baseline_over_async": round(med["baseline"] / med["async"], 3), "baseline_over_wait": round(med["baseline"] / med["wait"], 3),
+                       "results_equal": True}
+                print(json.dumps(rec), flush=True)
+                results.append(rec)
+                del host_scratch, scratch, outs
+            del keys
+            torch.cuda.empty_cache()
+    return results
+
+
 def slower_lists(rows):
     """the cases of the table where the entry's median is above a baseline's, by the unrounded ms (a ratio that rounds to 1.0
     may still be a loss): (slower than sort, slower than loop), each [shape, keys, index, ranks, baseline / entry]"""
@@ -208,6 +262,7 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--no-torch", action="store_true", help="leave the torch.median / torch.kthvalue column out")
     ap.add_argument("--stream-max-sweep", action="store_true", help="one segment per call: the stream class against the far class, by length")
+    ap.add_argument("--device-offsets", action="store_true", help="the entry with the borders in device memory, both modes, against copy + synchronise + host entry")
     args = ap.parse_args()
     import torch
     import rdst_amd
@@ -219,7 +274,14 @@ def main():
             old = json.load(f)
         summary.update({key: old[key] for key in ("stream_max_sweep", "crossing", "table", "slower_than_sort_baseline", "slower_than_loop_baseline")
                         if key in old})
-    if args.stream_max_sweep:
+    if args.device_offsets:
+        rows = device_offsets(torch, rdst_amd, args)
+        summary = {key: summary[key] for key in ("tool", "device", "reps", "limits_u32", "limits_u64")}
+        summary["device_offsets"] = rows
+        for mode in ("async", "wait"):                                      # by the unrounded medians
+            summary[f"slower_than_baseline_{mode}"] = [[r["shape"], r["keys"], r["index"], r["ranks"], r[f"baseline_over_{mode}"]] for r in rows
+                                                       if r["baseline_copy_sync_host_entry"]["ms"] < r[mode]["ms"]]
+    elif args.stream_max_sweep:
         summary["stream_max_sweep"] = stream_max_sweep(torch, rdst_amd, args)
         summary["crossing"] = {}
         for kind in ("u32", "u64"):
@@ -233,7 +295,7 @@ def main():
         summary["table"] = table(torch, rdst_amd, args)
     if "table" in summary:
         summary["slower_than_sort_baseline"], summary["slower_than_loop_baseline"] = slower_lists(summary["table"])
-    print(json.dumps({key: v for key, v in summary.items() if key not in ("stream_max_sweep", "table")}))
+    print(json.dumps({key: v for key, v in summary.items() if key not in ("stream_max_sweep", "table", "device_offsets")}))
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "w") as f:
