@@ -498,6 +498,28 @@ void select_segments_device_offsets(const T* dev_keys, std::size_t len, const Of
                                                           static_cast<std::uint32_t>(RadixKey<T>::LEVELS), largest ? RDST_TOPK_LARGEST : 0u, stream));
 }
 
+// Runs of bit-identical keys (rdst_hip_runs_device): `v.dedup()` on the device, and the CSR table of the groups of sorted
+// keys.  dev_out_keys: out_capacity keys or nullptr; dev_out_starts: out_capacity + 1 borders of type Off (a 4- or 8-byte
+// unsigned integer) or nullptr; dev_n_runs: one Off, the true number of runs R.  starts[0 .. R] is a table every
+// *_device_offsets entry takes (starts[R] = the length); with pad_starts the slots behind R hold the length too, so that
+// n_segments = out_capacity needs no look at R.  dev_len: nullptr, or the length in device memory (a 4- or 8-byte unsigned
+// integer, read in stream order).  More runs than out_capacity (> 0): the first out_capacity are complete and bit 0x40 of the
+// device error word is raised; out_capacity == 0 only counts.  Fully asynchronous: no copy to the host, no wait.  dev_scratch:
+// 256-byte aligned, at least runs_scratch_bytes<T>(len) bytes.
+template <typename T>
+std::size_t runs_scratch_bytes(std::size_t len) {
+    return rdst_hip_runs_scratch_bytes(len, sizeof(T));
+}
+template <typename T, typename Off, typename Len = std::uint64_t>
+void runs_device(const T* dev_keys, std::size_t len, T* dev_out_keys, Off* dev_out_starts, Off* dev_n_runs, std::size_t out_capacity, void* dev_scratch,
+                 std::size_t scratch_bytes, bool pad_starts = false, const Len* dev_len = nullptr, void* stream = nullptr) {
+    static_assert(std::is_unsigned<Off>::value && (sizeof(Off) == 4 || sizeof(Off) == 8), "borders are 4- or 8-byte unsigned integers");
+    static_assert(std::is_unsigned<Len>::value && (sizeof(Len) == 4 || sizeof(Len) == 8), "a device-resident length is a 4- or 8-byte unsigned integer");
+    detail::check(rdst_hip_runs_device(dev_keys, len, dev_len, sizeof(Len), dev_out_keys, dev_out_starts, dev_n_runs, sizeof(Off), out_capacity, dev_scratch,
+                                       scratch_bytes, sizeof(T), RadixKey<T>::kind, static_cast<std::uint32_t>(RadixKey<T>::LEVELS),
+                                       pad_starts ? RDST_RUNS_PAD_STARTS : 0u, stream));
+}
+
 // DEVICE-resident [u8; N] rows (src/radix_key_impl.rs:78-85) and DEVICE-resident structs ordered by a described key
 // (src/radix_key.rs; examples/impl_radix_key.rs:32-56), in place and with no host involvement
 // (rdst_hip_sort_bytes_device_nowait, rdst_hip_sort_records_by_fields_device_nowait): N, or the sum of the fields' widths,

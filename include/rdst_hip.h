@@ -731,6 +731,63 @@ int rdst_hip_select_segments_device_offsets(const void* dev_keys, uint64_t len,
 uint64_t rdst_hip_select_segments_device_offsets_scratch_bytes(uint64_t n_segments, uint64_t far_capacity, uint64_t n_ranks,
                                                                uint32_t elem_bytes, uint32_t index_bytes);
 
+/* Runs of equal keys: the device twin of `v.radix_sort_unstable(); v.dedup();` and of "where does each key's group begin".
+ * Call m the length: `len`, or, with a non-NULL dev_len, the unsigned integer of len_bytes (4 or 8) bytes it points to, read
+ * only and in stream order exactly as rdst_hip_sort_device_devlen reads it.  A run is a maximal stretch of consecutive
+ * elements of dev_keys[0 .. m) with BIT-IDENTICAL keys: -0.0 and +0.0, and two NaN payloads, are different keys; identical NaN
+ * bits are one key.  The input need not be sorted (Vec::dedup, unique_consecutive); on a sorted input the runs are the
+ * distinct keys with their multiplicities.  Call R the number of runs.  Written, bit for bit and deterministic:
+ *   - dev_n_runs[0] = R, the true number, whatever out_capacity is (one unsigned integer of offset_bytes bytes);
+ *   - for r < min(R, out_capacity): dev_out_keys[r] = the key of run r in its original bits, dev_out_starts[r] = the position
+ *     of its first element (offset_bytes bytes each); either pointer may be NULL, which skips that output;
+ *   - R <= out_capacity: dev_out_starts[R] = m, so starts[0 .. R] is a CSR table of the groups, valid for every
+ *     *_device_offsets entry;
+ *   - RDST_RUNS_PAD_STARTS and R <= out_capacity: dev_out_starts[r] = m for every r in (R, out_capacity] as well — a second
+ *     launch sized by out_capacity, A WRITE OF out_capacity OFFSETS —, so that a caller passes n_segments = out_capacity to a
+ *     segmented entry without ever reading R: the surplus segments are empty.  Without the flag nothing behind slot R is
+ *     written;
+ *   - R > out_capacity > 0: the first out_capacity runs are complete — keys, starts, and starts[out_capacity] = the end of
+ *     the last kept run —, nothing is padded, and the bit of value 64 (0x40) of the device error word is set:
+ *     rdst_hip_device_status returns RDST_ERR_DEVICE once;
+ *   - out_capacity == 0: the counting call.  Only dev_n_runs is written, the output pointers may be NULL, no error bit;
+ *   - m == 0: R = 0 and starts[0] = 0;
+ *   - m > len: NOTHING at all is written and bit 0x20 is set, as the _devlen sorts do.
+ * The input is never written.  Nothing is touched outside [0, out_capacity) of the keys, [0, out_capacity] of the starts, the
+ * one n_runs word and [0, rdst_hip_runs_scratch_bytes(len, elem_bytes)) of the scratch.  Every width of rdst_hip_sort_device
+ * (1, 2, 4, 8, 16 bytes) and every kind; 4-byte offsets are legal for every supported len.
+ * ASYNCHRONOUS on `stream` for every input: one pass over the keys (a chained scan with decoupled look-back),
+ * no copy to or from the host, no wait on an event or on the stream, no library workspace; the caller's scratch (256-byte
+ * aligned) holds everything, needs no clearing — the library clears it itself in stream order — and is reusable by the next
+ * call on the same stream.  THE ONLY DATA-DEPENDENT OUTCOMES are the two error bits above.
+ * Arguments, checked in this order before any device work:
+ *   1. the key arguments as rdst_hip_sort_device checks them (its codes and messages);
+ *   2. RDST_KEY_BYTES_BE -> RDST_ERR_UNSUPPORTED;   3. len >= 2^32 -> RDST_ERR_UNSUPPORTED (positions are u32 in the kernels);
+ *   4. unknown flag bits -> RDST_ERR_ARG;
+ *   5. with dev_len: len_bytes not 4 or 8 -> RDST_ERR_ARG, misaligned -> RDST_ERR_ALIGN;
+ *   6. offset_bytes not 4 or 8 -> RDST_ERR_ARG;
+ *   7. NULL dev_n_runs -> RDST_ERR_ARG, misaligned -> RDST_ERR_ALIGN, inside the input or on the length -> RDST_ERR_ARG;
+ *   8. with out_capacity > 0: a misaligned output -> RDST_ERR_ALIGN; outputs that overlap the input, the length or each other
+ *      (dev_n_runs included) -> RDST_ERR_ARG; RDST_RUNS_PAD_STARTS with NULL dev_out_starts -> RDST_ERR_ARG;
+ *   9. NULL scratch -> RDST_ERR_ARG, not 256-byte aligned -> RDST_ERR_ALIGN, scratch_bytes below
+ *      rdst_hip_runs_scratch_bytes(len, elem_bytes) -> RDST_ERR_ARG, those bytes overlapping the input, the length, dev_n_runs
+ *      or an output -> RDST_ERR_ARG.
+ * len == 0 still does the device writes of m == 0. */
+#define RDST_RUNS_PAD_STARTS 1u
+int rdst_hip_runs_device(const void* dev_keys, uint64_t len,
+                         const void* dev_len, uint32_t len_bytes,
+                         void* dev_out_keys, void* dev_out_starts,
+                         void* dev_n_runs, uint32_t offset_bytes,
+                         uint64_t out_capacity,
+                         void* dev_scratch, uint64_t scratch_bytes,
+                         uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels,
+                         uint32_t flags, void* stream);
+/* The scratch of the call above: a 256-byte header and one 64-bit status word per tile of `len` keys (rdst_hip_runs_limits).  Pure, monotone in len.
+ * 0 for len >= 2^32 and unsupported widths. */
+uint64_t rdst_hip_runs_scratch_bytes(uint64_t len, uint32_t elem_bytes);
+/* out[0] = keys per tile, out[1] = status words one look-back round trip fetches (tests place their inputs by them).  Pure.
+ * Unsupported widths: RDST_ERR_UNSUPPORTED. */
+int rdst_hip_runs_limits(uint32_t elem_bytes, uint32_t out[2]);
+
 /* [u8; N] rows (N = n_bytes in 1..RDST_BYTES_MAX_N), device-resident, sorted IN PLACE in lexicographic order
  * (src/radix_key_impl.rs:78-85).  No alignment requirement on dev_rows.  dev_scratch: at least
  * rdst_hip_sort_bytes_scratch_bytes(len, n_bytes) bytes, 256-byte aligned.  len <= 1: no-op.

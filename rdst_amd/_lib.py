@@ -22,6 +22,7 @@ RDST_STAGE_SEGMENTS_TILED = 14   # rdst_stage: the tiled route of the nowait ent
 RDST_STAGE_TOPK = 15       # rdst_stage: one select level of the partial sort (level in bits 8..15; 0xFF: the collection pass)
 RDST_STAGE_SELECT = 16     # rdst_stage: one level of one round of the order statistics (level in bits 8..15; 0xFF: the collection pass)
 RDST_TOPK_LARGEST = 1      # rdst_hip_topk_device flags: the k largest, in descending order
+RDST_RUNS_PAD_STARTS = 1   # rdst_hip_runs_device flags: fill the starts behind slot R with m, up to the capacity
 RDST_RANK_LOWER, RDST_RANK_HIGHER, RDST_RANK_NEAREST = 0, 1, 2   # rdst_rank_spec.mode: how a quantile's virtual index is rounded
 
 
@@ -96,6 +97,9 @@ def _signatures():
         "rdst_hip_debug_topk_segments_plan_device": (ci, [vp, u32, u64, u64, u64, u32, u32, u32, vp, u64, items, u64, u64p, u64p, u32p, vp]),
         "rdst_hip_select_segments_device_offsets": (ci, [vp, u64, vp, u32, u64, specs, u64, vp, vp, u32, vp, u64, u64, u32, ci, u32, u32, vp]),
         "rdst_hip_select_segments_device_offsets_scratch_bytes": (u64, [u64, u64, u64, u32, u32]),
+        "rdst_hip_runs_device": (ci, [vp, u64, vp, u32, vp, vp, vp, u32, u64, vp, u64, u32, ci, u32, u32, vp]),
+        "rdst_hip_runs_scratch_bytes": (u64, [u64, u32]),
+        "rdst_hip_runs_limits": (ci, [u32, u32p]),
         "rdst_hip_sort_segments_device": (ci, [vp, vp, u64, u64, u64p, u64, u32, ci, u32, vp]),
         "rdst_hip_sort_segments_pairs_device": (ci, [vp, vp, vp, vp, u64, u64, u64p, u64, u32, ci, u32, u32, vp]),
         "rdst_hip_sort_segments_limits": (ci, [u32, u32, u32p]),

@@ -17,6 +17,24 @@ struct KeyMap {  // order-preserving map as two xor masks (src/radix_key_impl.rs
     u128 pos;  // xor applied when it is clear
 };
 
+// look-back status word: top two bits state, the rest value (u32 for n < 2^30, u64 above)
+constexpr uint32_t ST_EMPTY = 0, ST_AGG = 1, ST_INCL = 2;
+template <typename S> struct StatusWord {
+    static constexpr int SHIFT = sizeof(S) * 8 - 2;
+    static constexpr S MASK = (S(1) << SHIFT) - 1;
+};
+// bounded spins: s_sleep(2) is ~128 clocks; 1<<22 polls is seconds, never reached in a healthy run
+constexpr uint32_t SPIN_LIMIT = 1u << 22;
+
+template <typename S>
+__device__ __forceinline__ S ld_relaxed(const S* p) {
+    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+template <typename S>
+__device__ __forceinline__ void st_relaxed(S* p, S v) {
+    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 template <typename K>
 __device__ __forceinline__ K map_key(K k, K neg, K pos) {
     constexpr int W = sizeof(K) * 8;

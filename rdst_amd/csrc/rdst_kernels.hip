@@ -49,14 +49,7 @@ namespace {
 constexpr int RADIX = 256;
 constexpr int MAX_LEVELS = 16;
 
-// look-back status word: top two bits state, the rest value (u32 for n < 2^30, u64 above)
-constexpr uint32_t ST_EMPTY = 0, ST_AGG = 1, ST_INCL = 2;
-template <typename S> struct StatusWord {
-    static constexpr int SHIFT = sizeof(S) * 8 - 2;
-    static constexpr S MASK = (S(1) << SHIFT) - 1;
-};
-// bounded spins: s_sleep(2) is ~128 clocks; 1<<22 polls is seconds, never reached in a healthy run
-constexpr uint32_t SPIN_LIMIT = 1u << 22;
+// ST_EMPTY / ST_AGG / ST_INCL, StatusWord, SPIN_LIMIT: rdst_device.h
 
 #ifndef RDST_PRIO_LOAD
 #define RDST_PRIO_LOAD 2
@@ -167,16 +160,8 @@ struct LevelChains {  // written by K2 for every executed level, read by K3's ti
     uint32_t pad[3];
 };
 
-// u128, KeyMap, map_key, unmap_key, digit_of: rdst_device.h
+// u128, KeyMap, map_key, unmap_key, digit_of, ld_relaxed, st_relaxed: rdst_device.h
 
-template <typename S>
-__device__ __forceinline__ S ld_relaxed(const S* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-template <typename S>
-__device__ __forceinline__ void st_relaxed(S* p, S v) {
-    __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
 // Four status words in one write-through store.  A scalar (4-byte) sc1 store is a fabric write of its
 // own and costs about six times a 16-byte one per byte (MI355X_MICROARCH.md); the protocol needs every
 // WORD to arrive whole, which a naturally aligned dword inside a 16-byte store does.
@@ -5617,8 +5602,8 @@ int read_device_error(DeviceState& D, hipStream_t s) {
         const uint32_t word = *D.host_err;
         RDST_HIP_TRY(hipMemsetAsync(D.err_dev, 0, sizeof(uint32_t), s));  // reported once: the next check starts clean
         RDST_HIP_TRY(hipStreamSynchronize(s));
-        char b[448];
-        snprintf(b, sizeof b, "device error word = 0x%x (1 = look-back spin bound expired, 2 = scatter destination out of range, 4 = hybrid-route bucket larger than a tile, 8 = [u8; N] route: a row index or run out of range, 16 = segmented sort: offsets table decreasing, past len, or a segment beyond block_max without tmp, 32 = device-length sort: the length read from device memory is past the capacity)", word);
+        char b[576];
+        snprintf(b, sizeof b, "device error word = 0x%x (1 = look-back spin bound expired, 2 = scatter destination out of range, 4 = hybrid-route bucket larger than a tile, 8 = [u8; N] route: a row index or run out of range, 16 = segmented sort: offsets table decreasing, past len, or a segment beyond block_max without tmp, 32 = device-length sort: the length read from device memory is past the capacity, 64 = runs: more runs than out_capacity)", word);
         return fail(RDST_ERR_DEVICE, b);
     }
     return RDST_OK;

@@ -836,6 +836,90 @@ def select_segments_device_offsets_tensor(keys, offsets, ranks=None, quantiles=N
     return out_keys, out_index
 
 
+def runs_limits(dtype):
+    """``rdst_hip_runs_limits``: (keys per tile, status words per look-back round trip) of :func:`runs_device_tensor` for keys
+    of ``dtype`` (a numpy / torch dtype or its name, ``"u128"`` / ``"i128"``)."""
+    _kind, nbytes, _levels = key_info(dtype)
+    out = (ctypes.c_uint32 * 2)()
+    _lib.check(_lib.load().rdst_hip_runs_limits(nbytes, out))
+    return int(out[0]), int(out[1])
+
+
+def runs_scratch_bytes(n, dtype):
+    """``rdst_hip_runs_scratch_bytes``: bytes of scratch :func:`runs_device_tensor` needs for ``n`` keys of ``dtype`` (0 for
+    2^32 keys and more)."""
+    _kind, nbytes, _levels = key_info(dtype)
+    return int(_lib.load().rdst_hip_runs_scratch_bytes(int(n), nbytes))
+
+
+def runs_device_tensor(keys, length=None, capacity=None, starts="int64", pad=False, scratch=None, check=True, key=None, out=None):
+    """``rdst_hip_runs_device``: the runs of bit-identical keys of the 1-D contiguous HIP tensor ``keys`` (``key="u128"/"i128"``:
+    shape (n, 2)) — ``Vec::dedup`` / ``unique_consecutive`` on the device; on sorted keys, the distinct keys and where each
+    one's group begins.  Returns ``(run_keys, starts, n_runs)``: the key of every run (``capacity`` entries; the capacity
+    defaults to ``len(keys)``), the position of its first element (``capacity + 1`` entries of dtype ``starts``:
+    ``torch.int64``, ``torch.int32`` or their names; ``None`` skips the table) and the number of
+    runs R as a one-element device tensor that this function never reads.  ``starts[:R + 1]`` is a CSR table of the groups
+    (``starts[R]`` = the length) that every ``*_device_offsets_tensor`` wrapper takes; with ``pad`` the slots behind R hold
+    the length too, so ``starts`` as a whole is a table of ``capacity`` segments whose surplus ones are empty — nobody has to
+    read R.  Slots behind R are otherwise left as they were.  ``length``: an optional one-element device tensor (see
+    :func:`sort_device_devlen_tensor`): only the first ``m`` keys are looked at.  More runs than ``capacity`` (> 0) keeps the
+    first ``capacity`` complete, stores the true R and raises from :func:`device_status` (bit 64); ``capacity=0`` only
+    counts.  ``out``: optional ``(run_keys, starts, n_runs)`` tensors to write into; a ``None`` in place of
+    the first or the second skips that output (the call is then keys-only, starts-only or, with both, a count), one in place
+    of the third is allocated.
+    ``scratch``: optional uint8 tensor of at least :func:`runs_scratch_bytes` bytes, 256-byte aligned.  ``keys`` is not
+    modified.  The call only enqueues work on the tensor's current stream; ``check=False`` makes no blocking call at all."""
+    import torch
+    kind, nbytes, levels, n, per_key = _keys_operand("runs_device_tensor", keys, key)
+    devlen = _device_length(_WHOLE if length is None else length, keys) or (None, 0)
+    capacity = n if capacity is None else int(capacity)
+    if capacity < 0:
+        raise ValueError("capacity must not be negative")
+    if starts is not None:
+        starts = getattr(torch, starts) if isinstance(starts, str) else starts
+        if starts not in (torch.int32, torch.int64):
+            raise ValueError("starts must be None, torch.int32 or torch.int64")
+    o_keys, o_starts, o_count = out if out is not None else (None, None, None)
+    if out is not None and o_starts is None:                                    # either way of skipping the table
+        starts = None
+    if starts is None:
+        o_starts = None
+    if pad and starts is None:
+        raise ValueError("pad fills the starts: it needs them")
+    if starts is not None:
+        off_dtype = starts
+    else:                                                                       # no table: the caller's n_runs decides, else int64
+        off_dtype = o_count.dtype if o_count is not None and o_count.dtype in (torch.int32, torch.int64) else torch.int64
+    if out is None:
+        o_keys = torch.empty((capacity, 2) if _wide(key) else (capacity,), dtype=keys.dtype, device=keys.device)
+    if starts is not None and o_starts is None:
+        o_starts = torch.empty(capacity + 1, dtype=off_dtype, device=keys.device)
+    if o_count is None:
+        o_count = torch.empty(1, dtype=off_dtype, device=keys.device)
+    for t, dtype, need, what in ((o_keys, keys.dtype, capacity * per_key, "run_keys"), (o_starts, off_dtype, capacity + 1, "starts"), (o_count, off_dtype, 1, "n_runs")):
+        if t is not None and (t.dtype != dtype or t.device != keys.device or not t.is_contiguous() or t.numel() < need):
+            raise ValueError(f"out: {what} must be a contiguous {dtype} tensor on the keys' device with at least {need} elements")
+    need = int(_lib.load().rdst_hip_runs_scratch_bytes(n, nbytes))
+    scratch, sbytes = _scratch(scratch, need, keys.device)
+    _call(keys, check, "rdst_hip_runs_device", _ptr(keys, empty_is_null=True), n, *devlen, _ptr(o_keys), _ptr(o_starts), _ptr(o_count), o_count.element_size(),
+          capacity, _ptr(scratch), sbytes, nbytes, kind, levels, _lib.RDST_RUNS_PAD_STARTS if pad else 0)
+    return o_keys, o_starts, o_count
+
+
+def unique_device_tensor(keys, counts=False, scratch=None, check=True, key=None):
+    """Sort, then dedup, on the device: a clone of ``keys``, :func:`sort_device_tensor` on it, then
+    :func:`runs_device_tensor`.  Returns ``(unique_keys, n_unique)`` — ``len(keys)`` slots of which the first R hold the distinct
+    keys in the sort's order, and R as a one-element device tensor —, with ``counts`` ``(unique_keys, counts, n_unique)``:
+    the multiplicity of every distinct key, 0 in the slots behind R (``starts[1:] - starts[:-1]`` of the padded table, a torch
+    expression).  ``keys`` is not modified.  Nothing is copied to the host; ``check=False`` makes no blocking call."""
+    work = keys.clone()
+    sort_device_tensor(work, check=False, key=key)
+    uniq, starts, count = runs_device_tensor(work, starts="int64" if counts else None, pad=counts, scratch=scratch, check=check, key=key)
+    if not counts:
+        return uniq, count
+    return uniq, starts[1:] - starts[:-1], count
+
+
 def sort_segments_device_offsets_tensor(keys, offsets, tmp=None, values=None, tmp_values=None, scratch=None, check=True, key=None):
     """``rdst_hip_sort_segments_device_offsets`` (with ``values``: ``rdst_hip_sort_segments_pairs_device_offsets``):
     :func:`sort_segments_device_tensor` for a table of borders that lives on the device — a CSR row pointer, a ``cumsum`` of
