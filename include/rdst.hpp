@@ -520,6 +520,26 @@ void runs_device(const T* dev_keys, std::size_t len, T* dev_out_keys, Off* dev_o
                                        pad_starts ? RDST_RUNS_PAD_STARTS : 0u, stream));
 }
 
+// Binary search (rdst_hip_search_device): `partition_point` for many needles at once.  For every i < n_needles, lower[i] = the
+// number of keys of dev_sorted[0 .. m) that order strictly before dev_needles[i] and upper[i] = the number that order before
+// or equal it, in the sort's order (the mapped bits: -0.0 < +0.0, NaNs by their bits); Off is a 4- or 8-byte unsigned
+// integer, either output may be nullptr.  m is len, or the value dev_len points to (a 4- or 8-byte unsigned integer in
+// device memory, read in stream order; past len: nothing is written and bit 0x20 of the device error word is raised).  The
+// haystack and the needles are not written and may overlap.  Fully asynchronous: no copy to the host, no wait.  dev_scratch:
+// 256-byte aligned, at least search_scratch_bytes<T>(len, n_needles) bytes.
+template <typename T>
+std::size_t search_scratch_bytes(std::size_t len, std::size_t n_needles) {
+    return rdst_hip_search_scratch_bytes(len, n_needles, sizeof(T));
+}
+template <typename T, typename Off, typename Len = std::uint64_t>
+void search_device(const T* dev_sorted, std::size_t len, const T* dev_needles, std::size_t n_needles, Off* dev_out_lower, Off* dev_out_upper,
+                   void* dev_scratch, std::size_t scratch_bytes, const Len* dev_len = nullptr, void* stream = nullptr) {
+    static_assert(std::is_unsigned<Off>::value && (sizeof(Off) == 4 || sizeof(Off) == 8), "positions are 4- or 8-byte unsigned integers");
+    static_assert(std::is_unsigned<Len>::value && (sizeof(Len) == 4 || sizeof(Len) == 8), "a device-resident length is a 4- or 8-byte unsigned integer");
+    detail::check(rdst_hip_search_device(dev_sorted, len, dev_len, sizeof(Len), dev_needles, n_needles, dev_out_lower, dev_out_upper, sizeof(Off), dev_scratch,
+                                         scratch_bytes, sizeof(T), RadixKey<T>::kind, static_cast<std::uint32_t>(RadixKey<T>::LEVELS), 0u, stream));
+}
+
 // DEVICE-resident [u8; N] rows (src/radix_key_impl.rs:78-85) and DEVICE-resident structs ordered by a described key
 // (src/radix_key.rs; examples/impl_radix_key.rs:32-56), in place and with no host involvement
 // (rdst_hip_sort_bytes_device_nowait, rdst_hip_sort_records_by_fields_device_nowait): N, or the sum of the fields' widths,

@@ -788,6 +788,63 @@ uint64_t rdst_hip_runs_scratch_bytes(uint64_t len, uint32_t elem_bytes);
  * Unsupported widths: RDST_ERR_UNSUPPORTED. */
 int rdst_hip_runs_limits(uint32_t elem_bytes, uint32_t out[2]);
 
+/* Binary search: the device twin of `binary_search` / `partition_point` on a sorted slice and of numpy.searchsorted — where
+ * each of n_needles keys falls in a sorted array.  Call m the length of the haystack: `len`, or, with a non-NULL dev_len, the
+ * unsigned integer of len_bytes (4 or 8) bytes it points to, read only and in stream order exactly as rdst_hip_runs_device
+ * reads its length.  THE ORDER IS THE SORT'S: key a comes before key b when map_key(a) < map_key(b) for `kind`; floats go
+ * -NaN < -inf < ... < -0.0 < +0.0 < ... < +inf < +NaN, NaNs by their bits, and two keys are equal only when they are
+ * BIT-IDENTICAL (the equality of rdst_hip_runs_device).  Precondition: dev_sorted[0 .. m) is in that order, as every sort
+ * entry leaves it.  Written for every i < n_needles, bit for bit and deterministic, as unsigned integers of offset_bytes
+ * (4 or 8) bytes:
+ *   - dev_out_lower[i] = the number of keys of dev_sorted[0 .. m) that order strictly before dev_needles[i]
+ *     (partition_point(|x| x < q), side="left");
+ *   - dev_out_upper[i] = the number that order before it or equal it (side="right");
+ *   either pointer may be NULL, which skips that output.  upper - lower is the multiplicity of the needle in the haystack,
+ *   lower == upper means "not present".
+ *   - m == 0: every output is 0;
+ *   - n_needles == 0: RDST_OK after the argument checks, no device work;
+ *   - m > len: NOTHING at all is written and bit 0x20 of the device error word is set, as the _devlen sorts and
+ *     rdst_hip_runs_device do.  THE ONLY DATA-DEPENDENT OUTCOME is that bit.
+ * AN UNSORTED HAYSTACK costs correctness only, never safety: every output is some value in [0, m], nothing outside the buffers
+ * is read or written, and every loop has a bound that does not depend on the data's order.
+ * The haystack and the needles are never written and may overlap each other in any way (an array searched for its own keys
+ * gives each element's group start and end); the outputs and the scratch may overlap nothing else.  Every width of
+ * rdst_hip_sort_device (1, 2, 4, 8, 16 bytes) and every kind except RDST_KEY_BYTES_BE; len and n_needles below 2^32.
+ * ASYNCHRONOUS on `stream` for every input: two launches (a splitter table, then one workgroup per tile of needles that
+ * searches a staged window in LDS or the table and one gap of the haystack), no copy to or from the host, no
+ * wait on an event or on the stream, no library workspace, no allocation; the caller's scratch (256-byte aligned) holds
+ * everything, needs no clearing — the library initialises it itself in stream order — and is reusable by the next call on
+ * the same stream.
+ * Arguments, checked in this order before any device work:
+ *   1. the key arguments of the haystack as rdst_hip_sort_device checks them (its codes and messages);
+ *   2. RDST_KEY_BYTES_BE -> RDST_ERR_UNSUPPORTED;   3. len or n_needles >= 2^32 -> RDST_ERR_UNSUPPORTED (positions are u32 in
+ *      the kernels);
+ *   4. any flag bit -> RDST_ERR_ARG (none is defined yet);
+ *   5. with dev_len: len_bytes not 4 or 8 -> RDST_ERR_ARG, misaligned -> RDST_ERR_ALIGN;
+ *   6. NULL dev_needles with n_needles > 0 -> RDST_ERR_ARG, not aligned to elem_bytes -> RDST_ERR_ALIGN;
+ *   7. offset_bytes not 4 or 8 -> RDST_ERR_ARG;
+ *   8. both outputs NULL -> RDST_ERR_ARG; a misaligned output -> RDST_ERR_ALIGN; an output that overlaps the haystack, the
+ *      needles, the length or the other output -> RDST_ERR_ARG;
+ *   9. NULL scratch -> RDST_ERR_ARG, not 256-byte aligned -> RDST_ERR_ALIGN, scratch_bytes below
+ *      rdst_hip_search_scratch_bytes(len, n_needles, elem_bytes) -> RDST_ERR_ARG, those bytes overlapping the haystack, the
+ *      needles, the length or an output -> RDST_ERR_ARG. */
+int rdst_hip_search_device(const void* dev_sorted, uint64_t len,
+                           const void* dev_len, uint32_t len_bytes,
+                           const void* dev_needles, uint64_t n_needles,
+                           void* dev_out_lower, void* dev_out_upper, uint32_t offset_bytes,
+                           void* dev_scratch, uint64_t scratch_bytes,
+                           uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels,
+                           uint32_t flags, void* stream);
+/* The scratch of the call above: a 256-byte header and the splitter table (rdst_hip_search_limits), the same for every
+ * supported length.  Pure, monotone in every argument.  0 for len or n_needles >= 2^32 and unsupported widths. */
+uint64_t rdst_hip_search_scratch_bytes(uint64_t len, uint64_t n_needles, uint32_t elem_bytes);
+/* out[0] = needles per workgroup tile, out[1] = splitters, out[2] = the most keys of the haystack a workgroup stages in LDS
+ * (tests place their inputs by them).  Pure.  Unsupported widths: RDST_ERR_UNSUPPORTED. */
+int rdst_hip_search_limits(uint32_t elem_bytes, uint32_t out[3]);
+/* Test hook, BLOCKING on `stream`: the scratch header of the last rdst_hip_search_device call there.  out[0] = m,
+ * out[1] = tiles that took the staged path, out[2] = tiles that took the table path, out[3] = 1 if m was past len. */
+int rdst_hip_debug_search_state(const void* dev_scratch, void* stream, uint64_t out[4]);
+
 /* [u8; N] rows (N = n_bytes in 1..RDST_BYTES_MAX_N), device-resident, sorted IN PLACE in lexicographic order
  * (src/radix_key_impl.rs:78-85).  No alignment requirement on dev_rows.  dev_scratch: at least
  * rdst_hip_sort_bytes_scratch_bytes(len, n_bytes) bytes, 256-byte aligned.  len <= 1: no-op.

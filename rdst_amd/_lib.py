@@ -100,6 +100,10 @@ def _signatures():
         "rdst_hip_runs_device": (ci, [vp, u64, vp, u32, vp, vp, vp, u32, u64, vp, u64, u32, ci, u32, u32, vp]),
         "rdst_hip_runs_scratch_bytes": (u64, [u64, u32]),
         "rdst_hip_runs_limits": (ci, [u32, u32p]),
+        "rdst_hip_search_device": (ci, [vp, u64, vp, u32, vp, u64, vp, vp, u32, vp, u64, u32, ci, u32, u32, vp]),
+        "rdst_hip_search_scratch_bytes": (u64, [u64, u64, u32]),
+        "rdst_hip_search_limits": (ci, [u32, u32p]),
+        "rdst_hip_debug_search_state": (ci, [vp, vp, u64p]),
         "rdst_hip_sort_segments_device": (ci, [vp, vp, u64, u64, u64p, u64, u32, ci, u32, vp]),
         "rdst_hip_sort_segments_pairs_device": (ci, [vp, vp, vp, vp, u64, u64, u64p, u64, u32, ci, u32, u32, vp]),
         "rdst_hip_sort_segments_limits": (ci, [u32, u32, u32p]),

@@ -14,12 +14,14 @@ SOURCES = [os.path.join(HERE, "csrc", "rdst_kernels.hip"), os.path.join(HERE, "c
            os.path.join(HERE, "csrc", "rdst_select_segments.hip"), os.path.join(HERE, "csrc", "rdst_select_segments_offsets.hip"),
            os.path.join(HERE, "csrc", "rdst_select_segments_offsets.cpp"),
            os.path.join(HERE, "csrc", "rdst_runs.hip"), os.path.join(HERE, "csrc", "rdst_runs.cpp"),
+           os.path.join(HERE, "csrc", "rdst_search.hip"), os.path.join(HERE, "csrc", "rdst_search.cpp"),
            os.path.join(HERE, "csrc", "rdst_tuner.cpp"),
            os.path.join(HERE, "csrc", "rdst_regions.cpp"), os.path.join(HERE, "csrc", "rdst_segments.cpp")]
 HEADERS = [os.path.join(ROOT, "include", "rdst_hip.h"), os.path.join(HERE, "csrc", "rdst_internal.h"),
            os.path.join(HERE, "csrc", "rdst_device.h"), os.path.join(HERE, "csrc", "rdst_segments_layout.h"),
            os.path.join(HERE, "csrc", "rdst_stream.h"), os.path.join(HERE, "csrc", "rdst_segments_device.h"),
-           os.path.join(HERE, "csrc", "rdst_rank_rule.h"), os.path.join(HERE, "csrc", "rdst_runs_layout.h")]
+           os.path.join(HERE, "csrc", "rdst_rank_rule.h"), os.path.join(HERE, "csrc", "rdst_runs_layout.h"),
+           os.path.join(HERE, "csrc", "rdst_search_layout.h")]
 OUT = os.path.join(HERE, "librdst_hip.so")
 
 

@@ -906,18 +906,92 @@ def runs_device_tensor(keys, length=None, capacity=None, starts="int64", pad=Fal
     return o_keys, o_starts, o_count
 
 
-def unique_device_tensor(keys, counts=False, scratch=None, check=True, key=None):
+def search_limits(dtype):
+    """``rdst_hip_search_limits``: (needles per workgroup tile, splitters, keys a workgroup stages in LDS) of
+    :func:`search_device_tensor` for keys of ``dtype`` (a numpy / torch dtype or its name, ``"u128"`` / ``"i128"``)."""
+    _kind, nbytes, _levels = key_info(dtype)
+    out = (ctypes.c_uint32 * 3)()
+    _lib.check(_lib.load().rdst_hip_search_limits(nbytes, out))
+    return int(out[0]), int(out[1]), int(out[2])
+
+
+def search_scratch_bytes(n, n_needles, dtype):
+    """``rdst_hip_search_scratch_bytes``: bytes of scratch :func:`search_device_tensor` needs for ``n_needles`` needles in ``n``
+    keys of ``dtype`` (0 for 2^32 and more of either)."""
+    _kind, nbytes, _levels = key_info(dtype)
+    return int(_lib.load().rdst_hip_search_scratch_bytes(int(n), int(n_needles), nbytes))
+
+
+def search_state(scratch):
+    """``rdst_hip_debug_search_state`` (test hook, blocking): what the most recent :func:`search_device_tensor` on ``scratch``
+    did — dict with ``m`` (the haystack's length as the device read it), ``staged`` and ``table`` (tiles of needles per path)
+    and ``past`` (1: m was past the capacity)."""
+    import torch
+    out = (ctypes.c_uint64 * 4)()
+    with torch.cuda.device(scratch.device):
+        _lib.check(_lib.load().rdst_hip_debug_search_state(_ptr(scratch), _stream_handle(scratch), out))
+    return {"m": int(out[0]), "staged": int(out[1]), "table": int(out[2]), "past": int(out[3])}
+
+
+def search_device_tensor(sorted_keys, needles, side="left", length=None, positions="int64", scratch=None, check=True, key=None, out=None):
+    """``rdst_hip_search_device``: where each of ``needles`` falls in the sorted 1-D contiguous HIP tensor ``sorted_keys``
+    (``key="u128"/"i128"``: both of shape (n, 2)) — ``numpy.searchsorted`` / ``partition_point`` in THE SORT'S order: the
+    mapped bits, so -0.0 comes before +0.0, every NaN has its place and 16-byte keys are keys.  ``side="left"``: the number of
+    keys strictly before each needle; ``"right"``: before or equal; ``"both"``: the tuple ``(lower, upper)``, whose
+    difference is the needle's multiplicity.  The result has one entry per needle, of dtype ``positions`` (``torch.int64``,
+    ``torch.int32`` or their names).  ``length``: an optional one-element device tensor (see
+    :func:`sort_device_devlen_tensor`): only the first ``m`` keys are the haystack — the R that :func:`runs_device_tensor`
+    has just written, never read by the host; ``m`` past ``len(sorted_keys)`` writes nothing and raises from
+    :func:`device_status` (bit 32).  ``out``: the tensor (for ``"both"``: the two tensors) to write into.  ``scratch``:
+    optional uint8 tensor of at least :func:`search_scratch_bytes` bytes, 256-byte aligned.  Neither input is modified, and
+    they may be the same tensor.  An unsorted haystack gives positions in [0, m] that mean nothing.  The call only enqueues
+    work on the tensor's current stream; ``check=False`` makes no blocking call at all."""
+    import torch
+    kind, nbytes, levels, n, _per_key = _keys_operand("search_device_tensor", sorted_keys, key)
+    _kind, _nbytes, _levels, n_needles, _per = _keys_operand("search_device_tensor", needles, key)
+    if needles.dtype != sorted_keys.dtype or needles.device != sorted_keys.device:
+        raise ValueError("needles must have the dtype and the device of sorted_keys")
+    if side not in ("left", "right", "both"):
+        raise ValueError('side must be "left", "right" or "both"')
+    devlen = _device_length(_WHOLE if length is None else length, sorted_keys) or (None, 0)
+    positions = getattr(torch, positions) if isinstance(positions, str) else positions
+    if positions not in (torch.int32, torch.int64):
+        raise ValueError("positions must be torch.int32 or torch.int64")
+    given = (None, None) if out is None else (tuple(out) if side == "both" else (out, None) if side == "left" else (None, out))
+    if len(given) != 2 or (side == "both" and out is not None and (given[0] is None or given[1] is None)):
+        raise ValueError('out: one tensor, or (lower, upper) for side="both"')
+    want = (side != "right", side != "left")
+    outs = []
+    for t, wanted, what in zip(given, want, ("lower", "upper")):
+        if not wanted:
+            t = None
+        elif t is None:
+            t = torch.empty(n_needles, dtype=positions, device=sorted_keys.device)
+        elif t.dtype != positions or t.device != sorted_keys.device or not t.is_contiguous() or t.numel() < n_needles:
+            raise ValueError(f"out: {what} must be a contiguous {positions} tensor on the keys' device with at least {n_needles} elements")
+        outs.append(t)
+    need = int(_lib.load().rdst_hip_search_scratch_bytes(n, n_needles, nbytes))
+    scratch, sbytes = _scratch(scratch, need, sorted_keys.device)
+    _call(sorted_keys, check, "rdst_hip_search_device", _ptr(sorted_keys, empty_is_null=True), n, *devlen, _ptr(needles, empty_is_null=True), n_needles,
+          _ptr(outs[0]), _ptr(outs[1]), outs[0].element_size() if outs[0] is not None else outs[1].element_size(), _ptr(scratch), sbytes, nbytes, kind, levels, 0)
+    return tuple(outs) if side == "both" else outs[0] if side == "left" else outs[1]
+
+
+def unique_device_tensor(keys, counts=False, scratch=None, check=True, key=None, inverse=False):
     """Sort, then dedup, on the device: a clone of ``keys``, :func:`sort_device_tensor` on it, then
     :func:`runs_device_tensor`.  Returns ``(unique_keys, n_unique)`` — ``len(keys)`` slots of which the first R hold the distinct
     keys in the sort's order, and R as a one-element device tensor —, with ``counts`` ``(unique_keys, counts, n_unique)``:
     the multiplicity of every distinct key, 0 in the slots behind R (``starts[1:] - starts[:-1]`` of the padded table, a torch
-    expression).  ``keys`` is not modified.  Nothing is copied to the host; ``check=False`` makes no blocking call."""
+    expression).  With ``inverse`` the tuple gets one more element at its end: an int64 tensor with
+    ``unique_keys[inverse[i]] == keys[i]`` bit for bit (:func:`search_device_tensor` of the distinct keys for ``keys``, with
+    ``length=n_unique``).  ``keys`` is not modified.  Nothing is copied to the host; ``check=False`` makes no blocking call."""
     work = keys.clone()
     sort_device_tensor(work, check=False, key=key)
-    uniq, starts, count = runs_device_tensor(work, starts="int64" if counts else None, pad=counts, scratch=scratch, check=check, key=key)
-    if not counts:
-        return uniq, count
-    return uniq, starts[1:] - starts[:-1], count
+    uniq, starts, count = runs_device_tensor(work, starts="int64" if counts else None, pad=counts, scratch=scratch, check=check and not inverse, key=key)
+    result = (uniq, starts[1:] - starts[:-1], count) if counts else (uniq, count)
+    if not inverse:
+        return result
+    return result + (search_device_tensor(uniq, keys, length=count, check=check, key=key),)
 
 
 def sort_segments_device_offsets_tensor(keys, offsets, tmp=None, values=None, tmp_values=None, scratch=None, check=True, key=None):
