@@ -10,9 +10,8 @@ SOURCES = [os.path.join(HERE, "csrc", "rdst_kernels.hip"), os.path.join(HERE, "c
            os.path.join(HERE, "csrc", "rdst_segments.hip"), os.path.join(HERE, "csrc", "rdst_topk.hip"),
            os.path.join(HERE, "csrc", "rdst_select.hip"),
            os.path.join(HERE, "csrc", "rdst_topk_segments.hip"), os.path.join(HERE, "csrc", "rdst_topk_segments_offsets.hip"),
-           os.path.join(HERE, "csrc", "rdst_topk_segments_offsets.cpp"),
            os.path.join(HERE, "csrc", "rdst_select_segments.hip"), os.path.join(HERE, "csrc", "rdst_select_segments_offsets.hip"),
-           os.path.join(HERE, "csrc", "rdst_select_segments_offsets.cpp"),
+           os.path.join(HERE, "csrc", "rdst_rank_args.cpp"),
            os.path.join(HERE, "csrc", "rdst_runs.hip"), os.path.join(HERE, "csrc", "rdst_runs.cpp"),
            os.path.join(HERE, "csrc", "rdst_search.hip"), os.path.join(HERE, "csrc", "rdst_search.cpp"),
            os.path.join(HERE, "csrc", "rdst_tuner.cpp"),
@@ -21,7 +20,8 @@ HEADERS = [os.path.join(ROOT, "include", "rdst_hip.h"), os.path.join(HERE, "csrc
            os.path.join(HERE, "csrc", "rdst_device.h"), os.path.join(HERE, "csrc", "rdst_segments_layout.h"),
            os.path.join(HERE, "csrc", "rdst_stream.h"), os.path.join(HERE, "csrc", "rdst_segments_device.h"),
            os.path.join(HERE, "csrc", "rdst_rank_rule.h"), os.path.join(HERE, "csrc", "rdst_runs_layout.h"),
-           os.path.join(HERE, "csrc", "rdst_search_layout.h")]
+           os.path.join(HERE, "csrc", "rdst_search_layout.h"), os.path.join(HERE, "csrc", "rdst_args.h"),
+           os.path.join(HERE, "csrc", "rdst_topk_layout.h"), os.path.join(HERE, "csrc", "rdst_select_layout.h")]
 OUT = os.path.join(HERE, "librdst_hip.so")
 
 

@@ -34,6 +34,7 @@
 
 #include "rdst_hip.h"
 #include "rdst_internal.h"
+#include "rdst_args.h"
 
 namespace {
 
@@ -403,7 +404,7 @@ __global__ __launch_bounds__(256) void rows_gather_kernel(const U* __restrict__ 
 // host side
 // ------------------------------------------------------------------------------------------------------------------------
 
-uint64_t align256(uint64_t x) { return (x + 255) / 256 * 256; }
+using rdst_args::align256;
 
 // Scratch of the core for n rows (n < 2^32): 8 + 8 + 5 x 4 bytes per row, the run tables (at most n / 2 runs) and the
 // scan's tile sums.

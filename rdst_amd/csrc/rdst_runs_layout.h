@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "rdst_hip.h"
+#include "rdst_args.h"
 
 namespace rdst_runs_layout {
 
@@ -18,7 +19,7 @@ constexpr uint32_t THREADS = 256;  // one workgroup per tile: four waves, each o
 constexpr uint32_t rows(uint32_t elem_bytes) { return elem_bytes >= 8 ? 16 : (elem_bytes == 1 ? 4 : 8); }
 constexpr uint32_t LOOKBACK_WINDOW = 8;  // predecessor status words fetched per look-back round trip
 
-constexpr bool key_width_ok(uint32_t elem_bytes) { return elem_bytes == 1 || elem_bytes == 2 || elem_bytes == 4 || elem_bytes == 8 || elem_bytes == 16; }
+using rdst_args::key_width_ok;
 constexpr uint32_t keys_per_tile(uint32_t elem_bytes) { return THREADS * rows(elem_bytes) * 16 / elem_bytes; }
 // tiles the launch is sized for: those of `len` keys, one for an empty array (it writes the outputs of m == 0)
 constexpr uint64_t tiles(uint64_t len, uint32_t elem_bytes) {

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "rdst_hip.h"
+#include "rdst_args.h"
 #include "rdst_search_layout.h"
 
 namespace rdst_internal {
@@ -13,25 +14,9 @@ int note_error(int code, const char* what);
 int check_key_args(const void* p, uint64_t len, uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels);
 }  // namespace rdst_internal
 
+using namespace rdst_args;
 using rdst_internal::note_error;
 namespace L = rdst_search_layout;
-
-namespace {
-
-bool misaligned(const void* p, uint64_t to) { return reinterpret_cast<uintptr_t>(p) % to != 0; }
-
-struct Range {  // [lo, hi) of the address space; an empty one overlaps nothing
-    uintptr_t lo, hi;
-};
-Range range_of(const void* p, uint64_t elems, uint64_t bytes_each) {  // (elems < 2^32, bytes_each <= 2^15: no overflow)
-    const uintptr_t lo = reinterpret_cast<uintptr_t>(p);
-    const uint64_t room = UINTPTR_MAX - lo;
-    const uint64_t bytes = elems > room / bytes_each ? room : elems * bytes_each;
-    return {lo, lo + (uintptr_t)bytes};
-}
-bool overlap(Range a, Range b) { return a.lo < a.hi && b.lo < b.hi && a.lo < b.hi && b.lo < a.hi; }
-
-}  // namespace
 
 int rdst_internal::search_check_args(const void* dev_sorted, uint64_t len, const void* dev_len, uint32_t len_bytes, const void* dev_needles,
                                      uint64_t n_needles, const void* dev_out_lower, const void* dev_out_upper, uint32_t offset_bytes,

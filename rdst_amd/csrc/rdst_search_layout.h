@@ -7,6 +7,7 @@
 #include <stdint.h>
 
 #include "rdst_hip.h"
+#include "rdst_args.h"
 
 namespace rdst_search_layout {
 
@@ -20,7 +21,7 @@ constexpr uint32_t SPLITTERS = 1024;
 // Keys of the haystack a workgroup stages in LDS: 32 KiB for 4-, 8- and 16-byte keys; 1- and 2-byte keys stay at 8 192 keys.
 constexpr uint32_t window(uint32_t elem_bytes) { return elem_bytes == 16 ? 2048 : (elem_bytes == 8 ? 4096 : 8192); }
 
-constexpr bool key_width_ok(uint32_t elem_bytes) { return elem_bytes == 1 || elem_bytes == 2 || elem_bytes == 4 || elem_bytes == 8 || elem_bytes == 16; }
+using rdst_args::key_width_ok;
 // the position of splitter j in a haystack of m keys (m > 0): below m, never decreasing in j
 constexpr uint32_t splitter_pos(uint32_t j, uint32_t m) { return (uint32_t)((uint64_t)j * m / SPLITTERS); }
 // no stretch between two neighbouring splitters (or behind the last one) is longer than this

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "rdst_hip.h"
+#include "rdst_args.h"
 #include "rdst_rank_rule.h"
 #include "rdst_segments_layout.h"
 
@@ -114,8 +115,8 @@ uint32_t g_topk_stream_max = 0;  // 0: the default
 // keys only: every width; with an index: 4- and 8-byte keys and a 4- or 8-byte index (rdst_hip_topk_limits' codes)
 int topk_segments_widths(uint32_t elem_bytes, uint32_t index_bytes) {
     if (!L::key_width_ok(elem_bytes)) return note_error(RDST_ERR_UNSUPPORTED, "device path is built for 1-, 2-, 4-, 8- and 16-byte keys");
-    if (index_bytes != 0 && index_bytes != 4 && index_bytes != 8) return note_error(RDST_ERR_ARG, "topk: index_bytes must be 4 or 8");
-    if (index_bytes != 0 && !L::pair_width_ok(elem_bytes)) return note_error(RDST_ERR_UNSUPPORTED, "topk: an index output takes 4- or 8-byte keys");
+    if (index_bytes != 0 && !rdst_args::index_bytes_ok(index_bytes)) return note_error(RDST_ERR_ARG, "topk: index_bytes must be 4 or 8");
+    if (index_bytes != 0 && !rdst_args::index_keys_ok(elem_bytes)) return note_error(RDST_ERR_UNSUPPORTED, "topk: an index output takes 4- or 8-byte keys");
     return RDST_OK;
 }
 }  // namespace

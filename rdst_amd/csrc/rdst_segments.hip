@@ -464,7 +464,7 @@ struct SegCall {
     bool pairs() const { return val_bytes != 0; }
 };
 
-bool misaligned(const void* p, uint32_t to) { return reinterpret_cast<uintptr_t>(p) % to != 0; }
+using rdst_args::misaligned;
 
 // What every entry checks first: the key arguments, then (the pair entries) the widths.
 int check_call(const SegCall& c, bool pair_entry, uint64_t n_segments) {

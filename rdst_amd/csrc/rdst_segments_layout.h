@@ -10,11 +10,12 @@
 #include <initializer_list>
 
 #include "rdst_hip.h"
+#include "rdst_args.h"
 
 namespace rdst_segments_layout {
 
 // ---- widths ----------------------------------------------------------------------------------------------------------
-constexpr bool key_width_ok(uint32_t b) { return b == 1 || b == 2 || b == 4 || b == 8 || b == 16; }
+using rdst_args::key_width_ok;
 constexpr bool pair_width_ok(uint32_t b) { return b == 4 || b == 8; }  // the keys and the values of a key-value sort
 
 // ---- shapes ----------------------------------------------------------------------------------------------------------
@@ -43,6 +44,8 @@ constexpr uint32_t SELECT_SEGMENTS_MAX_RANKS = 32;
 // ---- scratch (byte offsets from its 256-byte aligned base; every array is rounded up to 256 bytes) ----------------------
 constexpr uint64_t MAX_SEGMENTS = 1ull << 30;  // of a table in device memory
 constexpr uint64_t up256(uint64_t bytes) { return (bytes + 255) / 256 * 256; }
+// the segmented partial sort and select, borders on the host: the item table; a far segment's own scratch lies behind it
+constexpr uint64_t table_bytes(uint64_t n_segments) { return up256(n_segments * sizeof(rdst_segment_item)); }
 
 // Device-resident offsets: what the plan keeps.  A 256-byte header; four u32 arrays of n_segments (the class keys and
 // segment indices of the plan's pair sort, and that sort's two tmps); the item table (16 bytes per segment): 32 bytes per

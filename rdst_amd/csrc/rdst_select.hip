@@ -40,21 +40,15 @@
 #include "rdst_internal.h"
 #include "rdst_device.h"
 #include "rdst_stream.h"
+#include "rdst_select_layout.h"
 
 namespace {
 
+using namespace rdst_select_layout;  // the ranks of a round, the digits, the rooms, select_layout: shared with rdst_rank_args.cpp
+using rdst_args::POSITION_BITS;
 using rdst_internal::launch;
 using rdst_internal::set_error;
 
-constexpr uint32_t MAX_RANKS = 64;             // ranks followed in the same reads: rows of counters in LDS
-constexpr uint32_t DIGIT0_BITS_WIDE = 12;      // level 0, keys of two bytes and more
-constexpr uint32_t DIGIT0_BITS_BYTE = 8;       // level 0, one-byte keys: the whole key
-constexpr uint32_t DIGIT_BITS = 8;             // every later level
-constexpr uint32_t COUNTERS0 = 1u << DIGIT0_BITS_WIDE;
-constexpr uint32_t ROW = 1u << DIGIT_BITS;     // counters per group
-constexpr uint32_t COUNTER_WORDS = MAX_RANKS * ROW;  // 64 KiB: the level kernel's LDS rows and the counters in the scratch
-constexpr uint32_t POSITION_BITS = 32;         // len < 2^32
-constexpr uint64_t DEFAULT_CAND_CAPACITY = 1ull << 24;  // 64 uniform buckets of 10^9 keys after level 0: 64 x 2.44 x 10^5 = 1.56 x 10^7
 constexpr int STREAM_THREADS = 256;            // level 0 and the collection
 constexpr int LEVEL_THREADS = 512;             // later levels: 74 KiB of LDS per workgroup, two workgroups per CU
 constexpr int STREAM_UNROLL = 4;               // 16-byte loads in flight per lane
@@ -62,8 +56,6 @@ constexpr uint32_t STAGE_BYTES = 4096;         // collection: LDS per wave betwe
 constexpr int PICK_THREADS = 1024;
 constexpr int BLOCKS_PER_CU = 8;
 constexpr int LEVEL_BLOCKS_PER_CU = 2;
-constexpr uint64_t HEADER_BYTES = 256;
-static_assert(COUNTER_WORDS >= COUNTERS0, "level 0 counts into the same counters");
 
 struct SelectHeader {  // the first HEADER_BYTES of the scratch
     uint32_t ready;        // no further level is needed
@@ -86,35 +78,13 @@ struct SelectTable {  // behind the header
     uint32_t off[MAX_RANKS];      //            sum of m over the groups before it
     uint32_t grp[MAX_RANKS];      // per rank of the round: its group
 };
+static_assert(sizeof(SelectTable) == TABLE_BYTES, "the table fills the place the layout gives it");
 
 struct RankArgs {  // one round's ranks, ascending, and the caller's slot of each: a kernel argument
     uint32_t n;
     uint32_t rank[MAX_RANKS];
     uint32_t slot[MAX_RANKS];
 };
-
-constexpr uint64_t align256(uint64_t x) { return (x + 255) / 256 * 256; }
-
-bool key_width_ok(uint32_t b) { return b == 1 || b == 2 || b == 4 || b == 8 || b == 16; }
-uint32_t digit0_bits_for(uint32_t elem_bytes) { return elem_bytes == 1 ? DIGIT0_BITS_BYTE : DIGIT0_BITS_WIDE; }
-uint32_t levels_over(uint32_t bits, uint32_t digit) { return (bits + digit - 1) / digit; }
-uint32_t key_levels_for(uint32_t elem_bytes) { return 1 + levels_over(8 * elem_bytes - digit0_bits_for(elem_bytes), DIGIT_BITS); }
-
-struct SelectLayout {
-    uint64_t table, counters, cand, cand_tmp, total;
-    uint64_t cap;  // the capacity the candidate buffers are sized for
-};
-SelectLayout select_layout(uint64_t len, uint32_t elem_bytes, uint32_t index_bytes, uint64_t cand_capacity) {
-    const uint64_t c_bytes = index_bytes ? 2ull * elem_bytes : elem_bytes;
-    SelectLayout L{};
-    L.cap = std::min<uint64_t>(cand_capacity ? cand_capacity : DEFAULT_CAND_CAPACITY, std::max<uint64_t>(len, 1));
-    L.table = HEADER_BYTES;
-    L.counters = L.table + align256(sizeof(SelectTable));
-    L.cand = L.counters + COUNTER_WORDS * sizeof(uint32_t);
-    L.cand_tmp = L.cand + align256(L.cap * c_bytes);
-    L.total = L.cand_tmp + align256(L.cap * c_bytes);
-    return L;
-}
 
 // ---- device side -------------------------------------------------------------------------------------------------------------
 
@@ -435,8 +405,6 @@ struct SelectCall {
     hipStream_t s;
 };
 
-bool misaligned(const void* p, uint64_t to) { return reinterpret_cast<uintptr_t>(p) % to != 0; }
-
 uint32_t stream_grid(uint64_t len, uint32_t elem_bytes, int cus, int threads, int per_cu) {
     const uint64_t vecs = len / (16 / elem_bytes) + 1;
     const uint64_t want = (vecs + threads - 1) / threads;
@@ -573,33 +541,10 @@ int rdst_internal::select_slice_locked(const void* keys, uint64_t len, const uin
 
 extern "C" {
 
-uint64_t rdst_hip_select_scratch_bytes(uint64_t len, uint64_t n_ranks, uint32_t elem_bytes, uint32_t index_bytes, uint64_t cand_capacity) {
-    (void)n_ranks;  // a longer list is served in rounds on the same scratch
-    if (!key_width_ok(elem_bytes)) return 0;
-    if (index_bytes != 0 && (index_bytes != 4 && index_bytes != 8)) return 0;
-    if (index_bytes != 0 && elem_bytes != 4 && elem_bytes != 8) return 0;
-    return select_layout(len, elem_bytes, index_bytes, cand_capacity).total;
-}
-
-int rdst_hip_select_limits(uint32_t elem_bytes, uint32_t index_bytes, uint32_t out[5]) {
-    if (out == nullptr) return set_error(RDST_ERR_ARG, "null output");
-    if (!key_width_ok(elem_bytes)) return set_error(RDST_ERR_UNSUPPORTED, "device path is built for 1-, 2-, 4-, 8- and 16-byte keys");
-    if (index_bytes != 0 && index_bytes != 4 && index_bytes != 8) return set_error(RDST_ERR_ARG, "select: index_bytes must be 4 or 8");
-    if (index_bytes != 0 && elem_bytes != 4 && elem_bytes != 8) return set_error(RDST_ERR_UNSUPPORTED, "select: an index output takes 4- or 8-byte keys");
-    out[0] = MAX_RANKS;
-    out[1] = digit0_bits_for(elem_bytes);
-    out[2] = DIGIT_BITS;
-    out[3] = (uint32_t)DEFAULT_CAND_CAPACITY;
-    out[4] = key_levels_for(elem_bytes) + (index_bytes ? levels_over(POSITION_BITS, DIGIT_BITS) : 0);
-    return RDST_OK;
-}
-
 int rdst_hip_select_device(const void* dev_keys, uint64_t len, const uint64_t* ranks, uint64_t n_ranks, void* dev_out_keys, void* dev_out_index,
                            uint32_t index_bytes, void* dev_scratch, uint64_t scratch_bytes, uint64_t cand_capacity, uint32_t elem_bytes,
                            rdst_key_kind kind, uint32_t levels, uint32_t flags, void* stream) {
-    if (int rc = rdst_internal::check_key_args(dev_keys, len, elem_bytes, kind, levels)) return rc;
-    if (kind == RDST_KEY_BYTES_BE) return set_error(RDST_ERR_UNSUPPORTED, "select: [u8; N] keys are not built");
-    if (len >= (1ull << 32)) return set_error(RDST_ERR_UNSUPPORTED, "select: len must be below 2^32");
+    if (int rc = rdst_internal::rank_check_head("select", dev_keys, len, elem_bytes, kind, levels)) return rc;
     if (flags & ~RDST_TOPK_LARGEST) return set_error(RDST_ERR_ARG, "select: unknown flag bits");
     if (n_ranks == 0) return RDST_OK;
     if (ranks == nullptr) return set_error(RDST_ERR_ARG, "select: null ranks");
@@ -609,17 +554,7 @@ int rdst_hip_select_device(const void* dev_keys, uint64_t len, const uint64_t* r
             snprintf(msg, sizeof msg, "select: ranks[%llu] is not below len", (unsigned long long)i);
             return set_error(RDST_ERR_ARG, msg);
         }
-    if (dev_out_keys == nullptr) return set_error(RDST_ERR_ARG, "select: null key output");
-    if (misaligned(dev_out_keys, elem_bytes)) return set_error(RDST_ERR_ALIGN, "select: key output not aligned to the element size");
-    if (dev_out_index != nullptr) {
-        if (index_bytes != 4 && index_bytes != 8) return set_error(RDST_ERR_ARG, "select: index_bytes must be 4 or 8");
-        if (elem_bytes != 4 && elem_bytes != 8) return set_error(RDST_ERR_UNSUPPORTED, "select: an index output takes 4- or 8-byte keys");
-        if (misaligned(dev_out_index, index_bytes)) return set_error(RDST_ERR_ALIGN, "select: index output not aligned to index_bytes");
-    } else {
-        index_bytes = 0;
-    }
-    if (dev_scratch == nullptr) return set_error(RDST_ERR_ARG, "select: null scratch");
-    if (misaligned(dev_scratch, 256)) return set_error(RDST_ERR_ALIGN, "select: scratch not aligned to 256 bytes");
+    if (int rc = rdst_internal::rank_check_outputs("select", dev_out_keys, dev_out_index, &index_bytes, dev_scratch, elem_bytes)) return rc;
     if (scratch_bytes < select_layout(len, elem_bytes, index_bytes, cand_capacity).total)
         return set_error(RDST_ERR_ARG, "select: scratch_bytes is below rdst_hip_select_scratch_bytes(len, n_ranks, elem_bytes, index_bytes, cand_capacity)");
     // ascending rank order (equal ranks in slot order), before the mutex is taken; nothing may be thrown through the C ABI
@@ -639,7 +574,7 @@ int rdst_hip_select_device(const void* dev_keys, uint64_t len, const uint64_t* r
 
 int rdst_hip_debug_select_state(const void* dev_scratch, void* stream, uint64_t out[4]) {
     if (dev_scratch == nullptr || out == nullptr) return set_error(RDST_ERR_ARG, "select: null scratch or output");
-    if (misaligned(dev_scratch, 256)) return set_error(RDST_ERR_ALIGN, "select: scratch not aligned to 256 bytes");
+    if (int rc = rdst_internal::rank_check_scratch("select", dev_scratch)) return rc;
     SelectHeader h;
     hipStream_t s = static_cast<hipStream_t>(stream);
     RDST_HIP_TRY(hipMemcpyAsync(&h, dev_scratch, sizeof h, hipMemcpyDeviceToHost, s));

@@ -306,8 +306,6 @@ __global__ __launch_bounds__(BLOCK_THREADS) void select_segment_stream_counted_k
 
 using SegSelectCall = rdst_internal::SelectSegmentsCall;
 
-bool misaligned(const void* p, uint64_t to) { return reinterpret_cast<uintptr_t>(p) % to != 0; }
-
 // One round over the item table in device memory: wave class first, then block class, then stream class.  `hdr` == nullptr:
 // the host knows the counts, counts[0 .. 2], and the classes follow one another in `items`.  With `hdr`, the plan header in
 // device memory: the counts stand there, and counts[0 .. 2] are the host's bounds on them, for the grids alone.
@@ -364,8 +362,6 @@ int launch_round(const SegSelectCall& c, const rdst_segment_item* items, const u
     }
 }
 
-uint64_t table_bytes(uint64_t n_segments) { return L::up256(n_segments * sizeof(rdst_segment_item)); }
-
 }  // namespace
 
 // Every round of c.n_ranks specs, MAX_RANKS a round, over the same items: slot i keeps its place in the row.
@@ -383,28 +379,16 @@ int rdst_internal::select_segments_launch_locked(const SelectSegmentsCall& c, co
     return RDST_OK;
 }
 
-extern "C" uint64_t rdst_hip_select_segments_scratch_bytes(uint64_t n_segments, uint64_t longest_segment, uint64_t n_ranks, uint32_t elem_bytes,
-                                                           uint32_t index_bytes) {
-    uint32_t lim[4];
-    if (n_segments == 0 || n_segments >= (1ull << 32) || longest_segment >= (1ull << 32)) return 0;
-    if (rdst_hip_select_segments_limits(elem_bytes, index_bytes, lim)) return 0;
-    uint64_t total = table_bytes(n_segments);
-    if (longest_segment > lim[2]) total += rdst_hip_select_scratch_bytes(longest_segment, n_ranks, elem_bytes, index_bytes, 0);  // a far segment is possible
-    return total;
-}
-
 extern "C" int rdst_hip_select_segments_device(const void* dev_keys, uint64_t len, const uint64_t* offsets, uint64_t n_segments,
                                                const rdst_rank_spec* ranks, uint64_t n_ranks, void* dev_out_keys, void* dev_out_index,
                                                uint32_t index_bytes, void* dev_scratch, uint64_t scratch_bytes, uint32_t elem_bytes, rdst_key_kind kind,
                                                uint32_t levels, uint32_t flags, void* stream) {
-    if (int rc = rdst_internal::check_key_args(dev_keys, len, elem_bytes, kind, levels)) return rc;
-    if (kind == RDST_KEY_BYTES_BE) return set_error(RDST_ERR_UNSUPPORTED, "select: [u8; N] keys are not built");
-    if (len >= (1ull << 32)) return set_error(RDST_ERR_UNSUPPORTED, "select: len must be below 2^32");
+    if (int rc = rdst_internal::rank_check_head("select", dev_keys, len, elem_bytes, kind, levels)) return rc;
     if (flags & ~RDST_TOPK_LARGEST) return set_error(RDST_ERR_ARG, "select: unknown flag bits");
     if (n_ranks == 0 || n_segments == 0) return RDST_OK;
     // the table: its own errors, and the counts (a work list that does not fit capacity 0 is the expected answer)
     if (dev_out_index == nullptr) index_bytes = 0;
-    const bool index_ok = index_bytes == 0 || ((index_bytes == 4 || index_bytes == 8) && (elem_bytes == 4 || elem_bytes == 8));
+    const bool index_ok = rdst_args::index_widths_ok(elem_bytes, index_bytes);
     uint64_t counts[4] = {0, 0, 0, 0}, longest_far = 0;
     int rc = rdst_topk_segments_plan(offsets, n_segments, len, 1, elem_bytes, index_ok ? index_bytes : 0, nullptr, 0, counts, &longest_far);
     const uint64_t total = counts[0] + counts[1] + counts[2] + counts[3];
@@ -417,15 +401,7 @@ extern "C" int rdst_hip_select_segments_device(const void* dev_keys, uint64_t le
                      (unsigned long long)i);
             return set_error(RDST_ERR_ARG, msg);
         }
-    if (dev_out_keys == nullptr) return set_error(RDST_ERR_ARG, "select: null key output");
-    if (misaligned(dev_out_keys, elem_bytes)) return set_error(RDST_ERR_ALIGN, "select: key output not aligned to the element size");
-    if (dev_out_index != nullptr) {
-        if (index_bytes != 4 && index_bytes != 8) return set_error(RDST_ERR_ARG, "select: index_bytes must be 4 or 8");
-        if (elem_bytes != 4 && elem_bytes != 8) return set_error(RDST_ERR_UNSUPPORTED, "select: an index output takes 4- or 8-byte keys");
-        if (misaligned(dev_out_index, index_bytes)) return set_error(RDST_ERR_ALIGN, "select: index output not aligned to index_bytes");
-    }
-    if (dev_scratch == nullptr) return set_error(RDST_ERR_ARG, "select: null scratch");
-    if (misaligned(dev_scratch, 256)) return set_error(RDST_ERR_ALIGN, "select: scratch not aligned to 256 bytes");
+    if ((rc = rdst_internal::rank_check_outputs("select", dev_out_keys, dev_out_index, &index_bytes, dev_scratch, elem_bytes))) return rc;
     uint64_t longest = 0;
     for (uint64_t s = 0; s < n_segments; ++s) longest = std::max(longest, offsets[s + 1] - offsets[s]);
     if (scratch_bytes < rdst_hip_select_segments_scratch_bytes(n_segments, longest, n_ranks, elem_bytes, index_bytes))
@@ -474,7 +450,7 @@ extern "C" int rdst_hip_select_segments_device(const void* dev_keys, uint64_t le
     }
     // far segments one after another, each by the whole-array select (no copy to the host, no wait), in the scratch behind the
     // table
-    char* far_scratch = static_cast<char*>(dev_scratch) + table_bytes(n_segments);
+    char* far_scratch = static_cast<char*>(dev_scratch) + L::table_bytes(n_segments);
     for (uint64_t f = 0; f < counts[3]; ++f) {
         const uint32_t sg = items[batched + f].seg;
         const uint64_t start = offsets[sg], n = offsets[sg + 1] - start, row = (uint64_t)sg * n_ranks, have = far_have[f];

@@ -33,8 +33,6 @@ using rdst_internal::set_error;
 using Call = rdst_internal::SelectSegmentsCall;
 using Plan = rdst_internal::TopkSegmentsPlan;
 
-bool misaligned(const void* p, uint64_t to) { return reinterpret_cast<uintptr_t>(p) % to != 0; }
-
 // The asynchronous mode after the checks: the plan and, per round, three counted launches, grids from what the host knows — a
 // segment holds at least one key, a block-class one more than wave_max, a stream-class one more than block_max —, counts
 // from the header.  Nothing here waits for the device or copies to the host.  Callers hold the library's mutex.
@@ -141,9 +139,7 @@ extern "C" int rdst_hip_select_segments_device_offsets(const void* dev_keys, uin
                                                        uint64_t far_capacity, uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels, uint32_t flags,
                                                        void* stream) {
     // 1: the key arguments, len and flags, as rdst_hip_select_segments_device checks them
-    if (int rc = rdst_internal::check_key_args(dev_keys, len, elem_bytes, kind, levels)) return rc;
-    if (kind == RDST_KEY_BYTES_BE) return set_error(RDST_ERR_UNSUPPORTED, "select: [u8; N] keys are not built");
-    if (len >= (1ull << 32)) return set_error(RDST_ERR_UNSUPPORTED, "select: len must be below 2^32");
+    if (int rc = rdst_internal::rank_check_head("select", dev_keys, len, elem_bytes, kind, levels)) return rc;
     if (flags & ~RDST_TOPK_LARGEST) return set_error(RDST_ERR_ARG, "select: unknown flag bits");
     // 2
     if (n_ranks == 0 || n_segments == 0) return RDST_OK;
@@ -159,18 +155,8 @@ extern "C" int rdst_hip_select_segments_device_offsets(const void* dev_keys, uin
                      (unsigned long long)i);
             return set_error(RDST_ERR_ARG, msg);
         }
-    // 5: the outputs
-    if (dev_out_keys == nullptr) return set_error(RDST_ERR_ARG, "select: null key output");
-    if (misaligned(dev_out_keys, elem_bytes)) return set_error(RDST_ERR_ALIGN, "select: key output not aligned to the element size");
-    if (dev_out_index == nullptr) index_bytes = 0;
-    else {
-        if (index_bytes != 4 && index_bytes != 8) return set_error(RDST_ERR_ARG, "select: index_bytes must be 4 or 8");
-        if (elem_bytes != 4 && elem_bytes != 8) return set_error(RDST_ERR_UNSUPPORTED, "select: an index output takes 4- or 8-byte keys");
-        if (misaligned(dev_out_index, index_bytes)) return set_error(RDST_ERR_ALIGN, "select: index output not aligned to index_bytes");
-    }
-    // 6: the scratch
-    if (dev_scratch == nullptr) return set_error(RDST_ERR_ARG, "select: null scratch");
-    if (misaligned(dev_scratch, 256)) return set_error(RDST_ERR_ALIGN, "select: scratch not aligned to 256 bytes");
+    // 5, 6: the outputs, the scratch
+    if ((rc = rdst_internal::rank_check_outputs("select", dev_out_keys, dev_out_index, &index_bytes, dev_scratch, elem_bytes))) return rc;
     if (far_capacity >= (1ull << 32)) return set_error(RDST_ERR_ARG, "select: far_capacity must be below 2^32 (pass len)");
     if (scratch_bytes < rdst_hip_select_segments_device_offsets_scratch_bytes(n_segments, far_capacity, n_ranks, elem_bytes, index_bytes))
         return set_error(RDST_ERR_ARG, "select: scratch_bytes is below rdst_hip_select_segments_device_offsets_scratch_bytes(n_segments, far_capacity, n_ranks, elem_bytes, index_bytes)");

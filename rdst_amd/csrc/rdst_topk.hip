@@ -36,23 +36,20 @@
 #include "rdst_internal.h"
 #include "rdst_device.h"
 #include "rdst_stream.h"
+#include "rdst_topk_layout.h"
 
 namespace {
 
+using namespace rdst_topk_layout;  // the digits, the room of the header, topk_layout: shared with rdst_rank_args.cpp
+using namespace rdst_args;          // levels_over, POSITION_BITS
 using rdst_internal::launch;
 using rdst_internal::set_error;
 
-constexpr uint32_t COUNTERS = 4096;           // one counter per value of the widest digit
-constexpr uint32_t DIGIT_BITS_WIDE = 12;      // keys of two bytes and more
-constexpr uint32_t DIGIT_BITS_BYTE = 8;       // one-byte keys: the whole key
-constexpr uint32_t POSITION_BITS = 32;        // len < 2^32
-constexpr uint64_t DEFAULT_CAND_CAPACITY = 1ull << 20;  // a uniform bucket of 10^9 keys after one level: 2.4 x 10^5
 constexpr int HIST_THREADS = 256;
 constexpr int HIST_UNROLL = 4;                // 16-byte loads in flight per lane
 constexpr uint32_t STAGE_BYTES = 4096;       // collection: LDS per wave and class between two claims of output space
 constexpr int PICK_THREADS = 1024;
 constexpr int BLOCKS_PER_CU = 8;
-constexpr uint64_t HEADER_BYTES = 256;
 
 struct TopkHeader {  // the first HEADER_BYTES of the scratch
     uint32_t ready;        // no further level is needed
@@ -68,29 +65,6 @@ struct TopkHeader {  // the first HEADER_BYTES of the scratch
     uint64_t pref[2], pmask[2];  // prefix over the key's bits, low word first
 };
 static_assert(sizeof(TopkHeader) <= HEADER_BYTES, "the header fits its place in the scratch");
-
-constexpr uint64_t align256(uint64_t x) { return (x + 255) / 256 * 256; }
-
-bool key_width_ok(uint32_t b) { return b == 1 || b == 2 || b == 4 || b == 8 || b == 16; }
-uint32_t digit_bits_for(uint32_t elem_bytes) { return elem_bytes == 1 ? DIGIT_BITS_BYTE : DIGIT_BITS_WIDE; }
-uint32_t levels_over(uint32_t bits, uint32_t digit) { return (bits + digit - 1) / digit; }
-struct TopkLayout {
-    uint64_t counters, sel, sel_tmp, cand, cand_tmp, total;
-    uint64_t cap;  // the capacity the candidate buffers are sized for
-};
-TopkLayout topk_layout(uint64_t len, uint64_t k, uint32_t elem_bytes, uint32_t index_bytes, uint64_t cand_capacity) {
-    const uint64_t c_bytes = index_bytes ? 2ull * elem_bytes : elem_bytes;
-    TopkLayout L{};
-    L.cap = std::min<uint64_t>(cand_capacity ? cand_capacity : DEFAULT_CAND_CAPACITY, std::max<uint64_t>(len, 1));
-    const uint64_t kk = std::min(k, len);
-    L.counters = HEADER_BYTES;
-    L.sel = L.counters + COUNTERS * sizeof(uint32_t);
-    L.sel_tmp = L.sel + align256(kk * c_bytes);
-    L.cand = L.sel_tmp + align256(kk * c_bytes);
-    L.cand_tmp = L.cand + align256(L.cap * c_bytes);
-    L.total = L.cand_tmp + align256(L.cap * c_bytes);
-    return L;
-}
 
 // ---- device side -------------------------------------------------------------------------------------------------------------
 
@@ -253,8 +227,6 @@ struct TopkCall {
     hipStream_t s;
 };
 
-bool misaligned(const void* p, uint64_t to) { return reinterpret_cast<uintptr_t>(p) % to != 0; }
-
 uint32_t stream_grid(uint64_t len, uint32_t elem_bytes, int cus) {
     const uint64_t vecs = len / (16 / elem_bytes) + 1;
     const uint64_t want = (vecs + HIST_THREADS - 1) / HIST_THREADS;
@@ -359,45 +331,14 @@ int rdst_internal::topk_slice_locked(const void* keys, uint64_t len, uint64_t k,
 
 extern "C" {
 
-uint64_t rdst_hip_topk_scratch_bytes(uint64_t len, uint64_t k, uint32_t elem_bytes, uint32_t index_bytes, uint64_t cand_capacity) {
-    if (!key_width_ok(elem_bytes)) return 0;
-    if (index_bytes != 0 && (index_bytes != 4 && index_bytes != 8)) return 0;
-    if (index_bytes != 0 && elem_bytes != 4 && elem_bytes != 8) return 0;
-    return topk_layout(len, k, elem_bytes, index_bytes, cand_capacity).total;
-}
-
-int rdst_hip_topk_limits(uint32_t elem_bytes, uint32_t index_bytes, uint32_t out[3]) {
-    if (out == nullptr) return set_error(RDST_ERR_ARG, "null output");
-    if (!key_width_ok(elem_bytes)) return set_error(RDST_ERR_UNSUPPORTED, "device path is built for 1-, 2-, 4-, 8- and 16-byte keys");
-    if (index_bytes != 0 && index_bytes != 4 && index_bytes != 8) return set_error(RDST_ERR_ARG, "topk: index_bytes must be 4 or 8");
-    if (index_bytes != 0 && elem_bytes != 4 && elem_bytes != 8) return set_error(RDST_ERR_UNSUPPORTED, "topk: an index output takes 4- or 8-byte keys");
-    const uint32_t digit = digit_bits_for(elem_bytes);
-    out[0] = digit;
-    out[1] = (uint32_t)DEFAULT_CAND_CAPACITY;
-    out[2] = levels_over(8 * elem_bytes, digit) + (index_bytes ? levels_over(POSITION_BITS, digit) : 0);
-    return RDST_OK;
-}
-
 int rdst_hip_topk_device(const void* dev_keys, uint64_t len, uint64_t k, void* dev_out_keys, void* dev_out_index, uint32_t index_bytes,
                          void* dev_scratch, uint64_t scratch_bytes, uint64_t cand_capacity, uint32_t elem_bytes, rdst_key_kind kind,
                          uint32_t levels, uint32_t flags, void* stream) {
-    if (int rc = rdst_internal::check_key_args(dev_keys, len, elem_bytes, kind, levels)) return rc;
-    if (kind == RDST_KEY_BYTES_BE) return set_error(RDST_ERR_UNSUPPORTED, "topk: [u8; N] keys are not built");
-    if (len >= (1ull << 32)) return set_error(RDST_ERR_UNSUPPORTED, "topk: len must be below 2^32");
+    if (int rc = rdst_internal::rank_check_head("topk", dev_keys, len, elem_bytes, kind, levels)) return rc;
     if (k > len) return set_error(RDST_ERR_ARG, "topk: k is larger than len");
     if (flags & ~RDST_TOPK_LARGEST) return set_error(RDST_ERR_ARG, "topk: unknown flag bits");
     if (k == 0) return RDST_OK;
-    if (dev_out_keys == nullptr) return set_error(RDST_ERR_ARG, "topk: null key output");
-    if (misaligned(dev_out_keys, elem_bytes)) return set_error(RDST_ERR_ALIGN, "topk: key output not aligned to the element size");
-    if (dev_out_index != nullptr) {
-        if (index_bytes != 4 && index_bytes != 8) return set_error(RDST_ERR_ARG, "topk: index_bytes must be 4 or 8");
-        if (elem_bytes != 4 && elem_bytes != 8) return set_error(RDST_ERR_UNSUPPORTED, "topk: an index output takes 4- or 8-byte keys");
-        if (misaligned(dev_out_index, index_bytes)) return set_error(RDST_ERR_ALIGN, "topk: index output not aligned to index_bytes");
-    } else {
-        index_bytes = 0;
-    }
-    if (dev_scratch == nullptr) return set_error(RDST_ERR_ARG, "topk: null scratch");
-    if (misaligned(dev_scratch, 256)) return set_error(RDST_ERR_ALIGN, "topk: scratch not aligned to 256 bytes");
+    if (int rc = rdst_internal::rank_check_outputs("topk", dev_out_keys, dev_out_index, &index_bytes, dev_scratch, elem_bytes)) return rc;
     TopkCall c{};
     c.L = topk_layout(len, k, elem_bytes, index_bytes, cand_capacity);
     if (scratch_bytes < c.L.total) return set_error(RDST_ERR_ARG, "topk: scratch_bytes is below rdst_hip_topk_scratch_bytes(len, k, elem_bytes, index_bytes, cand_capacity)");
@@ -419,7 +360,7 @@ int rdst_hip_topk_device(const void* dev_keys, uint64_t len, uint64_t k, void* d
 
 int rdst_hip_debug_topk_state(const void* dev_scratch, void* stream, uint64_t out[4]) {
     if (dev_scratch == nullptr || out == nullptr) return set_error(RDST_ERR_ARG, "topk: null scratch or output");
-    if (misaligned(dev_scratch, 256)) return set_error(RDST_ERR_ALIGN, "topk: scratch not aligned to 256 bytes");
+    if (int rc = rdst_internal::rank_check_scratch("topk", dev_scratch)) return rc;
     TopkHeader h;
     hipStream_t s = static_cast<hipStream_t>(stream);
     RDST_HIP_TRY(hipMemcpyAsync(&h, dev_scratch, sizeof h, hipMemcpyDeviceToHost, s));

@@ -233,8 +233,6 @@ __global__ __launch_bounds__(BLOCK_THREADS) void topk_segment_stream_counted_ker
 
 using SegTopkCall = rdst_internal::TopkSegmentsCall;
 
-bool misaligned(const void* p, uint64_t to) { return reinterpret_cast<uintptr_t>(p) % to != 0; }
-
 // The three batched launches over the item table in device memory: wave class first, then block class, then stream class.
 // `hdr` == nullptr: the host knows the counts, counts[0 .. 2], and the classes follow one another in `items`.  With `hdr`, the
 // plan header in device memory: the counts stand there, and counts[0 .. 2] are the host's bounds on them, for the grids alone.
@@ -291,8 +289,6 @@ int launch_classes(const SegTopkCall& c, const rdst_segment_item* items, const u
     }
 }
 
-uint64_t table_bytes(uint64_t n_segments) { return L::up256(n_segments * sizeof(rdst_segment_item)); }
-
 }  // namespace
 
 int rdst_internal::topk_segments_launch_locked(const TopkSegmentsCall& c, const rdst_segment_item* items, const uint32_t* hdr, const uint64_t counts[3]) {
@@ -301,41 +297,20 @@ int rdst_internal::topk_segments_launch_locked(const TopkSegmentsCall& c, const 
     return launch_classes(c, items, hdr, counts);
 }
 
-extern "C" uint64_t rdst_hip_topk_segments_scratch_bytes(uint64_t n_segments, uint64_t longest_segment, uint64_t k, uint32_t elem_bytes,
-                                                         uint32_t index_bytes) {
-    uint32_t lim[4];
-    if (n_segments == 0 || n_segments >= (1ull << 32) || longest_segment >= (1ull << 32)) return 0;
-    if (rdst_hip_topk_segments_limits(elem_bytes, index_bytes, lim)) return 0;
-    uint64_t total = table_bytes(n_segments);
-    if (longest_segment > lim[2] || (longest_segment > lim[1] && k > lim[3]))  // a far segment is possible
-        total += rdst_hip_topk_scratch_bytes(longest_segment, std::min(k, longest_segment), elem_bytes, index_bytes, 0);
-    return total;
-}
-
 extern "C" int rdst_hip_topk_segments_device(const void* dev_keys, uint64_t len, const uint64_t* offsets, uint64_t n_segments, uint64_t k,
                                              void* dev_out_keys, void* dev_out_index, uint32_t index_bytes, void* dev_scratch, uint64_t scratch_bytes,
                                              uint32_t elem_bytes, rdst_key_kind kind, uint32_t levels, uint32_t flags, void* stream) {
-    if (int rc = rdst_internal::check_key_args(dev_keys, len, elem_bytes, kind, levels)) return rc;
-    if (kind == RDST_KEY_BYTES_BE) return set_error(RDST_ERR_UNSUPPORTED, "topk: [u8; N] keys are not built");
-    if (len >= (1ull << 32)) return set_error(RDST_ERR_UNSUPPORTED, "topk: len must be below 2^32");
+    if (int rc = rdst_internal::rank_check_head("topk", dev_keys, len, elem_bytes, kind, levels)) return rc;
     if (flags & ~RDST_TOPK_LARGEST) return set_error(RDST_ERR_ARG, "topk: unknown flag bits");
     if (k == 0 || n_segments == 0) return RDST_OK;
     // the table: its own errors, and the counts (a work list that does not fit capacity 0 is the expected answer)
     if (dev_out_index == nullptr) index_bytes = 0;
-    const bool index_ok = index_bytes == 0 || ((index_bytes == 4 || index_bytes == 8) && (elem_bytes == 4 || elem_bytes == 8));
+    const bool index_ok = rdst_args::index_widths_ok(elem_bytes, index_bytes);
     uint64_t counts[4] = {0, 0, 0, 0}, longest_far = 0;
     int rc = rdst_topk_segments_plan(offsets, n_segments, len, k, elem_bytes, index_ok ? index_bytes : 0, nullptr, 0, counts, &longest_far);
     const uint64_t total = counts[0] + counts[1] + counts[2] + counts[3];
     if (rc != RDST_OK && !(rc == RDST_ERR_ARG && total > 0)) return rc;
-    if (dev_out_keys == nullptr) return set_error(RDST_ERR_ARG, "topk: null key output");
-    if (misaligned(dev_out_keys, elem_bytes)) return set_error(RDST_ERR_ALIGN, "topk: key output not aligned to the element size");
-    if (dev_out_index != nullptr) {
-        if (index_bytes != 4 && index_bytes != 8) return set_error(RDST_ERR_ARG, "topk: index_bytes must be 4 or 8");
-        if (elem_bytes != 4 && elem_bytes != 8) return set_error(RDST_ERR_UNSUPPORTED, "topk: an index output takes 4- or 8-byte keys");
-        if (misaligned(dev_out_index, index_bytes)) return set_error(RDST_ERR_ALIGN, "topk: index output not aligned to index_bytes");
-    }
-    if (dev_scratch == nullptr) return set_error(RDST_ERR_ARG, "topk: null scratch");
-    if (misaligned(dev_scratch, 256)) return set_error(RDST_ERR_ALIGN, "topk: scratch not aligned to 256 bytes");
+    if ((rc = rdst_internal::rank_check_outputs("topk", dev_out_keys, dev_out_index, &index_bytes, dev_scratch, elem_bytes))) return rc;
     uint64_t longest = 0;
     for (uint64_t s = 0; s < n_segments; ++s) longest = std::max(longest, offsets[s + 1] - offsets[s]);
     if (scratch_bytes < rdst_hip_topk_segments_scratch_bytes(n_segments, longest, k, elem_bytes, index_bytes))
@@ -356,7 +331,7 @@ extern "C" int rdst_hip_topk_segments_device(const void* dev_keys, uint64_t len,
         if ((rc = launch_classes(c, static_cast<const rdst_segment_item*>(dev_scratch), nullptr, counts))) return rc;
     }
     // far segments one after another, each by the whole-array route (no copy to the host, no wait), in the scratch behind the table
-    char* far_scratch = static_cast<char*>(dev_scratch) + table_bytes(n_segments);
+    char* far_scratch = static_cast<char*>(dev_scratch) + L::table_bytes(n_segments);
     for (uint64_t i = batched; i < total; ++i) {
         const uint32_t sg = items[i].seg;
         const uint64_t start = offsets[sg], n = offsets[sg + 1] - start, row = (uint64_t)sg * k;

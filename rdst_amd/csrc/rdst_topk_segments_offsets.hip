@@ -109,8 +109,6 @@ __global__ __launch_bounds__(PLAN_THREADS) void topk_segments_items_kernel(const
 
 // ---- host side -----------------------------------------------------------------------------------------------------------------
 
-bool misaligned(const void* p, uint64_t to) { return reinterpret_cast<uintptr_t>(p) % to != 0; }
-
 // The caller's scratch: header, the plan's pair arrays and their tmps, the item table, where rdst_segments_layout.h puts them.
 struct PlanScratch {
     uint32_t* hdr;
@@ -247,27 +245,15 @@ extern "C" int rdst_hip_topk_segments_device_offsets(const void* dev_keys, uint6
                                                      void* dev_scratch, uint64_t scratch_bytes, uint64_t far_capacity, uint32_t elem_bytes,
                                                      rdst_key_kind kind, uint32_t levels, uint32_t flags, void* stream) {
     // 1: the key arguments, len and flags, as rdst_hip_topk_segments_device checks them
-    if (int rc = rdst_internal::check_key_args(dev_keys, len, elem_bytes, kind, levels)) return rc;
-    if (kind == RDST_KEY_BYTES_BE) return set_error(RDST_ERR_UNSUPPORTED, "topk: [u8; N] keys are not built");
-    if (len >= (1ull << 32)) return set_error(RDST_ERR_UNSUPPORTED, "topk: len must be below 2^32");
+    if (int rc = rdst_internal::rank_check_head("topk", dev_keys, len, elem_bytes, kind, levels)) return rc;
     if (flags & ~RDST_TOPK_LARGEST) return set_error(RDST_ERR_ARG, "topk: unknown flag bits");
     // 2
     if (k == 0 || n_segments == 0) return RDST_OK;
     // 3: the table
     int rc = rdst_internal::check_offsets_table(dev_offsets, offset_bytes, n_segments, len);
     if (rc) return rc;
-    // 4: the outputs
-    if (dev_out_keys == nullptr) return set_error(RDST_ERR_ARG, "topk: null key output");
-    if (misaligned(dev_out_keys, elem_bytes)) return set_error(RDST_ERR_ALIGN, "topk: key output not aligned to the element size");
-    if (dev_out_index == nullptr) index_bytes = 0;
-    else {
-        if (index_bytes != 4 && index_bytes != 8) return set_error(RDST_ERR_ARG, "topk: index_bytes must be 4 or 8");
-        if (elem_bytes != 4 && elem_bytes != 8) return set_error(RDST_ERR_UNSUPPORTED, "topk: an index output takes 4- or 8-byte keys");
-        if (misaligned(dev_out_index, index_bytes)) return set_error(RDST_ERR_ALIGN, "topk: index output not aligned to index_bytes");
-    }
-    // 5: the scratch
-    if (dev_scratch == nullptr) return set_error(RDST_ERR_ARG, "topk: null scratch");
-    if (misaligned(dev_scratch, 256)) return set_error(RDST_ERR_ALIGN, "topk: scratch not aligned to 256 bytes");
+    // 4, 5: the outputs, the scratch
+    if ((rc = rdst_internal::rank_check_outputs("topk", dev_out_keys, dev_out_index, &index_bytes, dev_scratch, elem_bytes))) return rc;
     if (far_capacity >= (1ull << 32)) return set_error(RDST_ERR_ARG, "topk: far_capacity must be below 2^32 (pass len)");
     if (scratch_bytes < rdst_hip_topk_segments_device_offsets_scratch_bytes(n_segments, far_capacity, k, elem_bytes, index_bytes))
         return set_error(RDST_ERR_ARG, "topk: scratch_bytes is below rdst_hip_topk_segments_device_offsets_scratch_bytes(n_segments, far_capacity, k, elem_bytes, index_bytes)");
@@ -299,8 +285,7 @@ extern "C" int rdst_hip_debug_topk_segments_plan_device(const void* dev_offsets,
     if (n_segments == 0 || k == 0) return RDST_OK;
     if (len >= (1ull << 32)) return set_error(RDST_ERR_UNSUPPORTED, "topk: len must be below 2^32");
     if ((rc = rdst_internal::check_offsets_table(dev_offsets, offset_bytes, n_segments, len))) return rc;
-    if (dev_scratch == nullptr) return set_error(RDST_ERR_ARG, "topk: null scratch");
-    if (misaligned(dev_scratch, 256)) return set_error(RDST_ERR_ALIGN, "topk: scratch not aligned to 256 bytes");
+    if ((rc = rdst_internal::rank_check_scratch("topk", dev_scratch))) return rc;
     if (scratch_bytes < L::plan_layout(n_segments).total)
         return set_error(RDST_ERR_ARG, "topk: scratch_bytes is below rdst_hip_topk_segments_device_offsets_scratch_bytes(n_segments, 0, ...)");
     const PlanScratch P = plan_scratch(dev_scratch, n_segments);

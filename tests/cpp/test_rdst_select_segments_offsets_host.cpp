@@ -1,5 +1,5 @@
 // Stand-alone check of the host-only half of rdst_hip_select_segments_device_offsets (built by
-// tests/test_select_segments_offsets_abi.py with -fsanitize=address,undefined from rdst_select_segments_offsets.cpp and
+// tests/test_select_segments_offsets_abi.py with -fsanitize=address,undefined from rdst_rank_args.cpp and
 // rdst_segments.cpp): the scratch-size function over edge values — zeros, the sum it documents, monotone in every argument —,
 // and the plan it runs on: sorting the class keys of a table for k = 1 (rdst_segments_layout.h) gives the order of
 // rdst_topk_segments_plan with k = 1, with the stream class bounded (wait mode) and unbounded (asynchronous mode).
@@ -23,12 +23,9 @@ int note_error(int code, const char* what) {  // the library's own lives in rdst
     g_error = what;
     return code;
 }
+// the library's own lives in rdst_kernels.hip too; nothing here reaches the entries' checks, which call it
+int check_key_args(const void*, uint64_t, uint32_t, rdst_key_kind, uint32_t) { return note_error(RDST_ERR_ARG, "not reached"); }
 }  // namespace rdst_internal
-
-// the library's own lives in rdst_select.hip; here any pure function that is monotone in len and n_ranks will do
-extern "C" uint64_t rdst_hip_select_scratch_bytes(uint64_t len, uint64_t n_ranks, uint32_t elem_bytes, uint32_t index_bytes, uint64_t) {
-    return L::up256(len / 16 * elem_bytes) + L::up256(std::min<uint64_t>(n_ranks, 32) * (elem_bytes + index_bytes)) + 512;
-}
 
 #define CHECK(cond)                                                         \
     do {                                                                    \

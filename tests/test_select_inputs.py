@@ -27,7 +27,7 @@ def test_constants_are_the_library_s(hiplib):
             assert rc == 0 and tuple(out) == (S.MAX_RANKS, S.digit0_bits(kb), S.DIGIT_BITS, S.DEFAULT_CAND_CAPACITY, S.max_levels(kb, ib != 0)), (kb, ib)
     assert [S.max_levels(kb, False) for kb in (1, 2, 4, 8, 16)] == [1, 2, 4, 8, 16]
     assert S.max_levels(4, True) == 8 and S.max_levels(8, True) == 12
-    source = open(os.path.join(ROOT, "rdst_amd", "csrc", "rdst_select.hip")).read()
+    source = open(os.path.join(ROOT, "rdst_amd", "csrc", "rdst_select_layout.h")).read()
     assert f"constexpr uint32_t MAX_RANKS = {S.MAX_RANKS};" in source and "constexpr uint64_t DEFAULT_CAND_CAPACITY = 1ull << 24;" in source
 
 

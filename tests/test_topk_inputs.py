@@ -1,5 +1,5 @@
-"""tests/topk_inputs.py is what it claims: the constants are the library's (each found on the line of rdst_topk.hip that
-defines it, and in what rdst_hip_topk_limits answers), expected_topk agrees with the oracle's sorted output on the key bits
+"""tests/topk_inputs.py is what it claims: the constants are the library's (each found on the line of rdst_topk.hip,
+rdst_topk_layout.h or rdst_args.h that defines it, and in what rdst_hip_topk_limits answers), expected_topk agrees with the oracle's sorted output on the key bits
 and is the stable argsort the contract names, the restated level loop agrees with a statement of the depth that has no
 loop, and every case of tests/test_gpu_topk.py reaches the depth it is named for."""
 import os
@@ -12,7 +12,7 @@ import helpers as H
 import topk_inputs as T
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SOURCE = open(os.path.join(ROOT, "rdst_amd", "csrc", "rdst_topk.hip")).read()
+SOURCE = "".join(open(os.path.join(ROOT, "rdst_amd", "csrc", name)).read() for name in ("rdst_topk.hip", "rdst_topk_layout.h", "rdst_args.h"))
 UNSUPPORTED = -2
 
 

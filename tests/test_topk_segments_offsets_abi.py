@@ -52,7 +52,7 @@ def test_symbols_header_and_mirrors(hiplib):
     assert hpp.count("void topk_segments_device_offsets(") == 2 and hpp.count("std::size_t topk_segments_device_offsets_scratch_bytes(") == 2
     assert "template <typename T, typename Off, typename Idx>\nvoid topk_segments_device_offsets(" in hpp
     from rdst_amd import build as B
-    for unit in ("rdst_topk_segments_offsets.hip", "rdst_topk_segments_offsets.cpp"):
+    for unit in ("rdst_topk_segments_offsets.hip", "rdst_rank_args.cpp"):
         assert any(s.endswith(unit) for s in B.SOURCES)
     assert "fn rdst_hip_topk_segments_device_offsets(" in open(os.path.join(ROOT, "INTEGRATION.md")).read()
     # the asynchrony, and the cliff, are stated where callers read them
@@ -269,12 +269,12 @@ def test_cpp_source_compiles_and_links(tmp_path, hiplib):
 
 
 def test_host_half_under_sanitizers(tmp_path):
-    """rdst_topk_segments_offsets.cpp and rdst_segments.cpp with a main of their own, built with -fsanitize=address,undefined:
+    """rdst_rank_args.cpp and rdst_segments.cpp with a main of their own, built with -fsanitize=address,undefined:
     a sanitizer report or a failed check is a non-zero exit"""
     cxx = shutil.which("g++") or shutil.which("clang++") or "/opt/rocm/llvm/bin/clang++"
     exe = str(tmp_path / "test_rdst_topk_segments_offsets_host")
     cmd = [cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-I", os.path.join(ROOT, "include"),
-           os.path.join(ROOT, "tests", "cpp", "test_rdst_topk_segments_offsets_host.cpp"), os.path.join(CSRC, "rdst_topk_segments_offsets.cpp"),
+           os.path.join(ROOT, "tests", "cpp", "test_rdst_topk_segments_offsets_host.cpp"), os.path.join(CSRC, "rdst_rank_args.cpp"),
            os.path.join(CSRC, "rdst_segments.cpp"), "-o", exe]
     subprocess.run(cmd, check=True)
     r = subprocess.run([exe], capture_output=True, text=True)

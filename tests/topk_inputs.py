@@ -7,7 +7,7 @@ import numpy as np
 
 import helpers as H
 
-# the library's constants, quoted from rdst_amd/csrc/rdst_topk.hip (tests/test_topk_inputs.py looks each of them up)
+# the library's constants, quoted from rdst_amd/csrc/rdst_topk.hip and rdst_topk_layout.h (tests/test_topk_inputs.py looks each of them up)
 COUNTERS = 4096
 DIGIT_BITS_WIDE = 12
 DIGIT_BITS_BYTE = 8
